@@ -4,8 +4,13 @@
 warm-up, K timed forwards, frames/s = K*B*V / t -- without eval_fps's uninitialised
 intrinsics, its hard-coded 8 views and the CPU MANO step).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds what takes runs or passes of its
+own: the per-launch hipEvent timings behind `roofline` / `kernels` / `forward` (--instrument-every, --per-layer), the CPU
+oracle baseline with its parity check, and the fp16 (BASELINE configs[4]) leg.  --dump-outputs DIR writes the last timed
+step's outputs as DIR/<name>.npy (float32, seeded inputs: two builds can be compared output for output).
 
 Workload = BASELINE.json configs[2] (the configuration the metric is quoted on): B=32
 multi-view samples x V=8 views of 256x256 per GPU, ResNet50-paper backbone, cross-attention
@@ -90,6 +95,24 @@ def forward_block(dtype, total_flops, ms_step, fam, n_instr):
     fwd["step_floor_ms"] = {"mfma": round(t_mfma, 3), "hbm@8TB/s": round(t_hbm, 3), "sum_of_per_launch_floors": round(per_launch, 3)}
     fwd["frac_of_step_floor"] = round(max(t_mfma, t_hbm) / ms_step, 4)
     return fwd
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out, dirname):
+    """Writes each output tensor as DIR/<name>.npy in float32.  Arrays that do not fit their share of DUMP_BYTES (the smaller
+    ones are written whole first) are replaced by a fixed, seeded sample of their flattened elements, in index order."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = sorted(((k, v.detach().float().cpu().numpy()) for k, v in out.items()), key=lambda kv: kv[1].nbytes)
+    left = DUMP_BYTES - 4096 * len(arrs)   # room for the .npy headers
+    for i, (k, a) in enumerate(arrs):
+        share = left // (len(arrs) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+        left -= a.nbytes
 
 
 def cpu_baseline(cfg, sd, size, model, dev, min_seconds=10.0):
@@ -178,7 +201,8 @@ def launch_check(world: int, rank: int):
 
 def measure(args, world, rank, dev):
     """One workload in one arithmetic mode: W warm-up steps, K timed steps (barrier + synchronize on both sides, max over
-    ranks), then the roofline of the dominant kernel family.  Returns (JSON line dict on rank 0 else None, context)."""
+    ranks), the last step's outputs to --dump-outputs, then (--full) the roofline of the dominant kernel family.  Returns
+    (JSON line dict on rank 0 else None, context)."""
     bt, ch, V, B, size = WORKLOADS[args.workload]
     if args.batch:
         B = args.batch
@@ -221,9 +245,10 @@ def measure(args, world, rank, dev):
         step()
     if args.graphs:
         model.use_graphs(True)
-    every = args.instrument_every
-    model.set_profiling(True)          # fresh record list ...
-    model.set_profiling(False)         # ... paused until an instrumented step resumes it
+    every = args.instrument_every if args.full else 0
+    if args.full:
+        model.set_profiling(True)      # fresh record list ...
+        model.set_profiling(False)     # ... paused until an instrumented step resumes it
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -234,22 +259,26 @@ def measure(args, world, rank, dev):
         if instr:                      # hipEvent pairs around every conv/GEMM launch of this timed step
             model.set_profiling(2)
             n_instr += 1
-        step()
+        out = step()
         if instr:
             model.set_profiling(False)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:   # before anything else runs: gathered outputs are views of a reused buffer
+        dump_outputs(out, args.dump_outputs)
     graph_stats = model.graph_stats()
-    if n_instr == 0:                   # the roofline pass: same K steps, instrumented, not part of `value`
-        model.set_profiling(2)
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        n_instr = args.steps
-    recs = model.profile_records()
-    model.set_profiling(False)
+    recs = []
+    if args.full:
+        if n_instr == 0:               # the roofline pass: same K steps, instrumented, not part of `value`
+            model.set_profiling(2)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            n_instr = args.steps
+        recs = model.profile_records()
+        model.set_profiling(False)
     launches = model.launch_count()
     # what the communicator itself saw: its size, and from every rank its device and its own clock over the timed steps
     props = torch.cuda.get_device_properties(dev)
@@ -266,7 +295,7 @@ def measure(args, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    if rank == 0 and args.per_layer:
+    if rank == 0 and args.full and args.per_layer:
         lay = {}
         for r in recs:
             e = lay.setdefault(r["layer"], {"kernel": r["kernel"], "ms": 0.0, "flops": r["flops"], "bytes": r["bytes"], "n": 0})
@@ -276,7 +305,30 @@ def measure(args, world, rank, dev):
                  "gbs": v["bytes"] / (v["ms"] / v["n"] * 1e-3) / 1e9} for k, v in lay.items()]
         with open(args.per_layer, "w") as f:
             json.dump(rows, f, indent=1)
-    if rank == 0:
+    if rank != 0:
+        return None, (cfg, sd, size, model)
+    ms_step = elapsed / args.steps * 1e3
+    line = {
+        "metric": "samples/sec (BxV frames) eval_fps.py, 8-view 256x256; 21-kpt L2 vs reference",
+        "value": round(args.steps * B * V * world / elapsed, 2), "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic" if args.input == "nchw" else "synthetic uint8 480x640 frames + crop windows (prepared on the device)",
+        "config": {"workload": f"{ {'cfg3': 'BASELINE configs[2]', 'cfg2': 'BASELINE configs[1]', 'cfg1': 'BASELINE configs[0] (HO3D_HandMvNet.yaml shape)'}.get(args.workload, 'HRNet release-config backbone') }: B={B}/GPU x V={V} x {size}x{size}, "
+                               f"{'hrnet_' if cfg.is_hrnet else 'resnet'}{bt} backbone, d={cfg.feat_dim}, {args.fusion} x{cfg.fusion_layers}, GCN decoder",
+                   "global_batch": B * world, "views": V, "frame": size, "parallelism": f"sample-shard x{world}"},
+        "communicator": {"ranks_seen": ranks_seen, "backend": dist.get_backend() if world > 1 else None,
+                         "distinct_devices": len({(r["uuid"], r["pci_bus_id"], r["device"]) for r in ranks}),
+                         "collectives_per_step": (ranks[0]["collectives"] // max(args.warmup + args.steps + (args.steps if args.full and every == 0 else 0), 1)) if world > 1 else 0,
+                         "ranks": ranks},
+        "launches_per_forward": launches,
+        "timed_region": {"instrumented_steps": n_instr if every > 0 else 0,
+                         "note": "hipEvent pair around every conv/GEMM launch on the instrumented steps" if every > 0
+                                 else "no events in the timed region; roofline from a separate instrumented pass of the same steps"
+                                 if args.full else "no events in the timed region",
+                         "hipgraph": {"enabled": bool(args.graphs), "cached": graph_stats[0], "replays": graph_stats[1]}},
+    }
+    if args.full:
         # ---- roofline of the dominant kernel family from the live per-launch event timings.  Each launch carries its
         # algorithmic FLOPs (2*M*N*K over the real channels) and algorithmic HBM bytes (input pixels, weights, residual and
         # output rows moved once in the mode's storage type); the family's bound is whichever floor is higher:
@@ -319,37 +371,16 @@ def measure(args, world, rank, dev):
             roofline["executed_tflops"] = round(3 * tf, 2)
             roofline["executed_frac"] = round(3 * tf / d["peak_tflops"], 4)
             roofline["note"] = "algorithmic fp32 FLOPs; the fp16 matrix cores execute 3x that (hi*hi + lo*hi + hi*lo)"
-        ms_step = elapsed / args.steps * 1e3
         # dense algorithmic count for the ResNet workloads; for HRNet the executed FLOPs of the
         # conv/GEMM launches of one step (the engine's own 2*M*N*K accounting)
         total_flops = (sum(r["flops"] for r in recs) / max(n_instr, 1) if (cfg.is_hrnet or cfg.learnable_query)
                        else forward_flops(cfg, B, size))
-        line = {
-            "metric": "samples/sec (BxV frames) eval_fps.py, 8-view 256x256; 21-kpt L2 vs reference",
-            "value": round(args.steps * B * V * world / elapsed, 2), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-            "data": "synthetic" if args.input == "nchw" else "synthetic uint8 480x640 frames + crop windows (prepared on the device)",
-            "config": {"workload": f"{ {'cfg3': 'BASELINE configs[2]', 'cfg2': 'BASELINE configs[1]', 'cfg1': 'BASELINE configs[0] (HO3D_HandMvNet.yaml shape)'}.get(args.workload, 'HRNet release-config backbone') }: B={B}/GPU x V={V} x {size}x{size}, "
-                                   f"{'hrnet_' if cfg.is_hrnet else 'resnet'}{bt} backbone, d={cfg.feat_dim}, {args.fusion} x{cfg.fusion_layers}, GCN decoder",
-                       "global_batch": B * world, "views": V, "frame": size, "parallelism": f"sample-shard x{world}"},
-            "roofline": roofline,
-            "communicator": {"ranks_seen": ranks_seen, "backend": dist.get_backend() if world > 1 else None,
-                             "distinct_devices": len({(r["uuid"], r["pci_bus_id"], r["device"]) for r in ranks}),
-                             "collectives_per_step": (ranks[0]["collectives"] // max(args.warmup + args.steps + (args.steps if every == 0 else 0), 1)) if world > 1 else 0,
-                             "ranks": ranks},
-            "launches_per_forward": launches,
-            "timed_region": {"instrumented_steps": n_instr if every > 0 else 0,
-                             "note": "hipEvent pair around every conv/GEMM launch on the instrumented steps" if every > 0
-                                     else "no events in the timed region; roofline from a separate instrumented pass of the same steps",
-                             "hipgraph": {"enabled": bool(args.graphs), "cached": graph_stats[0], "replays": graph_stats[1]}},
-            "forward": forward_block(args.dtype, total_flops, ms_step, fam, n_instr),
-            "kernels": {k: {"ms_per_step": round(v["ms"] / n_instr, 3), "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
-                            "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1), "bound": v["bound"], "frac": round(v["frac"], 4)}
-                        for k, v in fam.items()},
-        }
-        return line, (cfg, sd, size, model)
-    return None, (cfg, sd, size, model)
+        line["roofline"] = roofline
+        line["forward"] = forward_block(args.dtype, total_flops, ms_step, fam, n_instr)
+        line["kernels"] = {k: {"ms_per_step": round(v["ms"] / n_instr, 3), "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
+                               "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1), "bound": v["bound"], "frac": round(v["frac"], 4)}
+                           for k, v in fam.items()}
+    return line, (cfg, sd, size, model)
 
 
 def main():
@@ -369,19 +400,30 @@ def main():
     ap.add_argument("--input", default="nchw", choices=["nchw", "frames"],
                     help="nchw = prepared fp32 batch (eval_fps.py protocol, the headline); frames = raw uint8 480x640 camera "
                          "frames + crop windows through hmv_forward_frames (SURVEY 8(f) row 4)")
-    ap.add_argument("--instrument-every", type=int, default=4,
-                    help="bracket every conv/GEMM launch with a hipEvent pair on every Nth timed step (N=1: every step; the "
-                         "events cost ~0.5 ms per instrumented cfg-3 step); 0: none in the timed region, roofline from a "
-                         "separate instrumented pass afterwards")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel figures from hipEvent-timed "
+                         "launches, the CPU oracle baseline and parity check, the fp16 (BASELINE configs[4]) leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--instrument-every", type=int, default=None,
+                    help="--full: bracket every conv/GEMM launch with a hipEvent pair on every Nth timed step (default 4; N=1: "
+                         "every step; the events cost ~0.5 ms per instrumented cfg-3 step); 0: none in the timed region, "
+                         "roofline from a separate instrumented pass afterwards")
     ap.add_argument("--graphs", action="store_true", help="opt into hipGraph replay for the un-instrumented steps")
-    ap.add_argument("--per-layer", default="", help="write per-layer launch timings (JSON) to this file")
+    ap.add_argument("--per-layer", default="", help="--full: write per-layer launch timings (JSON) to this file")
     ap.add_argument("--no-hr-fusion", action="store_true", help="A/B: HRNet fuse layers as one conv launch per term, one stream")
     ap.add_argument("--hr-mode", type=int, default=-1, help="A/B: hmv_set_hr_fusion mode (bit 0: fused fuse layers, bit 1: branch overlap)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the fp16 (BASELINE configs[4]) leg that the default full run appends as `configs4_fp16`")
+                    help="skip the fp16 (BASELINE configs[4]) leg that a --full run appends as `configs4_fp16`")
     ap.add_argument("--launch-check", action="store_true",
                     help="only exercise the rank launch / rendezvous / relay path (gloo, no GPU work): CPU test of --gpus N")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.per_layer or args.instrument_every is not None):
+        ap.error("--per-layer and --instrument-every need --full")
+    if args.instrument_every is None:
+        args.instrument_every = 4
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -408,19 +450,19 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
 
     line, (cfg, sd, size, model) = measure(args, world, rank, dev)
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_cpu_baseline:
             cb, rel = cpu_baseline(cfg, sd, size, model, dev, args.cpu_seconds)
             line["cpu_baseline"] = cb
             line["parity_rel_l2_vs_oracle"] = float(f"{rel:.3e}")
         else:
             line["cpu_baseline"] = None
-        # BASELINE configs[4] (the fp16 path) in the same default run, so that the driver's own record of `python bench.py`
-        # carries a number for it too: same workload, same K / W, no events in its timed region.  Not `value`.
+        # BASELINE configs[4] (the fp16 path) in the same --full run, so that the record of `python bench.py --full` carries a
+        # number for it too: same workload, same K / W, no events in its timed region.  Not `value`.
         if (world == 1 and args.dtype == "f32" and args.workload == "cfg3" and not args.batch and args.input == "nchw"
                 and not args.no_cpu_baseline and not args.no_secondary):
             a2 = argparse.Namespace(**vars(args))
-            a2.dtype, a2.per_layer, a2.instrument_every = "f16", "", 0
+            a2.dtype, a2.per_layer, a2.instrument_every, a2.dump_outputs = "f16", "", 0, ""
             x1, b1, i1 = synth_inputs(cfg, 1, 4242, size)
             probe = (torch.from_numpy(x1).to(dev), torch.from_numpy(b1).to(dev), {"intrinsic": torch.from_numpy(i1).to(dev)})
             ref32 = model(*probe)["joints_cam"].float().cpu().numpy()
@@ -440,6 +482,7 @@ def main():
                            "rounded to fp16, lands the noise floor above away from its fp32 run; tests hold the engine to 3x that floor "
                            "(DESIGN.md section 4, tests/test_gpu_parity.py)")
             line["configs4_fp16"] = sec
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -124,3 +124,71 @@ def test_pmc_summary_names_the_round3_kernels_like_the_engine_does():
     assert ps.family("void hmv::conv_igemm<float, 128, 128, 2, 2, 2, false, 32, false, true, false, false>(hmv::ConvParams)") == "conv_igemm_f32<128x128,dense,rowsum>"
     assert ps.family("_ZN3hmv10conv_igemmIDF16_Li64ELi64ELi2ELi2ELi0ELb0ELi32ELb0ELb0ELb0ELb1EEvNS_10ConvParamsE") == "conv_igemm_f16<64x64,taps,c32>"
     assert ps.family("_ZN3hmv10conv_igemmIDF16_Li256ELi256ELi2ELi4ELi3ELb0ELi64ELb0ELb0ELb0ELb0EEvNS_10ConvParamsE") == "conv_igemm_f16<256x256,halo>"
+
+
+def test_per_layer_and_instrument_every_need_full():
+    for extra in (["--per-layer", "pl.json"], ["--instrument-every", "1"]):
+        r = _run(["--gpus", "1", "--steps", "2"] + extra)
+        assert r.returncode == 2 and "need --full" in r.stderr, r.stderr[-2000:]
+
+
+def test_dump_outputs_writes_float32_and_samples_what_does_not_fit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4096 + 40000)
+    g = torch.Generator().manual_seed(0)
+    out = {"joints_cam": torch.randn(2, 21, 3, generator=g, dtype=torch.float64),
+           "joints_crop_img": torch.randn(2, 8, 21, 2, generator=g),
+           "heatmap": torch.randn(2, 8, 21, 32, 32, generator=g)}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in out}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["joints_cam"], out["joints_cam"].float().numpy())      # small arrays whole
+    assert np.array_equal(got["joints_crop_img"], out["joints_crop_img"].numpy())
+    hm = got["heatmap"]
+    assert 0 < hm.size < out["heatmap"].numel() and sum(a.nbytes for a in got.values()) <= bench.DUMP_BYTES
+    assert np.isin(hm, out["heatmap"].numpy()).all()                                   # a sample of the real elements
+    assert np.array_equal(hm, np.load(tmp_path / "b" / "heatmap.npy"))                 # the same sample every time
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain run prints the headline fields only (no roofline / CPU baseline: those are --full's) and --dump-outputs
+    writes the last timed step's outputs: those of the model on the benchmark's seeded weights and inputs."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from handmvnet_amd import HandMvNet
+    from handmvnet_amd.spec import config_from_params
+    from handmvnet_amd.synth import synth_inputs, synth_state_dict
+    r = _run(["--gpus", "1", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip())
+    assert line["steps"] == 3 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 3 * 1 * 4 / (3 * line["ms_per_step"] * 1e-3)) < 0.01 * line["value"]
+    assert "roofline" not in line and "cpu_baseline" not in line
+    tp, mp, dp = bench.params(*bench.WORKLOADS["cfg1"])
+    cfg = config_from_params(tp, mp, dp)
+    model = HandMvNet(tp, mp, dp)
+    model.load_state_dict(synth_state_dict(cfg, 1), strict=True)
+    x, bbox, intr = synth_inputs(cfg, 1, 1000, 128)
+    dev = torch.device("cuda:0")
+    ref = model(torch.from_numpy(x).to(dev), torch.from_numpy(bbox).to(dev), {"intrinsic": torch.from_numpy(intr).to(dev)})
+    for k, v in ref.items():
+        got = np.load(tmp_path / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape == tuple(v.shape)
+        np.testing.assert_allclose(got, v.cpu().numpy(), rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_roofline_and_the_cpu_baseline():
+    r = _run(["--gpus", "1", "--workload", "cfg1", "--steps", "4", "--warmup", "1", "--full", "--cpu-seconds", "0.5"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip())
+    assert line["steps"] == 4 and line["timed_region"]["instrumented_steps"] == 1
+    assert line["roofline"]["kernel"] in line["kernels"] and line["forward"]["tflops"] > 0
+    assert line["cpu_baseline"]["value"] > 0 and line["parity_rel_l2_vs_oracle"] < 1e-3

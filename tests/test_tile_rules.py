@@ -1,5 +1,5 @@
 """The launcher's tile rules (conv_igemm.hip::conv_pick_tile) for the shapes they were measured on: host logic, no GPU.  Every
-expectation below is a measured choice recorded in DESIGN.md (forced-tile runs of bench.py --per-layer); a change here should come
+expectation below is a measured choice recorded in DESIGN.md (forced-tile runs of bench.py --full --per-layer); a change here should come
 with a new measurement."""
 import pytest
 

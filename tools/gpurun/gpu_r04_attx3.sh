@@ -9,13 +9,13 @@ timeout -k 10 200 python tools/att_probe.py --x3 > $O/att_x3.txt 2>&1 || { tail 
 timeout -k 10 200 python tools/att_probe.py > $O/att_f32.txt 2>&1 || { tail -5 $O/att_f32.txt; exit 62; }
 echo x3; grep "B=" $O/att_x3.txt; echo f32; grep "B=" $O/att_f32.txt
 for r in 1 2; do
-timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary > $O/b_ax_$r.json 2> $O/b_ax.err || exit 52
-HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary > $O/b_noax_$r.json 2> $O/b_noax.err || exit 53
+timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary > $O/b_ax_$r.json 2> $O/b_ax.err || exit 52
+HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary > $O/b_noax_$r.json 2> $O/b_noax.err || exit 53
 done
-timeout -k 10 300 python bench.py --dtype f32x3 --no-cpu-baseline --no-secondary > $O/b_ax_x3.json 2> $O/b_ax_x3.err || exit 54
-HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --dtype f32x3 --no-cpu-baseline --no-secondary > $O/b_noax_x3.json 2> $O/b_noax_x3.err || exit 55
-timeout -k 10 300 python bench.py --dtype f16 --batch 1 --no-cpu-baseline --no-secondary --steps 200 --warmup 20 --instrument-every 0 > $O/b_ax_b1.json 2> $O/b_ax_b1.err || exit 56
-HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --dtype f16 --batch 1 --no-cpu-baseline --no-secondary --steps 200 --warmup 20 --instrument-every 0 > $O/b_noax_b1.json 2> $O/b_noax_b1.err || exit 57
+timeout -k 10 300 python bench.py --full --dtype f32x3 --no-cpu-baseline --no-secondary > $O/b_ax_x3.json 2> $O/b_ax_x3.err || exit 54
+HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --full --dtype f32x3 --no-cpu-baseline --no-secondary > $O/b_noax_x3.json 2> $O/b_noax_x3.err || exit 55
+timeout -k 10 300 python bench.py --full --dtype f16 --batch 1 --no-cpu-baseline --no-secondary --steps 200 --warmup 20 --instrument-every 0 > $O/b_ax_b1.json 2> $O/b_ax_b1.err || exit 56
+HMV_LIB=build/libhandmv_noax.so timeout -k 10 300 python bench.py --full --dtype f16 --batch 1 --no-cpu-baseline --no-secondary --steps 200 --warmup 20 --instrument-every 0 > $O/b_noax_b1.json 2> $O/b_noax_b1.err || exit 57
 python - <<'PY'
 import json
 for n in ("b_ax_1", "b_noax_1", "b_ax_2", "b_noax_2", "b_ax_x3", "b_noax_x3", "b_ax_b1", "b_noax_b1"):

@@ -4,8 +4,8 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "gem
 tail -3 $O/tests_g8p.log
 [ $rc -eq 0 ] || exit $rc
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_g8p_$r.json > $O/b_g8p_$r.json 2> $O/b_g8p.err || exit 52
-  HMV_LIB=build/libhandmv_htp.so timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nog8p_$r.json > $O/b_nog8p_$r.json 2> $O/b_nog8p.err || exit 53
+  timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_g8p_$r.json > $O/b_g8p_$r.json 2> $O/b_g8p.err || exit 52
+  HMV_LIB=build/libhandmv_htp.so timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nog8p_$r.json > $O/b_nog8p_$r.json 2> $O/b_nog8p.err || exit 53
 done
 python - <<'PY'
 import json

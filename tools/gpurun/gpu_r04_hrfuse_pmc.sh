@@ -1,7 +1,7 @@
 # round 4: PMC pass on the hr40 fp16 workload to see what the fused fuse-layer launch spends its cycles on
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04hrf; mkdir -p $O
-B="python3 bench.py --workload hr40 --dtype f16 --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --full --workload hr40 --dtype f16 --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY --output-format csv -d $O/sq1 -- $B > $O/b1.json 2> $O/sq1.err || exit 33
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_SMEM SQ_WAIT_ANY SQ_WAVES --output-format csv -d $O/sq2 -- $B > $O/b2.json 2> $O/sq2.err || exit 34
 python3 - <<'PY'

@@ -4,8 +4,8 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "tal
 tail -3 $O/tests_htp.log
 [ $rc -eq 0 ] || exit $rc
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_htp_$r.json > $O/b_htp_$r.json 2> $O/b_htp.err || exit 52
-  HMV_LIB=build/libhandmv_k16.so timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nohtp_$r.json > $O/b_nohtp_$r.json 2> $O/b_nohtp.err || exit 53
+  timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_htp_$r.json > $O/b_htp_$r.json 2> $O/b_htp.err || exit 52
+  HMV_LIB=build/libhandmv_k16.so timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nohtp_$r.json > $O/b_nohtp_$r.json 2> $O/b_nohtp.err || exit 53
 done
 python - <<'PY'
 import json

@@ -6,8 +6,8 @@ grep -v Warning $O/tests_m16.log | tail -8
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 ./tools/probe/copybw > $O/probe_copy.txt 2>&1 || exit 61
 cat $O/probe_copy.txt
-timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --per-layer $O/per_layer_f16_m16.json > $O/bench_f16_m16.json 2> $O/bench_f16_m16.err || { tail -20 $O/bench_f16_m16.err; exit 52; }
-timeout -k 10 300 python bench.py --workload cfg3 --batch 1 --dtype f16 --no-cpu-baseline --steps 200 --warmup 20 --instrument-every 0 > $O/bench_b1_f16_m16.json 2> $O/bench_b1_f16.err || exit 55
+timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --per-layer $O/per_layer_f16_m16.json > $O/bench_f16_m16.json 2> $O/bench_f16_m16.err || { tail -20 $O/bench_f16_m16.err; exit 52; }
+timeout -k 10 300 python bench.py --full --workload cfg3 --batch 1 --dtype f16 --no-cpu-baseline --steps 200 --warmup 20 --instrument-every 0 > $O/bench_b1_f16_m16.json 2> $O/bench_b1_f16.err || exit 55
 python - <<'PY'
 import json
 for n in ("bench_f16_m16", "bench_b1_f16_m16"):

@@ -1,7 +1,7 @@
 # round 4: rocprofv3 passes of the bench command on the final code (kernel stats; then PMC in separate passes, never combined with other traces)
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04prof; mkdir -p $O
-B="python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline"
+B="python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_f32 -- $B > $O/bench_under_rocprof_f32.json 2> $O/stats_f32.err || exit 31
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_f16 -- $B --dtype f16 > $O/bench_under_rocprof_f16.json 2> $O/stats_f16.err || exit 32
 echo "stats done"

@@ -5,8 +5,8 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "str
 tail -3 $O/tests_stemswz.log
 [ $rc -eq 0 ] || exit $rc
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_swz$r.json > $O/b_swz$r.json 2> $O/b_swz.err || exit 52
-  HMV_LIB=build/libhandmv_dev.so timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_ref$r.json > $O/b_ref$r.json 2> $O/b_ref.err || exit 53
+  timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_swz$r.json > $O/b_swz$r.json 2> $O/b_swz.err || exit 52
+  HMV_LIB=build/libhandmv_dev.so timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_ref$r.json > $O/b_ref$r.json 2> $O/b_ref.err || exit 53
 done
 python - <<'PY'
 import json

@@ -5,11 +5,11 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "spl
 tail -3 $O/tests_x3k16.log
 [ $rc -eq 0 ] || exit $rc
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_k16_$r.json > $O/b_k16_$r.json 2> $O/b_k16.err || exit 52
-  HMV_LIB=build/libhandmv_nosplit.so timeout -k 10 300 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nok16_$r.json > $O/b_nok16_$r.json 2> $O/b_nok16.err || exit 53
+  timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_k16_$r.json > $O/b_k16_$r.json 2> $O/b_k16.err || exit 52
+  HMV_LIB=build/libhandmv_nosplit.so timeout -k 10 300 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --per-layer $O/pl_nok16_$r.json > $O/b_nok16_$r.json 2> $O/b_nok16.err || exit 53
 done
-timeout -k 10 300 python bench.py --dtype f32x3 --no-cpu-baseline > $O/b_k16_x3.json 2> $O/b_k16_x3.err || exit 54
-HMV_LIB=build/libhandmv_nosplit.so timeout -k 10 300 python bench.py --dtype f32x3 --no-cpu-baseline > $O/b_nok16_x3.json 2> $O/b_nok16_x3.err || exit 55
+timeout -k 10 300 python bench.py --full --dtype f32x3 --no-cpu-baseline > $O/b_k16_x3.json 2> $O/b_k16_x3.err || exit 54
+HMV_LIB=build/libhandmv_nosplit.so timeout -k 10 300 python bench.py --full --dtype f32x3 --no-cpu-baseline > $O/b_nok16_x3.json 2> $O/b_nok16_x3.err || exit 55
 python - <<'PY'
 import json
 for n in ("b_k16_1", "b_nok16_1", "b_k16_2", "b_nok16_2", "b_k16_x3", "b_nok16_x3"):

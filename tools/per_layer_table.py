@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/rNN_per_layer_<dtype>.json (bench.py --per-layer) -> a markdown table: every conv / GEMM launch of one step with its
+"""profiles/rNN_per_layer_<dtype>.json (bench.py --full --per-layer) -> a markdown table: every conv / GEMM launch of one step with its
 algorithmic FLOPs and bytes, both floors (MFMA peak of the dtype it multiplies in, HBM at 8 TB/s) and the fraction of the higher one.
 usage: python tools/per_layer_table.py profiles/r02_per_layer_f32.json f32 > profiles/r02_per_layer_f32.md"""
 import json, sys

@@ -697,15 +697,9 @@ __global__ __launch_bounds__(512, 2) void conv_gemm8r_f16(const ConvParams p) {
 }
 
 // ====================================================================== host side
-static int g_gemm8_mode = -1;   // -1: the launcher's rule (HMV_NO_GEMM8=1 disables it); 0 never; 1 whenever supported (op-level tests)
-void conv_gemm8_set_mode(int mode) { g_gemm8_mode = mode; }
-static int g_gemm8_persist = 1;   // 1: the persistent form from two tiles per CU up; 0: never; 2: wherever it exists (op-level identity tests)
-void conv_gemm8_set_persistent(int on) { g_gemm8_persist = on; }
-
-bool conv_gemm8_supported(const ConvParams &p) {
-    static int off = -1;   // development knob: HMV_NO_GEMM8=1 keeps these convs on conv_igemm (A/B runs)
-    if (off < 0) off = HMV_DEV_ENV("HMV_NO_GEMM8") ? 1 : 0;
-    if (g_gemm8_mode == 0 || (g_gemm8_mode < 0 && off)) return false;
+// route.gemm8: the launcher's rule, never, or whenever supported (op-level tests)
+bool conv_gemm8_supported(const ConvParams &p, const ConvRoute &route) {
+    if (route.gemm8 == ROUTE_NEVER) return false;
     if (!p.in_f16 || !p.out_f16 || p.res || p.R != 1 || p.S != 1 || p.pad_h || p.pad_w || p.up || p.ksl > 1 || p.phases > 1) return false;
     if (p.cwrap || p.x3_plane || p.res_split || p.out_split || p.acc_shift || p.rd_cout || p.scatter || p.rg_out) return false;
     if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
@@ -721,35 +715,23 @@ bool conv_gemm8_supported(const ConvParams &p) {
         return false;
     }
     if ((long long)p.M * (p.lda ? p.lda : p.Cin) >= (1ll << 31)) return false;   // 32-bit element offsets of the pixel rows
-    if (g_gemm8_mode > 0) return true;
+    if (route.gemm8 == ROUTE_FORCE) return true;
     // the launcher's rule: the shapes conv_pick_tile gives the 256 x 256 tile (Cout > 128, >= 512 tiles)
     return p.Cout > 128 && (long long)((p.M + 255) / 256) * ((p.Cout + 255) / 256) >= 512;
 }
 
-hipError_t launch_conv_gemm8(ConvParams p, hipStream_t s, const char **name) {
+hipError_t launch_conv_gemm8(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route) {
     constexpr size_t lds = (size_t)2 * 4 * 128 * 64 * sizeof(_Float16);
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8_f16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8_f16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8_f16<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8_f16<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    hipError_t e = once.run([](int) { return set_max_lds(lds, conv_gemm8_f16<false>, conv_gemm8_f16<true>, conv_gemm8_f16<false, true>, conv_gemm8_f16<true, true>); });
+    if (e != hipSuccess) return e;
     p.mtiles = (p.M + 255) / 256;
     p.ntiles = (p.Cout + 255) / 256;
     // the persistent form (16x16x32 only): from two tiles per CU up, channel-tile counts that divide an XCD's 32 workgroups
-    if (p.m16 && g_gemm8_persist && ((long long)p.mtiles * p.ntiles >= 512 || g_gemm8_persist == 2) && (p.ntiles == 1 || p.ntiles == 2 || p.ntiles == 4)) {
-        static bool pconf[64] = {};
-        if (!pconf[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8p_f16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8p_f16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + 1024);
-            if (e != hipSuccess) return e;
-            pconf[dev] = true;
-        }
+    const int persist = route.gemm8_persist;
+    if (p.m16 && persist && ((long long)p.mtiles * p.ntiles >= 512 || persist == 2) && (p.ntiles == 1 || p.ntiles == 2 || p.ntiles == 4)) {
+        static DeviceOnce ponce;
+        if ((e = ponce.run([](int) { return set_max_lds(lds + 1024, conv_gemm8p_f16<false>, conv_gemm8p_f16<true>); })) != hipSuccess) return e;
         if (name) *name = p.in2 ? "conv_gemm8_f16<256x256,1x1,dual,m16,persistent>" : "conv_gemm8_f16<256x256,1x1,m16,persistent>";
         if (p.in2) hipLaunchKernelGGL(conv_gemm8p_f16<true>, dim3(256), dim3(512), lds + 1024, s, p);
         else hipLaunchKernelGGL(conv_gemm8p_f16<false>, dim3(256), dim3(512), lds + 1024, s, p);
@@ -765,15 +747,10 @@ hipError_t launch_conv_gemm8(ConvParams p, hipStream_t s, const char **name) {
     // development knob, OFF by default: HMV_GEMM8_RING=1 selects conv_gemm8r_f16 (wave-specialised operand streams on a k32 ring).
     // Measured 6 % SLOWER than the four-phase loop (layer3 conv1 172 vs 162 us, profiles/r03_probe_gemm8_ring.txt): these launches are
     // bound by power, not by request latency (0.68 MFMA-busy in cycles at a 1.06-1.35 GHz clock on dense operands)
-    static const int ring = HMV_DEV_ENV("HMV_GEMM8_RING") ? atoi(HMV_DEV_ENV("HMV_GEMM8_RING")) : 0;
+    static const int ring = HMV_DEV_INT("HMV_GEMM8_RING", 0);
     if (ring) {
-        static bool rconf[64] = {};
-        if (!rconf[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8r_f16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, G8R_LDS);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm8r_f16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, G8R_LDS);
-            if (e != hipSuccess) return e;
-            rconf[dev] = true;
-        }
+        static DeviceOnce ronce;
+        if ((e = ronce.run([](int) { return set_max_lds(G8R_LDS, conv_gemm8r_f16<false>, conv_gemm8r_f16<true>); })) != hipSuccess) return e;
         if (p.in2) hipLaunchKernelGGL(conv_gemm8r_f16<true>, dim3(p.mtiles * p.ntiles), dim3(512), G8R_LDS, s, p);
         else hipLaunchKernelGGL(conv_gemm8r_f16<false>, dim3(p.mtiles * p.ntiles), dim3(512), G8R_LDS, s, p);
         return hipGetLastError();

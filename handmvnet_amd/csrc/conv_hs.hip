@@ -564,9 +564,6 @@ __global__ __launch_bounds__(512, 2) void conv_hs_stem_f32(const ConvParams p) {
 }
 
 // ====================================================================== host side
-static int g_hs_mode = -1;   // -1: the launcher's rule (HMV_NO_HS=1 disables it); 0 never; 1 whenever supported (op-level tests)
-void conv_hs_set_mode(int mode) { g_hs_mode = mode; }
-
 // 0: no instantiation; 1: 3x3 pad 1, 64 -> 64 channels; 2: the 4x4 space-to-depth stem, 16 -> 64 channels; 3 / 4: 3x3 pad 1, 40 -> 40 /
 // 80 -> 80 channels in the plain (r, s, c) K order (HRNet-w40's two highest-resolution branches, hrnet.py:96-221; kind 4 on 8 x 16
 // blocks under three waves)
@@ -584,25 +581,25 @@ static bool hs_stem32(const ConvParams &p) {
     return !p.in_f16 && !p.out_f16 && !p.res && p.R == 4 && p.S == 4 && p.pad_h == 2 && p.pad_w == 2 && p.Cin == 12 && p.Cout == 64 && p.Kpad == 192 && p.K == 192;
 }
 
-bool conv_hs_supported(const ConvParams &p) {
-    static int off = -1;   // development knob: HMV_NO_HS=1 keeps these convs on conv_igemm (A/B runs)
-    if (off < 0) off = HMV_DEV_ENV("HMV_NO_HS") ? 1 : 0;
-    if (g_hs_mode == 0 || (g_hs_mode < 0 && off)) return false;
+// route.hs: the launcher's rule, never, or whenever supported (op-level tests)
+bool conv_hs_supported(const ConvParams &p, const ConvRoute &route) {
+    if (route.hs == ROUTE_NEVER) return false;
+    const bool force = route.hs == ROUTE_FORCE;
     if (p.pool) {   // conv + ReLU + MaxPool2d(3, 2, 1) in one launch: the fp16 stem only, at least four 7 x 7 pooled blocks per workgroup
         static const bool nopool = HMV_DEV_ENV("HMV_NO_STEMPOOL") != nullptr;   // development knob (A/B runs)
         if (nopool || hs_kind(p) != 2 || !p.in_f16 || !p.out_f16 || p.res || p.fill || p.act != ACT_RELU) return false;
         if (p.pool_h != (p.Ho + 2 - 3) / 2 + 1 || p.pool_w != (p.Wo + 2 - 3) / 2 + 1 || p.ldc != 64 || (p.Ho & 1) || (p.Wo & 1) || p.acc_shift) return false;
-        if (g_hs_mode <= 0 && (long long)p.N * ((p.pool_h + 6) / 7) * ((p.pool_w + 6) / 7) < 4 * 256) return false;
+        if (!force && (long long)p.N * ((p.pool_h + 6) / 7) * ((p.pool_w + 6) / 7) < 4 * 256) return false;
     }
     if (hs_stem32(p)) {
         static const bool off32 = HMV_DEV_ENV("HMV_NO_HS32") != nullptr;   // development knob (A/B runs)
-        if (off32 && g_hs_mode <= 0) return false;
+        if (off32 && !force) return false;
         if (p.stride != 1 || p.up || p.in2 || p.ksl > 1 || p.phases > 1 || p.Ho != p.H || p.Wo != p.W || (p.H & 15) || (p.W & 15)) return false;
         if (p.cwrap || p.x3_plane || p.res_split || p.out_split || p.acc_shift || p.rd_cout || p.scatter || p.rg_out || p.fill) return false;
         if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
         if ((p.lda ? p.lda : p.Cin) != 12 || ((p.ldw ? p.ldw : p.Kpad) & 3) || (p.ldc & 3) || p.ldc < 64) return false;
         if ((long long)p.N * p.H * p.W * 12 >= (1ll << 31)) return false;
-        if (g_hs_mode > 0) return true;
+        if (force) return true;
         return (long long)p.N * (p.H >> 4) * (p.W >> 4) >= 4 * 256;
     }
     if (!hs_kind(p) || !p.in_f16 || !p.out_f16 || (p.res && !p.res_f16)) return false;
@@ -612,7 +609,7 @@ bool conv_hs_supported(const ConvParams &p) {
     if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
     if ((p.lda ? p.lda : p.Cin) != p.Cin || ((p.ldw ? p.ldw : p.Kpad) & 7) || (p.ldc & 7) || (p.res && (p.ldr & 7))) return false;
     if ((long long)p.N * p.H * p.W * p.Cin >= (1ll << 31)) return false;   // 32-bit element offsets of the halo pixels
-    if (g_hs_mode > 0) return true;
+    if (force) return true;
     return (long long)p.N * (p.H / hs_bh(hs_kind(p))) * (p.W >> 4) >= 4 * 256;   // at least four blocks per workgroup
 }
 
@@ -622,15 +619,9 @@ static hipError_t launch_hs_one(const ConvParams &p, hipStream_t s) {
     constexpr int HROWS = (BH + R - 1) * (16 + S - 1), HP = (HROWS * CPP + NT - 1) / NT;
     constexpr size_t lds = (size_t)NSLOT * HP * NT * 16 + (HAS_RES ? (size_t)2 * NWV * TM * TN * 2 * 1024 : 0) + (POOL ? 256 * 128 : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool configured[64] = {};
     auto kern = conv_hs_f16<R, S, CPP, TM, TN, MW, NW, NSLOT, HAS_RES, POOL>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
     const int nblk = POOL ? p.N * ((p.pool_h + 6) / 7) * ((p.pool_w + 6) / 7) : p.N * (p.H / BH) * (p.W >> 4);
     const int cap = NT == 256 ? 512 : 256;   // four-wave workgroups: two per CU
     hipLaunchKernelGGL(kern, dim3(nblk < cap ? nblk : cap), dim3(NT), lds, s, p);
@@ -641,14 +632,8 @@ hipError_t launch_conv_hs(const ConvParams &p, hipStream_t s, const char **name)
     if (hs_stem32(p)) {
         constexpr int NSLOT = 4, HP = (19 * 19 * 3 + 511) / 512;
         constexpr size_t lds = (size_t)NSLOT * HP * 512 * 16;
-        static bool configured[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_hs_stem_f32<NSLOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
+        static DeviceOnce once;
+        if (const hipError_t e = once.run([](int) { return set_max_lds(lds, conv_hs_stem_f32<NSLOT>); }); e != hipSuccess) return e;
         if (name) *name = "conv_hs_stem_f32<4x4,12->64>";
         const int nblk = p.N * (p.H >> 4) * (p.W >> 4);
         hipLaunchKernelGGL(conv_hs_stem_f32<NSLOT>, dim3(nblk < 256 ? nblk : 256), dim3(512), lds, s, p);

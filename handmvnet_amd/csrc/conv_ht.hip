@@ -486,54 +486,35 @@ __global__ __launch_bounds__(512) void conv_htp_f16(const ConvParams p) {
 }
 
 // ====================================================================== host side
-static int g_ht_mode = -1;   // -1: launch_conv's rule (enough tiles to fill the chip); 0 never, 1 always (op-level tests)
-void conv_ht_set_mode(int mode) { g_ht_mode = mode; }
-int conv_ht_mode() { return g_ht_mode; }
-// MFMA shape of the tall-tile layers: 1 = 16x16x32 (the engine's: 12-15 % less time, profiles/r04_probe_mfma_shape.txt), 0 = 32x32x16 (the
-// A/B partner, hmv_op_conv2d_f16 kernel_sel 5 / 6).  A property of the BUILD, not of a launch: every batch size runs the same shape.
-static int g_ht_m16 = 1;
-void conv_ht_set_shape(int m16) { g_ht_m16 = m16; }
-static int g_ht_persist = 1;   // 1: the persistent form from two tiles per CU up; 0: never; 2: wherever it exists (op-level identity tests)
-void conv_ht_set_persistent(int on) { g_ht_persist = on; }
-int conv_ht_shape() { return g_ht_m16; }
-
 // shape rule (the engine asks it at weight-packing time and at launch: the same answer for every batch)
 bool conv_ht_shape_ok(int R, int S, int stride, int pad, int Cin, int Cout, int H, int W) {
-    static int off = -1;   // development knob: HMV_NO_HT=1 keeps these layers on conv_igemm's 256 x 256 halo tiles (A/B runs)
-    if (off < 0) off = HMV_DEV_ENV("HMV_NO_HT") ? 1 : 0;
+    static const bool off = HMV_DEV_ENV("HMV_NO_HT") != nullptr;   // development knob: HMV_NO_HT=1 keeps these layers on conv_igemm's 256 x 256 halo tiles (A/B runs)
     return !off && R == 3 && S == 3 && stride == 1 && pad == 1 && Cin % 32 == 0 && Cin >= 64 && Cout % 128 == 0 && H % 16 == 0 && W % 32 == 0 &&
            H > 0 && W > 0;
 }
 
-hipError_t launch_conv_ht(ConvParams p, hipStream_t s, const char **name) {
+// route.ht_m16: the MFMA shape, 1 = 16x16x32 (the engine's: 12-15 % less time, profiles/r04_probe_mfma_shape.txt), 0 = 32x32x16 (the A/B
+// partner, hmv_op_conv2d_f16 kernel_sel 5 / 6).  The engine never changes it: every batch size runs the same shape.
+hipError_t launch_conv_ht(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route) {
     if (!p.in_f16 || !p.out_f16 || p.res || !conv_ht_shape_ok(p.R, p.S, p.stride, p.pad_h, p.Cin, p.Cout, p.H, p.W) || p.pad_w != 1 || p.Ho != p.H ||
         p.Wo != p.W || p.up || p.in2 || p.ksl > 1 || p.phases > 1 || p.cwrap || p.x3_plane || p.out_split || p.acc_shift || p.rd_cout ||
         p.scatter || p.rg_out || (p.act != ACT_NONE && p.act != ACT_RELU) || (p.lda & 7) || p.lda < p.Cin || (p.ldw & 7) || (p.ldc & 7) || p.Kpad < 9 * p.Cin)
         return hipErrorInvalidValue;
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_ht_f16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, HT_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_ht_f16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, HT_LDS);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    hipError_t e = once.run([](int) { return set_max_lds(HT_LDS, conv_ht_f16<false>, conv_ht_f16<true>); });
+    if (e != hipSuccess) return e;
     p.mtiles = p.N * (p.H >> 4) * (p.W >> 5);
     p.ntiles = p.Cout / 128;
     // the persistent form (16x16x32 only: the engine's shape): from two tiles per CU up, channel tiles that divide an XCD's 32 workgroups
-    if (g_ht_m16 && g_ht_persist && ((long long)p.mtiles * p.ntiles >= 512 || g_ht_persist == 2) && (p.ntiles == 1 || p.ntiles == 2 || p.ntiles == 4)) {
-        static bool pconf[64] = {};
-        if (!pconf[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_htp_f16), hipFuncAttributeMaxDynamicSharedMemorySize, HT_LDS + 512);
-            if (e != hipSuccess) return e;
-            pconf[dev] = true;
-        }
+    const int persist = route.ht_persist;
+    if (route.ht_m16 && persist && ((long long)p.mtiles * p.ntiles >= 512 || persist == 2) && (p.ntiles == 1 || p.ntiles == 2 || p.ntiles == 4)) {
+        static DeviceOnce ponce;
+        if ((e = ponce.run([](int) { return set_max_lds(HT_LDS + 512, conv_htp_f16); })) != hipSuccess) return e;
         if (name) *name = "conv_ht_f16<512x128,3x3,m16,persistent>";
         hipLaunchKernelGGL(conv_htp_f16, dim3(256), dim3(512), HT_LDS + 512, s, p);
         return hipGetLastError();
     }
-    if (g_ht_m16) {
+    if (route.ht_m16) {
         if (name) *name = "conv_ht_f16<512x128,3x3,m16>";
         hipLaunchKernelGGL(conv_ht_f16<true>, dim3(p.mtiles * p.ntiles), dim3(512), HT_LDS, s, p);
         return hipGetLastError();

@@ -71,21 +71,22 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define HMV_TOUT 1     // 1: transposed-output register epilogue in the non-generic kernels (0 = the LDS-staged drain, for A/B builds)
 #endif
 
-// 256 bytes of zeros: out-of-range taps / rows DMA from here.
-static float *g_zero_page[64] = {};   // one per device ordinal
+// 256 bytes of zeros: out-of-range taps / rows DMA from here.  One per device ordinal.
 static hipError_t ensure_zero_page(float **page) {
+    static DeviceOnce once;
+    static float *pages[64] = {};   // written once by `once`
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!g_zero_page[dev]) {
+    const hipError_t e = once.run([](int d) {
         // 256 bytes of zeros, then 1 KiB that masked-out lanes of the burst epilogue store into (never read)
-        e = hipMalloc(reinterpret_cast<void **>(&g_zero_page[dev]), 256 + 1024);
-        if (e == hipSuccess) e = hipMemset(g_zero_page[dev], 0, 256 + 1024);
-        if (e != hipSuccess) { g_zero_page[dev] = nullptr; return e; }
-    }
-    *page = g_zero_page[dev];
-    return hipSuccess;
+        float *z = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&z), 256 + 1024);
+        if (e == hipSuccess) e = hipMemset(z, 0, 256 + 1024);
+        if (e == hipSuccess) pages[d] = z;
+        else if (z) (void)hipFree(z);
+        return e;
+    }, &dev);
+    if (e == hipSuccess) *page = pages[dev];
+    return e;
 }
 
 // A-operand addressing modes
@@ -1223,8 +1224,7 @@ bool conv_partial_n(ConvTile t, int Cout) {
 }
 
 ConvTile conv_pick_tile(int M, int Cout, int K, bool f16, bool has_res) {
-    static int forced = -2;   // development knob: HMV_FORCE_TILE=<ConvTile> for layers with Cout > 64
-    if (forced == -2) { const char *e = HMV_DEV_ENV("HMV_FORCE_TILE"); forced = e ? atoi(e) : -1; }
+    static const int forced = HMV_DEV_INT("HMV_FORCE_TILE", -1);   // development knob: HMV_FORCE_TILE=<ConvTile> for layers with Cout > 64
     static const bool force_all = HMV_DEV_ENV("HMV_FORCE_TILE_ALL") != nullptr;   // ... and for the narrow layers too
     if ((Cout > 64 || force_all) && forced >= 0 && forced < TILE_COUNT) return (ConvTile)forced;
     // Measured on MI355X (tools/conv_sweep.py): the matrix pipe is DVFS/power limited, so the tile with
@@ -1280,20 +1280,13 @@ static hipError_t launch_one(ConvParams p, hipStream_t s) {
     if constexpr (!X3 && sizeof(T) == 2 && KB == 64 && !GENERIC && !PARTN && !RD && MODE != MODE_HALO) {
         if (p.x3_plane) return launch_one<T, BM, BN, WGM, WGN, MODE, GENERIC, KB, PARTN, RD, true>(p, s);
     }
-    static bool configured[64] = {};   // per device ordinal
     constexpr bool tout = HMV_TOUT && sizeof(T) == 2 && !GENERIC && !RD;   // register epilogue: no staging memory (+ the 256-byte prefetch dummy slot)
     constexpr int ns = ring_stages(sizeof(T) == 2, KB, GENERIC, RD, BM, BN);
     const size_t lds = MODE == MODE_HALO ? (size_t)2 * (HALO_ROWS + BN) * KB * sizeof(T) + 256   // two halo images + two weight stages
                                          : (size_t)lds_floats(BM, BN, WGM, KB * (int)sizeof(T) / 4, RD, !tout, ns) * sizeof(float) + (tout ? 256 : 0);
     auto kern = conv_igemm<T, BM, BN, WGM, WGN, MODE, GENERIC, KB, PARTN, RD, X3, C32>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = (p.Cout + BN - 1) / BN;
     if (p.mtiles * p.ntiles < 4 * p.stagger_blocks) p.stagger = 0;   // too few rounds for a start-up offset to pay
@@ -1311,7 +1304,7 @@ static hipError_t launch_plain(const ConvParams &p, bool one, hipStream_t s) {
     return one ? launch_one<T, BM, BN, WGM, WGN, MODE_1X1, false, KB>(p, s) : launch_one<T, BM, BN, WGM, WGN, MODE_TAPS, false, KB>(p, s);
 }
 
-hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **name) {
+hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **name, const ConvRoute &route) {
     if (name) *name = "conv_igemm<none>";
     if (p.M <= 0) return hipSuccess;
     {
@@ -1322,21 +1315,23 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
     }
     if (!p.lda) p.lda = p.Cin;
     if (!p.ldw) p.ldw = p.Kpad;
-    {   // development knob: HMV_STAGGER=<10-ns ticks per phase group>[,<blocks of the first round>]
-        static int st_ticks = -1, st_blocks = 256, st_mode = 0;
-        if (st_ticks < 0) {
-            const char *e = HMV_DEV_ENV("HMV_STAGGER");
-            st_ticks = e ? atoi(e) : 0;
-            if (e) { const char *c = strchr(e, ','); if (c) { st_blocks = atoi(c + 1); c = strchr(c + 1, ','); if (c) st_mode = atoi(c + 1); } }
-        }
-        p.stagger = st_ticks;
-        p.stagger_blocks = st_blocks;
-        p.stagger_mode = st_mode;
-        static int pf = -1;   // development knob, OFF by default: HMV_PREFETCH=1 enables the software L2 prefetch (A/B runs)
-        if (pf < 0) { const char *e = HMV_DEV_ENV("HMV_PREFETCH"); pf = e ? atoi(e) : 0; }
+    {   // development knob: HMV_STAGGER=<10-ns ticks per phase group>[,<blocks of the first round>[,<mode>]]
+        struct Stagger { int ticks = 0, blocks = 256, mode = 0; };
+        static const Stagger st = [] {
+            Stagger r;
+            if (const char *e = HMV_DEV_ENV("HMV_STAGGER")) {
+                r.ticks = atoi(e);
+                const char *c = strchr(e, ',');
+                if (c) { r.blocks = atoi(c + 1); c = strchr(c + 1, ','); if (c) r.mode = atoi(c + 1); }
+            }
+            return r;
+        }();
+        p.stagger = st.ticks;
+        p.stagger_blocks = st.blocks;
+        p.stagger_mode = st.mode;
+        static const int pf = HMV_DEV_INT("HMV_PREFETCH", 0);   // development knob, OFF by default: HMV_PREFETCH=1 enables the software L2 prefetch (A/B runs)
         p.prefetch = pf;
-        static int burst = -1;   // development knob: HMV_BURST=0 keeps the residual on the register-ring path (A/B runs)
-        if (burst < 0) { const char *e = HMV_DEV_ENV("HMV_BURST"); burst = e ? atoi(e) : 1; }
+        static const int burst = HMV_DEV_INT("HMV_BURST", 1);   // development knob: HMV_BURST=0 keeps the residual on the register-ring path (A/B runs)
         p.burst = burst;
     }
     p.acc_scale = ldexpf(1.f, -p.acc_shift);
@@ -1351,9 +1346,9 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
         return hipErrorInvalidValue;   // the merged launch exists for the four 2x2 phases of the k4 s2 p1 transposed conv only
     const bool one = p.R == 1 && p.S == 1 && p.pad_h == 0 && p.pad_w == 0;
     // a chained 1x1 conv (ConvParams::nx_*) exists in conv_stream.hip only: the caller asked conv_stream_chain_ok first
-    if (p.nx_wgt && (generic || p.tall || !conv_stream_chain_ok(p, p.nx_cout))) return hipErrorInvalidValue;
+    if (p.nx_wgt && (generic || p.tall || !conv_stream_chain_ok(p, p.nx_cout, route))) return hipErrorInvalidValue;
     // ... and a fused max pool in conv_hs.hip only
-    if (p.pool && (generic || p.tall || !conv_hs_supported(p))) return hipErrorInvalidValue;
+    if (p.pool && (generic || p.tall || !conv_hs_supported(p, route))) return hipErrorInvalidValue;
     // weights packed for the tall-tile 3x3 kernel (conv_ht.hip; K order (32-channel chunk, r, s, c % 32)): that kernel when its 512-pixel x
     // 128-channel tiles fill the chip, else the 64 x 64 / 128 x 128 tiles of this file walking the SAME order -- same operand roles,
     // same accumulation sequence, same epilogue arithmetic, so the bits do not depend on which of the two ran (tests/test_gpu_parity.py)
@@ -1361,13 +1356,12 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
         if (generic || !conv_ht_shape_ok(p.R, p.S, p.stride, p.pad_h, p.Cin, p.Cout, p.H, p.W) || !p.in_f16 || !p.out_f16 || p.res || p.in2 ||
             p.x3_plane || p.cwrap || p.rd_cout || p.ksl > 1 || p.phases > 1 || p.up)
             return hipErrorInvalidValue;
-        static int ht_min = -1;   // development knob: HMV_HT_MIN_TILES=<n> (default 256: one tile per CU)
-        if (ht_min < 0) { const char *e = HMV_DEV_ENV("HMV_HT_MIN_TILES"); ht_min = e ? atoi(e) : 256; }
+        static const int ht_min = HMV_DEV_INT("HMV_HT_MIN_TILES", 256);   // development knob (default 256: one tile per CU)
         const long long ht_tiles = (long long)p.N * (p.H >> 4) * (p.W >> 5) * (p.Cout / 128);
-        if (conv_ht_mode() > 0 || (conv_ht_mode() < 0 && ht_tiles >= ht_min)) return launch_conv_ht(p, s, name);
+        if (route.ht == ROUTE_FORCE || (route.ht == ROUTE_RULE && ht_tiles >= ht_min)) return launch_conv_ht(p, s, name, route);
         // small launches: conv_m16.hip's 64 x 64 / 128 x 128 tiles on the same 16x16x32 MFMA (same bits as conv_ht<..., m16>); the c32
-        // instantiations below are the 32x32x16 partner of the shape A/B (conv_ht_set_shape(0), op-level tests only)
-        if (conv_ht_shape()) return launch_conv_m16(p, s, name);
+        // instantiations below are the 32x32x16 partner of the shape A/B (route.ht_m16 = 0, op-level tests only)
+        if (route.ht_m16) return launch_conv_m16(p, s, name);
         if ((long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) < 256) {
             if (name) *name = "conv_igemm_f16<64x64,taps,c32>";
             return launch_one<_Float16, 64, 64, 2, 2, MODE_TAPS, false, 32, false, false, false, true>(p, s);
@@ -1378,19 +1372,19 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
     // token GEMMs over (hi, lo) fp16 pairs with fp32 output rows (the fusion blocks' q / k / v projections in the fp16-kernel modes):
     // gemm_x3.hip at every size (a four-stage ring on the 16x16x32 MFMA instead of the fused split loop's one DMA in flight)
     if (!generic && gemm_x3_rule(p)) return launch_gemm_x3(p, s, name);
-    if (!generic && gemm_x3k16_ok(p)) return launch_gemm_x3k16(p, s, name);
+    if (!generic && gemm_x3k16_ok(p, route)) return launch_gemm_x3k16(p, s, name, route);
     // MFMA-heavy fp16 1x1 convs without a residual (layer3's conv1, pose_net.0): the 16x16x32 MFMA at EVERY batch size -- the
     // phase-interleaved 256 x 256 tile where its tiles fill the chip, conv_m16.hip's small tiles elsewhere (same bits)
     if (!generic && conv_m16_rule(p)) {
         p.m16 = 1;
-        return conv_gemm8_supported(p) ? launch_conv_gemm8(p, s, name) : launch_conv_m16(p, s, name);
+        return conv_gemm8_supported(p, route) ? launch_conv_gemm8(p, s, name, route) : launch_conv_m16(p, s, name);
     }
     // short-reduction residual 1x1 convs over many pixels (fp16 Bottleneck conv3): the persistent weight-stationary kernel
-    if (!generic && conv_stream_supported(p)) return launch_conv_stream(p, s, name);
+    if (!generic && conv_stream_supported(p, route)) return launch_conv_stream(p, s, name);
     // MFMA-heavy fp16 1x1 convs without a residual on 256 x 256 tiles: the counted-vmcnt, phase-interleaved main loop
-    if (!generic && conv_gemm8_supported(p)) return launch_conv_gemm8(p, s, name);
+    if (!generic && conv_gemm8_supported(p, route)) return launch_conv_gemm8(p, s, name, route);
     // few-channel fp16 layers (3x3 64 -> 64, the space-to-depth stem) over many pixels: weights in registers, halo images streamed
-    if (!generic && conv_hs_supported(p)) return launch_conv_hs(p, s, name);
+    if (!generic && conv_hs_supported(p, route)) return launch_conv_hs(p, s, name);
     if (p.ksl > 1 && (!one || p.in_f16 || p.in2 || p.up || p.res || p.act != ACT_NONE || p.kslice <= 0 || p.kslice % 32 != 0 ||
                       p.ksl * p.kslice != p.Kpad || p.Cin % 32 != 0))
         return hipErrorInvalidValue;   // split-K: plain fp32 GEMM slices, epilogue left to the reduction kernel
@@ -1411,7 +1405,7 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
         (!p.in_f16 || p.rd_cout || (p.ldc & 3) || (p.res && (p.ldr & 3)) || p.act == ACT_GELU || p.act == ACT_LEAKY))
         return hipErrorInvalidValue;
     // row-decomposed fp32 convs over many pixels (HRNet-w40's 40- / 80-channel branches): the persistent weight-stationary kernel
-    if (p.rd_cout && !generic && conv_rds_supported(p)) return launch_conv_rds(p, s, name);
+    if (p.rd_cout && !generic && conv_rds_supported(p, route)) return launch_conv_rds(p, s, name);
     if (p.rd_cout) {   // row-decomposed 3x3 (see conv_igemm): the caller passes the 3x1 GEMM (R = 3, S = 1, Cout = 3 * rd_cout)
         if (generic || p.R != 3 || p.S != 1 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 0 || p.Cout != 3 * p.rd_cout || p.Cout > 256 ||
             (p.rd_cout & 3) || (p.ldc & 3) || (p.res && (p.ldr & 3)) || 128 % p.Wo != 0 || p.Ho != p.H || p.Wo != p.W)
@@ -1443,13 +1437,11 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
     }
     // fp16 256x256 (the plain kernels of the backbone) on the four-stage ring main loop (ring_stages above): measured 4-8 %
     // SLOWER than the two-stage loop (profiles/r02_probe_ring.txt), so it stays behind a development knob
-    static int ring = -1;   // HMV_F16_RING=1 selects it (A/B runs)
-    if (ring < 0) { const char *e = HMV_DEV_ENV("HMV_F16_RING"); ring = e ? atoi(e) : 0; }
+    static const int ring = HMV_DEV_INT("HMV_F16_RING", 0);   // HMV_F16_RING=1 selects it (A/B runs)
     if (ring && p.in_f16 && tile == TILE_256x256 && !generic && !dense && !p.x3_plane && !p.cwrap && !p.rd_cout && p.ksl <= 1)
         tile = TILE_256x256_RING;
     // fp16 3x3 stride-1 pad-1 convs on 256 x 256 tiles: 16 x 16 pixel blocks with the halo image in LDS (MODE_HALO)
-    static int halo = -1;   // development knob: HMV_NO_HALO=1 keeps the nine-fetch MODE_TAPS loop (A/B runs)
-    if (halo < 0) halo = HMV_DEV_ENV("HMV_NO_HALO") ? 0 : 1;
+    static const bool halo = HMV_DEV_ENV("HMV_NO_HALO") == nullptr;   // development knob: HMV_NO_HALO=1 keeps the nine-fetch MODE_TAPS loop (A/B runs)
     const bool use_halo = halo && p.in_f16 && (tile == TILE_256x256 || tile == TILE_256x128) && !generic && !dense && !p.x3_plane && !p.cwrap && !p.rd_cout &&
                           p.ksl <= 1 && !p.in2 && !p.res && !p.up && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad_h == 1 && p.pad_w == 1 &&
                           p.Ho == p.H && p.Wo == p.W && p.H % 16 == 0 && p.W % 16 == 0 && p.Cin % 64 == 0 && p.lda == p.Cin &&
@@ -1461,8 +1453,7 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
     }
     // last N-tile with >= 32 all-padding columns: the block-skipping instantiations (fp32, the three big tiles)
     const int mode = dense ? MODE_DENSE : (one ? MODE_1X1 : MODE_TAPS);
-    static int no_skip = -1;   // development knob: HMV_NO_SKIPN=1 disables the block-skipping instantiations (A/B runs)
-    if (no_skip < 0) { const char *e = HMV_DEV_ENV("HMV_NO_SKIPN"); no_skip = e ? atoi(e) : 0; }
+    static const int no_skip = HMV_DEV_INT("HMV_NO_SKIPN", 0);   // development knob: HMV_NO_SKIPN=1 disables the block-skipping instantiations (A/B runs)
     const bool partn = !no_skip && !p.in_f16 && !generic && conv_partial_n(tile, p.Cout) && !(dense && tile == TILE_256x256);
     if (name) *name = p.in_f16 ? conv_tile_name_f16(tile, mode) : tile_name("f32", tile, mode, partn);
     if (partn) {

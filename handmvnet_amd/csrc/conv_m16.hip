@@ -227,25 +227,17 @@ bool conv_m16_supported(const ConvParams &p) {
 // 1x1 layers on the 16x16x32 MFMA: the MFMA-heavy squeezing / head convs without a residual (layer3's conv1 1024 -> 256 and 512 -> 256,
 // pose_net.0 1024 -> 512: resnet.py:124-131, handmvnet.py:70-86) -- long reductions (K >= 128, whole 64-channel k-steps), wide outputs.
 // Everything in the rule is a property of the layer (shape, epilogue, storage), nothing of the launch size.
-static int g_m16_rule = 1;
-void conv_m16_set_rule(int on) { g_m16_rule = on; }
 bool conv_m16_rule(const ConvParams &p) {
     // (two-source launches: only the long one, layer3.0's conv3 + downsample, K = 256 + 512; the K = 128 / 384 ones of layer1.0 / layer2.0
     // are HBM-bound and belong to conv_stream.hip at every size that matters)
-    return g_m16_rule && conv_m16_supported(p) && p.R == 1 && p.Kpad % 64 == 0 && p.Kpad >= (p.in2 ? 768 : 128) && p.Cout > 128 && !p.tall && !p.fill;
+    return conv_m16_supported(p) && p.R == 1 && p.Kpad % 64 == 0 && p.Kpad >= (p.in2 ? 768 : 128) && p.Cout > 128 && !p.tall && !p.fill;
 }
 
 template <int BM, int BN, bool TAPS, bool DUAL = false>
 static hipError_t launch_m16(ConvParams p, hipStream_t s) {
     constexpr int lds = M16_NS * (BM + BN) * 64;
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_m16_f16<BM, BN, TAPS, DUAL>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([](int) { return set_max_lds(lds, conv_m16_f16<BM, BN, TAPS, DUAL>); }); e != hipSuccess) return e;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = p.Cout / BN;
     hipLaunchKernelGGL((conv_m16_f16<BM, BN, TAPS, DUAL>), dim3(p.mtiles * p.ntiles), dim3(256), lds, s, p);

@@ -210,13 +210,9 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_rds_f32(const ConvParams p) 
 }
 
 // ====================================================================== host side
-static int g_rds_mode = -1;   // -1: the launcher's rule (HMV_NO_RDS=1 disables it); 0 never; 1 whenever supported (op-level tests)
-void conv_rds_set_mode(int mode) { g_rds_mode = mode; }
-
-bool conv_rds_supported(const ConvParams &p) {
-    static int off = -1;   // development knob: HMV_NO_RDS=1 keeps these layers on conv_igemm's row-decomposed tiles (A/B runs)
-    if (off < 0) off = HMV_DEV_ENV("HMV_NO_RDS") ? 1 : 0;
-    if (g_rds_mode == 0 || (g_rds_mode < 0 && off)) return false;
+// route.rds: the launcher's rule, never, or whenever supported (op-level tests)
+bool conv_rds_supported(const ConvParams &p, const ConvRoute &route) {
+    if (route.rds == ROUTE_NEVER) return false;
     if (p.in_f16 || p.out_f16 || p.res_f16 || (p.rd_cout != 40 && p.rd_cout != 80)) return false;
     if (p.R != 3 || p.S != 1 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 0 || p.Cout != 3 * p.rd_cout || p.Cin != p.rd_cout) return false;
     if (p.Ho != p.H || p.Wo != p.W || p.W <= 0 || 64 % p.W != 0 || (p.H * p.W) % 64 != 0) return false;
@@ -226,7 +222,7 @@ bool conv_rds_supported(const ConvParams &p) {
     const int kp = (3 * p.rd_cout + 31) / 32 * 32;
     if ((p.lda ? p.lda : p.Cin) != p.Cin || (p.ldw ? p.ldw : p.Kpad) < kp || ((p.ldw ? p.ldw : p.Kpad) & 3) || (p.ldc & 3) || (p.res && (p.ldr & 3))) return false;
     if ((long long)p.M * p.Cin >= (1ll << 31)) return false;
-    if (g_rds_mode > 0) return true;
+    if (route.rds == ROUTE_FORCE) return true;
     return (long long)(p.M + 63) / 64 >= 4 * 256;   // at least four tiles per workgroup
 }
 
@@ -235,15 +231,9 @@ static hipError_t launch_rds_one(ConvParams p, hipStream_t s) {
     constexpr int NB = (3 * CH + 31) / 32;
     constexpr size_t lds = (size_t)4 * 64 * 32 * 4 + (size_t)64 * (32 * NB + 4) * 4;
     static_assert(lds * (8 / NWV) <= 160 * 1024, "LDS budget");
-    static bool configured[64] = {};
     auto kern = conv_rds_f32<CH, HAS_RES, NWV>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
     p.mtiles = (p.M + 63) / 64;
     p.ntiles = 1;
     const int grid = 256 * (8 / NWV);

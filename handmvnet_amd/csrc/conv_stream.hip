@@ -591,16 +591,10 @@ static hipError_t launch_stream_one(ConvParams p, hipStream_t s) {
     // chain without landing zones: the output tile's LDS image has its own BM x BN x 2 bytes behind the ring
     constexpr size_t lds = (size_t)NSLOT * BM * 128 + (HAS_RES ? (size_t)2 * NWV * TM * TN * 2 * 1024 : (N2 ? (size_t)BM * BN * 2 : 0));
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool configured[64] = {};
     auto kern = conv_stream_f16<TM, TN, MW, NW, NP, NSLOT, HAS_RES, SPREAD, NT_, DUAL, N2>;
     if (N2 && (p.Cout != BN || p.nx_cout != N2 || !p.nx_wgt || !p.nx_bias || !p.nx_out)) return hipErrorInvalidValue;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = p.Cout / BN;
     hipLaunchKernelGGL(kern, dim3(256), dim3(64 * NWV), lds, s, p);
@@ -628,11 +622,6 @@ static int stream_bn(const ConvParams &p, int *bm = nullptr) {
     return bn;
 }
 
-// -1: the launcher's rule (HMV_NO_STREAM=1 in the environment disables the kernel for A/B runs); 0: never; 1: whenever the shape
-// has an instantiation, whatever the pixel count (op-level tests: hmv_op_conv2d_f16)
-static int g_stream_mode = -1;
-void conv_stream_set_mode(int mode) { g_stream_mode = mode; }
-
 // fp32: residual-bearing 1x1 convs with K = 64 / 128 / 256 and Cout a multiple of 256 (64 x 256 tiles, one 32-channel block per wave)
 static int stream32_shape(const ConvParams &p) {   // 0 none; 1 residual-bearing (64 x 256 tiles); 2 the squeezing conv1 256 -> 64 (128 x 64 tiles);
     if (p.in_f16 || p.out_f16) return 0;            // 3 conv3 + downsample of layer1.0 (64 + 64 -> 256) as one GEMM over two sources
@@ -649,22 +638,21 @@ static bool stream32_rule(const ConvParams &p) {
     return p.res ? (p.Kpad <= 128 || (!no256 && p.Cout % 128 == 0 && 64 % (p.Cout / 128) == 0)) : true;
 }
 
-bool conv_stream_supported(const ConvParams &p) {
-    static int off = -1;   // development knob: HMV_NO_STREAM=1 keeps every conv on conv_igemm (A/B runs)
-    if (off < 0) off = HMV_DEV_ENV("HMV_NO_STREAM") ? 1 : 0;
-    static int min_env = -1;   // tiles per workgroup below which the per-tile workgroups of conv_igemm fill the chip better
-    if (min_env < 0) { const char *e = HMV_DEV_ENV("HMV_STREAM_MIN_TILES"); min_env = e ? atoi(e) : 4; }
-    if (g_stream_mode == 0 || (g_stream_mode < 0 && off)) return false;
-    const int min_tiles = g_stream_mode > 0 ? 0 : min_env;
+// route.stream: the launcher's rule, never, or whenever the shape has an instantiation, whatever the pixel count (op-level tests)
+bool conv_stream_supported(const ConvParams &p, const ConvRoute &route) {
+    static const int min_env = HMV_DEV_INT("HMV_STREAM_MIN_TILES", 4);   // tiles per workgroup below which the per-tile workgroups of conv_igemm fill the chip better
+    if (route.stream == ROUTE_NEVER) return false;
+    const bool force = route.stream == ROUTE_FORCE;
+    const int min_tiles = force ? 0 : min_env;
     if (stream32_shape(p)) {
         static const bool off32 = HMV_DEV_ENV("HMV_NO_STREAM32") != nullptr;   // development knob (A/B runs)
-        if (off32 && g_stream_mode <= 0) return false;
+        if (off32 && !force) return false;
         if (p.R != 1 || p.S != 1 || p.stride != 1 || p.pad_h || p.pad_w || p.up || p.ksl > 1 || p.phases > 1) return false;
         if (p.cwrap || p.x3_plane || p.res_split || p.out_split || p.acc_shift || p.rd_cout || p.scatter || p.rg_out || p.fill) return false;
         if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
         if ((!p.in2 && p.Cin != p.Kpad) || p.K != p.Kpad) return false;
         if ((p.lda ? p.lda : p.Cin) % 4 || (p.ldw ? p.ldw : p.Kpad) % 4 || p.ldc % 4 || (p.res && p.ldr % 4)) return false;
-        if (g_stream_mode > 0) return true;
+        if (force) return true;
         const int bm32 = (p.res || p.in2) ? 64 : 128, streams32 = p.res ? 256 / (p.Cout / 256) : 256;
         return stream32_rule(p) && (long long)(p.M + bm32 - 1) / bm32 >= (long long)min_tiles * streams32;
     }
@@ -683,7 +671,7 @@ bool conv_stream_supported(const ConvParams &p) {
 
 // chain (ConvParams::nx_*): the fp16 launches whose workgroup owns all output channels of its pixel tile -- Bottleneck conv3 of layer1
 // (64 -> 256 + residual; conv3 + downsample of layer1.0 as two sources) -- followed by a 1x1 conv 256 -> 64 / 128 + ReLU
-bool conv_stream_chain_ok(const ConvParams &q, int nx_cout) {
+bool conv_stream_chain_ok(const ConvParams &q, int nx_cout, const ConvRoute &route) {
     static const bool off = HMV_DEV_ENV("HMV_NO_CHAIN") != nullptr;   // development knob (A/B runs)
     if (off || (nx_cout != 64 && nx_cout != 128)) return false;
     ConvParams p = q;
@@ -692,7 +680,7 @@ bool conv_stream_chain_ok(const ConvParams &q, int nx_cout) {
     if (!p.ldw) p.ldw = p.Kpad;
     if (!p.in_f16 || !p.out_f16 || p.acc_shift || p.Cout != 256 || (p.ldc & 7)) return false;
     if (!(p.in2 ? (!p.res && p.Kpad == 128 && p.ksplit == 64 && nx_cout == 64) : (p.res && p.Kpad == 64))) return false;
-    return conv_stream_supported(p);
+    return conv_stream_supported(p, route);
 }
 
 template <int TM, int TN, int MW, int NW, int NP, int NSLOT, bool HAS_RES, bool DUAL = false, bool HALF = false>
@@ -700,15 +688,9 @@ static hipError_t launch_stream32(ConvParams p, hipStream_t s) {
     constexpr int BM = 32 * TM * MW, BN = 32 * TN * NW;
     constexpr size_t lds = (size_t)NSLOT * BM * 128 + (HAS_RES ? (size_t)(HALF ? 1 : 2) * MW * NW * TM * TN * 4 * 1024 : 0);
     static_assert(lds * (HALF ? 2 : 1) <= 160 * 1024, "LDS budget");
-    static bool configured[64] = {};
     auto kern = conv_stream_f32<TM, TN, MW, NW, NP, NSLOT, HAS_RES, DUAL, HALF>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = p.Cout / BN;
     hipLaunchKernelGGL(kern, dim3(HALF ? 512 : 256), dim3(64 * MW * NW), lds, s, p);
@@ -733,8 +715,8 @@ hipError_t launch_conv_stream(const ConvParams &p, hipStream_t s, const char **n
     // non-temporal residual loads, 4 non-temporal pixel pieces too.  Measured (profiles/r03_probe_stream_variants.txt): spreading
     // gains 3-4 % at K = 256 (four piece steps) and loses 4 % at K = 128; non-temporal loads lose 15-25 % everywhere (the next
     // launch finds less of its input in the Infinity Cache).  Default: spread at K = 256 only.
-    static int variant = -1;
-    if (variant < 0) { const char *e = HMV_DEV_ENV("HMV_STREAM_VARIANT"); variant = e ? atoi(e) : -1; if (variant < 0) variant = 100; }
+    static const int knob = HMV_DEV_INT("HMV_STREAM_VARIANT", 100);
+    const int variant = knob < 0 ? 100 : knob;
 #define HMV_STREAM_VARIANTS(...)                                                                            \
     switch (variant) {                                                                                      \
         case 1: return launch_stream_one<__VA_ARGS__, true, true, 0>(p, s);                                 \

@@ -31,7 +31,7 @@ const int kBlocks[3][4] = {{2, 2, 2, 2}, {3, 4, 6, 3}, {3, 4, 6, 3}};
 const int kHrChannels[2][4] = {{40, 80, 160, 320}, {64, 128, 256, 512}};   // hrnet.py:430-447
 inline int cpad(int c) { return (c + 3) / 4 * 4; }   // NHWC channel stride: 16-byte pixels are all the conv kernel needs
 
-std::string g_create_err;
+thread_local std::string g_create_err;   // hmv_last_error(NULL): per thread, like errno
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -1134,6 +1134,7 @@ struct Runner {
     // second A source of the next conv() call (conv3 + downsample as one GEMM); consumed by that call
     struct Dual { const float *in2 = nullptr; int ksplit = 0, H2 = 0, W2 = 0, lda2 = 0, stride2 = 1; } dual;
     const char **kernel_name = nullptr;   // op-level entries: receives the kernel family of the last launch
+    ConvRoute route = conv_rule();        // the kernel families its launches may take (op-level entries: from a kernel_sel); planning asks with it too
     // chained 1x1 conv of the next conv() call (conv_stream.hip: Bottleneck i's conv3 -> Bottleneck i + 1's conv1 from the output tile
     // while it is in LDS); consumed by that call.  `probe`: the next conv() call only fills *probe with the launch it WOULD make (also
     // in the planning run) -- what chain_ok() asks conv_stream_chain_ok about
@@ -1232,7 +1233,7 @@ struct Runner {
             check(hipEventRecord(pr->e0, s), "hipEventRecord");
         }
         const char *kname = nullptr;
-        check(launch_conv(p, tile, s, &kname), L.label.c_str());
+        check(launch_conv(p, tile, s, &kname, route), L.label.c_str());
         ++h->launches;
         if (kernel_name) *kernel_name = kname;
         if (pr) {
@@ -1444,7 +1445,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                 ConvParams q{};
                 R.probe = &q;
                 R.conv(b.c3, t2, N, H2, W2, 1, 0, 0, y, 256, res, 256, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
-                ch = conv_stream_chain_ok(q, nb->c1.Cout);
+                ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
             }
             if (ch) { t1_chained = R.alloc(ACT((size_t)N * H2 * W2 * 64)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
             R.conv(b.c3, t2, N, H2, W2, 1, 0, 0, y, 256, res, 256, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
@@ -1613,7 +1614,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         R.pool.h = hh; R.pool.w = ww;
         R.conv(h->stem, in4, N, Hs, Ws, 1, 2, 2, nullptr, 64, nullptr, 0, ACT_RELU, H1, W1, 0, 0, 0, 0, 0, h16);
         R.pool = Runner::Pool();
-        stem_pool = q.pool && conv_hs_supported(q);
+        stem_pool = q.pool && conv_hs_supported(q, R.route);
     }
     float *cur;
     if (stem_pool) {
@@ -1671,7 +1672,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                         ConvParams q{};
                         R.probe = &q;
                         R.conv_dual(b.c3ds, t2, planes, cur, C, N, hh, ww, b.stride, y, outc, ho, wo, h16);
-                        ch = conv_stream_chain_ok(q, nb->c1.Cout);
+                        ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
                     }
                     if (ch) { t1_chained = R.alloc(ACT((size_t)N * ho * wo * nb->c1.Cout)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
                     R.conv_dual(b.c3ds, t2, planes, cur, C, N, hh, ww, b.stride, y, outc, ho, wo, h16);
@@ -1688,7 +1689,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                         ConvParams q{};
                         R.probe = &q;
                         R.conv(b.c3, t2, N, ho, wo, 1, 0, 0, y, outc, res, outc, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
-                        ch = conv_stream_chain_ok(q, nb->c1.Cout);
+                        ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
                     }
                     if (ch) { t1_chained = R.alloc(ACT((size_t)N * ho * wo * nb->c1.Cout)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
                     R.conv(b.c3, t2, N, ho, wo, 1, 0, 0, y, outc, res, outc, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
@@ -2195,12 +2196,6 @@ int hmv_set_tail_fusion(hmv_handle h, int32_t enable) {
 
 /* Chained launches (Bottleneck conv3 -> the next block's conv1 from the output tile in LDS) on (default) / off (one launch per conv:
  * the same bits).  Part of the workspace plan, so the workspace is re-planned on the next forward. */
-int hmv_set_x3k16_mode(int32_t mode) {
-    if (mode < -1 || mode > 1) { g_create_err = "hmv_set_x3k16_mode: -1, 0 or 1"; return HMV_ERR_ARG; }
-    gemm_x3k16_set_mode(mode);
-    return HMV_OK;
-}
-
 int hmv_set_chain_fusion(hmv_handle h, int32_t enable) {
     if (!h) return HMV_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2317,103 +2312,74 @@ int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_
     return HMV_OK;
 }
 
-static const char **g_op_kernel_name = nullptr;   // hmv_op_conv2d_sel: where the kernel family of the next hmv_op_conv2d goes
-
-int hmv_op_conv2d(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
-                  const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual,
-                  int32_t relu, float *out, void *stream) {
-    if (!in || !w_oihw || !out || Cin % 4 != 0) {
-        g_create_err = "hmv_op_conv2d: Cin must be a multiple of 4";
-        return HMV_ERR_ARG;
-    }
-    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
-    const int K = R * S * Cin, Kpad = round_up(K, 32), Cp = round_up(Cout, 256);
-    std::vector<float> w((size_t)Cp * Kpad, 0.f), b((size_t)Cp, 0.f);
-    for (int o = 0; o < Cout; ++o) {
-        for (int k = 0; k < K; ++k) {
-            int c, tap;
-            if (Cin % 32 == 0) { const int chunk = k / (32 * R * S), rem = k % (32 * R * S); tap = rem / 32; c = chunk * 32 + rem % 32; }
-            else { c = k % Cin; tap = k / Cin; }
-            w[(size_t)o * Kpad + k] = w_oihw[(((size_t)o * Cin + c) * R + tap / S) * S + tap % S];
-        }
-        if (bias_host) b[o] = bias_host[o];
-    }
-    float *dw = nullptr, *db = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dw), w.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&db), b.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(dw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        ConvParams p{};
-        p.in = in; p.wgt = dw; p.bias = db; p.res = residual; p.out = out;
-        p.N = N; p.H = H; p.W = W; p.Cin = Cin;
-        p.Ho = (H + 2 * pad - R) / stride + 1; p.Wo = (W + 2 * pad - S) / stride + 1; p.Cout = Cout;
-        p.R = R; p.S = S; p.stride = stride; p.pad_h = pad; p.pad_w = pad;
-        p.K = K; p.Kpad = Kpad; p.M = N * p.Ho * p.Wo; p.ldc = Cout; p.ldr = Cout;
-        p.act = relu ? ACT_RELU : ACT_NONE; p.osy = p.osx = 1;
-        e = launch_conv(p, conv_pick_tile(p.M, Cout, K, false, residual != nullptr), static_cast<hipStream_t>(stream), g_op_kernel_name);
-        if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    }
-    if (dw) (void)hipFree(dw);
-    if (db) (void)hipFree(db);
-    if (e != hipSuccess) { g_create_err = std::string("hmv_op_conv2d: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
-    return HMV_OK;
-}
-
 }  // extern "C"
 
-// One conv in any arithmetic mode through the engine's own packing (Loader::conv) and launch path (Runner::conv).
-// out16: the layer writes fp16 rows (plain fp16 mode only), as every backbone layer of the fp16 path does
-static int op_conv2d_any(const char *who, int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
-                         const float *w_oihw, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
-                         int32_t pad, const float *residual, int32_t relu, void *out, bool out16, const char **kernel_name, void *stream,
-                         bool tall = false) {
+// One conv through the engine's own packing (Loader::conv) and launch path (Runner::conv) under `route`: what every hmv_op_conv2d*
+// entry runs.  HMV_F32 reads and writes fp32 rows; HMV_F16 / HMV_F32X3 convert the input (and residual) rows first, and with out16
+// the layer writes fp16 rows, as every backbone layer of the fp16 path does.  tall: conv_ht.hip's K order.  rd: the row-decomposed
+// packing of a 3x3 C -> C conv, whose bias is then the shift of an identity BatchNorm (that packing takes its shift from one).
+static int op_conv(const char *who, int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                   const float *w_oihw, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad,
+                   const float *residual, int32_t relu, void *out, bool out16, const ConvRoute &route, const char **kernel_name,
+                   void *stream, bool tall = false, bool rd = false) {
     if (tall && (residual || !out16 || !conv_ht_shape_ok(R, S, stride, pad, Cin, Cout, H, W))) {
         g_create_err = std::string(who) + ": the tall-tile kernel takes 3x3 stride-1 pad-1 convs without residual, Cin % 32 == 0 (>= 64), Cout % 128 == 0, H % 16 == 0, W % 32 == 0";
         return HMV_ERR_ARG;
     }
-    if ((dtype != HMV_F16 && dtype != HMV_F32X3) || !in || !w_oihw || !out || Cin % 8 != 0 || Cout % 4 != 0 || (out16 && dtype != HMV_F16)) {
-        g_create_err = std::string(who) + ": dtype must be HMV_F32 / HMV_F16 / HMV_F32X3; the fp16-based modes need Cin % 8 == 0, Cout % 4 == 0";
+    const bool half = dtype != HMV_F32;
+    if ((half && dtype != HMV_F16 && dtype != HMV_F32X3) || !in || !w_oihw || !out || Cin % (half ? 8 : 4) != 0 || (half && Cout % 4 != 0) ||
+        (out16 && dtype != HMV_F16)) {
+        g_create_err = std::string(who) + ": dtype must be HMV_F32 / HMV_F16 / HMV_F32X3; fp32 needs Cin % 4 == 0, the fp16-based modes Cin % 8 == 0, Cout % 4 == 0";
         return HMV_ERR_ARG;
     }
     if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     hmv_engine eng;
     eng.cfg.device = device;
-    HostTensor wt;
+    HostTensor wt, bt;
     wt.shape = {Cout, Cin, R, S};
     wt.data.assign(w_oihw, w_oihw + (size_t)Cout * Cin * R * S);
     eng.host["w"] = wt;
-    if (bias_host) {
-        HostTensor bt;
-        bt.shape = {Cout};
-        bt.data.assign(bias_host, bias_host + Cout);
+    bt.shape = {Cout};
+    bt.data.assign(Cout, 0.f);
+    if (bias_host) bt.data.assign(bias_host, bias_host + Cout);
+    if (rd) {
+        HostTensor g1 = bt, m0 = bt, v1 = bt;
+        g1.data.assign(Cout, 1.f); m0.data.assign(Cout, 0.f);
+        v1.data.assign(Cout, 1.f - 1e-5f);   // scale = 1 / sqrt(var + eps) == 1 to fp32 rounding
+        eng.host["bn.weight"] = g1; eng.host["bn.bias"] = bt; eng.host["bn.running_mean"] = m0; eng.host["bn.running_var"] = v1;
+    } else if (bias_host) {
         eng.host["b"] = bt;
     }
     Loader L{&eng};
     L.split = dtype == HMV_F32X3;
     Layer layer;
-    L.conv(layer, "op", "w", bias_host ? "b" : "", "", Cout, Cin, R, S, 0, true, false, nullptr, tall);
+    L.conv(layer, "op", "w", bias_host && !rd ? "b" : "", rd ? "bn" : "", Cout, Cin, R, S, 0, half, rd, nullptr, tall);
     int rc = L.rc;
+    if (rc == HMV_OK && rd && !layer.rd_cout) { eng.err = "the layer was not packed row-decomposed"; rc = HMV_ERR_ARG; }
     const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    const size_t rows_in = (size_t)N * H * W, rows_out = (size_t)N * Ho * Wo;
-    const int mode = dtype == HMV_F32X3 ? 2 : 1;
+    const void *x = in, *res = residual;
     void *din = nullptr, *dres = nullptr;
     hipError_t e = hipSuccess;
-    if (rc == HMV_OK) {
-        e = hipMalloc(&din, rows_in * Cin * (mode == 2 ? 4 : 2));
-        if (e == hipSuccess && residual) e = hipMalloc(&dres, rows_out * Cout * (mode == 2 ? 4 : 2));
+    if (rc == HMV_OK && half) {   // fp16 rows, or (hi, lo) pairs in HMV_F32X3
+        const int mode = dtype == HMV_F32X3 ? 2 : 1;
+        const size_t rows_in = (size_t)N * H * W, rows_out = (size_t)N * Ho * Wo;
+        e = hipMalloc(&din, rows_in * Cin * 2 * mode);
+        if (e == hipSuccess && residual) e = hipMalloc(&dres, rows_out * Cout * 2 * mode);
         if (e == hipSuccess) e = launch_rows_f32_to_half(in, din, rows_in, Cin, mode, s);
         if (e == hipSuccess && residual) e = launch_rows_f32_to_half(residual, dres, rows_out, Cout, mode, s);
-        if (e == hipSuccess) {
-            Arena dummy;
-            Runner Rn{&eng, s, false, HMV_OK, dummy};
-            Rn.kernel_name = kernel_name;
-            Rn.conv(layer, static_cast<const float *>(din), N, H, W, stride, pad, pad, static_cast<float *>(out), Cout,
-                    static_cast<const float *>(dres), Cout, relu ? ACT_RELU : ACT_NONE, Ho, Wo, 0, 0, 0, 0, 0, out16);
-            rc = Rn.rc;
-            if (rc == HMV_OK) e = hipStreamSynchronize(s);
-        }
+        x = din;
+        res = dres;
+    }
+    if (rc == HMV_OK && e == hipSuccess) {
+        Arena dummy;
+        Runner Rn{&eng, s, false, HMV_OK, dummy};
+        Rn.kernel_name = kernel_name;
+        Rn.route = route;
+        Rn.conv(layer, static_cast<const float *>(x), N, H, W, stride, pad, pad, static_cast<float *>(out), Cout, static_cast<const float *>(res),
+                Cout, relu ? ACT_RELU : ACT_NONE, Ho, Wo, 0, 0, 0, 0, 0, out16);
+        rc = Rn.rc;
+        if (rc == HMV_OK) e = hipStreamSynchronize(s);
     }
     if (din) (void)hipFree(din);
     if (dres) (void)hipFree(dres);
@@ -2423,14 +2389,84 @@ static int op_conv2d_any(const char *who, int32_t device, int32_t dtype, const f
     return HMV_OK;
 }
 
-extern "C" int hmv_op_conv2d_ex(int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
-                                const float *w_oihw, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
-                                int32_t pad, const float *residual, int32_t relu, float *out, void *stream) {
-    if (dtype == HMV_F32)
-        return hmv_op_conv2d(device, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, stream);
-    return op_conv2d_any("hmv_op_conv2d_ex", device, dtype, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu,
-                         out, false, nullptr, stream);
+// kernel_sel -> route of the op-level entries (include/handmv.h).  Families a sel does not name keep the launcher's rule.
+static ConvRoute route_sel(int sel) {   // hmv_op_conv2d_sel: 1 conv_igemm, 2 conv_stream_f32 whenever the shape has an instantiation
+    ConvRoute r = conv_rule();
+    if (sel) r.stream = sel == 2 ? ROUTE_FORCE : ROUTE_NEVER;
+    return r;
 }
+static ConvRoute route_f16(int sel) {
+    ConvRoute r = conv_rule();
+    if (sel) r.stream = r.gemm8 = r.hs = (sel == 2 || sel == 8) ? ROUTE_FORCE : ROUTE_NEVER;   // (3 .. 7 keep the other special kernels out)
+    if (sel >= 3 && sel <= 7) r.ht = (sel == 4 || sel == 6) ? ROUTE_NEVER : ROUTE_FORCE;
+    r.ht_m16 = sel != 5 && sel != 6;
+    r.ht_persist = sel == 7 ? 2 : (sel == 3 ? 0 : 1);
+    r.gemm8_persist = sel == 8 ? 2 : (sel == 2 ? 0 : 1);
+    return r;
+}
+static ConvRoute route_x3(int sel) {   // hmv_op_conv2d_x3: 1 conv_igemm's fused split loop, 2 gemm_x3k16 whenever the shape allows
+    ConvRoute r = conv_rule();
+    if (sel) r.x3k16 = sel == 2 ? ROUTE_FORCE : ROUTE_NEVER;
+    return r;
+}
+static ConvRoute route_rd(int sel) {   // hmv_op_conv2d_rd: 1 conv_igemm's row-decomposed tiles, 2 conv_rds whatever the size
+    ConvRoute r = conv_rule();
+    if (sel) r.rds = sel == 2 ? ROUTE_FORCE : ROUTE_NEVER;
+    return r;
+}
+
+extern "C" {
+
+int hmv_op_conv2d(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
+                  const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual,
+                  int32_t relu, float *out, void *stream) {
+    return op_conv("hmv_op_conv2d", device, HMV_F32, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
+                   conv_rule(), nullptr, stream);
+}
+
+int hmv_op_conv2d_ex(int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
+                     const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual,
+                     int32_t relu, float *out, void *stream) {
+    return op_conv("hmv_op_conv2d_ex", device, dtype, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
+                   conv_rule(), nullptr, stream);
+}
+
+int hmv_op_conv2d_sel(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw, const float *bias_host,
+                      int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual, int32_t relu, float *out,
+                      int32_t kernel_sel, const char **kernel_name, void *stream) {
+    if (kernel_sel < 0 || kernel_sel > 2) { g_create_err = "hmv_op_conv2d_sel: kernel_sel must be 0, 1 or 2"; return HMV_ERR_ARG; }
+    return op_conv("hmv_op_conv2d_sel", device, HMV_F32, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
+                   route_sel(kernel_sel), kernel_name, stream);
+}
+
+int hmv_op_conv2d_f16(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw, const float *bias_host,
+                      int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual, int32_t relu, void *out_f16,
+                      int32_t kernel_sel, const char **kernel_name, void *stream) {
+    if (kernel_sel < 0 || kernel_sel > 8) { g_create_err = "hmv_op_conv2d_f16: kernel_sel must be 0 .. 8"; return HMV_ERR_ARG; }
+    return op_conv("hmv_op_conv2d_f16", device, HMV_F16, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out_f16,
+                   true, route_f16(kernel_sel), kernel_name, stream, kernel_sel >= 3 && kernel_sel <= 7);   // (3 .. 7: the tall-tile packing)
+}
+
+int hmv_op_conv2d_x3(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw, const float *bias_host,
+                     int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual, int32_t relu, float *out,
+                     int32_t kernel_sel, const char **kernel_name, void *stream) {
+    if (kernel_sel < 0 || kernel_sel > 2) { g_create_err = "hmv_op_conv2d_x3: kernel_sel must be 0, 1 or 2"; return HMV_ERR_ARG; }
+    return op_conv("hmv_op_conv2d_x3", device, HMV_F32X3, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
+                   route_x3(kernel_sel), kernel_name, stream);
+}
+
+// One fp32 3x3 stride-1 pad-1 conv C -> C in the ROW-DECOMPOSED packing: what HRNet-w40's 40- / 80-channel branches run
+int hmv_op_conv2d_rd(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t C, const float *w_oihw, const float *bias_host,
+                     const float *residual, int32_t relu, float *out, int32_t kernel_sel, const char **kernel_name, void *stream) {
+    if (!in || !w_oihw || !out || C % 4 != 0 || 3 * C > 256 || C % 32 == 0 || W <= 0 || 128 % W != 0 || kernel_sel < 0 || kernel_sel > 2) {
+        g_create_err = "hmv_op_conv2d_rd: C % 4 == 0, C % 32 != 0, 3 C <= 256, 128 % W == 0, kernel_sel 0 .. 2";
+        return HMV_ERR_ARG;
+    }
+    return op_conv("hmv_op_conv2d_rd", device, HMV_F32, in, N, H, W, C, w_oihw, bias_host, C, 3, 3, 1, 1, residual, relu, out, false,
+                   route_rd(kernel_sel), kernel_name, stream, false, true);
+}
+
+}  // extern "C"
 
 // The up-sampling terms of an HRNet fuse layer through hr_fuse.hip alone (op-level parity tests): out = act(base + sum_s up_{2^shift_s}(W_s x_s + b_s)),
 // terms added in the order given.  base / x_s device fp32 NHWC; f16 != 0 runs the fp16 instantiation on fp16 copies of them and `out` receives
@@ -2488,88 +2524,4 @@ extern "C" int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base,
     if (e != hipSuccess) return fail(HMV_ERR_HIP, hipGetErrorString(e));
     for (void *q : owned) (void)hipFree(q);
     return HMV_OK;
-}
-
-// One fp32 3x3 stride-1 pad-1 conv C -> C in the ROW-DECOMPOSED packing (Loader::conv, rd) through Runner::conv: what HRNet-w40's 40- /
-// 80-channel branches run.  kernel_sel: 0 the launcher's choice, 1 conv_igemm's row-decomposed tiles, 2 conv_rds.hip whatever the size
-extern "C" int hmv_op_conv2d_rd(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t C, const float *w_oihw,
-                                const float *bias_host, const float *residual, int32_t relu, float *out, int32_t kernel_sel,
-                                const char **kernel_name, void *stream) {
-    if (!in || !w_oihw || !out || C % 4 != 0 || 3 * C > 256 || C % 32 == 0 || W <= 0 || 128 % W != 0 || kernel_sel < 0 || kernel_sel > 2) {
-        g_create_err = "hmv_op_conv2d_rd: C % 4 == 0, C % 32 != 0, 3 C <= 256, 128 % W == 0, kernel_sel 0 .. 2";
-        return HMV_ERR_ARG;
-    }
-    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hmv_engine eng;
-    eng.cfg.device = device;
-    HostTensor wt;
-    wt.shape = {C, C, 3, 3};
-    wt.data.assign(w_oihw, w_oihw + (size_t)C * C * 9);
-    eng.host["w"] = wt;
-    // (the row-decomposed packing takes its shift from a BatchNorm: an identity BN whose shift is the bias)
-    HostTensor g1, b1, m0, v1;
-    g1.shape = b1.shape = m0.shape = v1.shape = {C};
-    g1.data.assign(C, 1.f); m0.data.assign(C, 0.f);
-    v1.data.assign(C, 1.f - 1e-5f);   // scale = 1 / sqrt(var + eps) == 1 to fp32 rounding
-    b1.data.assign(C, 0.f);
-    if (bias_host) b1.data.assign(bias_host, bias_host + C);
-    eng.host["bn.weight"] = g1; eng.host["bn.bias"] = b1; eng.host["bn.running_mean"] = m0; eng.host["bn.running_var"] = v1;
-    Loader L{&eng};
-    Layer layer;
-    L.conv(layer, "op", "w", "", "bn", C, C, 3, 3, 0, false, true);
-    int rc = L.rc;
-    hipError_t e = hipSuccess;
-    if (rc == HMV_OK && !layer.rd_cout) { eng.err = "the layer was not packed row-decomposed"; rc = HMV_ERR_ARG; }
-    if (rc == HMV_OK) {
-        conv_rds_set_mode(kernel_sel == 0 ? -1 : kernel_sel - 1);
-        Arena dummy;
-        Runner Rn{&eng, s, false, HMV_OK, dummy};
-        Rn.kernel_name = kernel_name;
-        Rn.conv(layer, in, N, H, W, 1, 1, 1, out, C, residual, C, relu ? ACT_RELU : ACT_NONE, H, W, 0, 0, 0, 0, 0, false);
-        rc = Rn.rc;
-        conv_rds_set_mode(-1);
-        if (rc == HMV_OK) e = hipStreamSynchronize(s);
-    }
-    for (void *ptr : eng.dev_allocs) (void)hipFree(ptr);
-    if (rc != HMV_OK) { g_create_err = std::string("hmv_op_conv2d_rd: ") + eng.err; return rc; }
-    if (e != hipSuccess) { g_create_err = std::string("hmv_op_conv2d_rd: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
-    return HMV_OK;
-}
-
-extern "C" int hmv_op_conv2d_sel(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
-                                 const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad,
-                                 const float *residual, int32_t relu, float *out, int32_t kernel_sel, const char **kernel_name, void *stream) {
-    if (kernel_sel < 0 || kernel_sel > 2) { g_create_err = "hmv_op_conv2d_sel: kernel_sel must be 0, 1 or 2"; return HMV_ERR_ARG; }
-    conv_stream_set_mode(kernel_sel == 0 ? -1 : kernel_sel - 1);
-    g_op_kernel_name = kernel_name;
-    const int rc = hmv_op_conv2d(device, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, stream);
-    g_op_kernel_name = nullptr;
-    conv_stream_set_mode(-1);
-    return rc;
-}
-
-extern "C" int hmv_op_conv2d_f16(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
-                                 const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad,
-                                 const float *residual, int32_t relu, void *out_f16, int32_t kernel_sel, const char **kernel_name,
-                                 void *stream) {
-    if (kernel_sel < 0 || kernel_sel > 8) { g_create_err = "hmv_op_conv2d_f16: kernel_sel must be 0 .. 8"; return HMV_ERR_ARG; }
-    const int force = kernel_sel == 0 ? -1 : ((kernel_sel == 2 || kernel_sel == 8) ? 1 : 0);   // 3 .. 7 (tall-tile packing) keep the other special kernels out
-    conv_gemm8_set_persistent(kernel_sel == 8 ? 2 : (kernel_sel == 2 ? 0 : 1));
-    conv_ht_set_mode((kernel_sel == 3 || kernel_sel == 5 || kernel_sel == 7) ? 1 : ((kernel_sel == 4 || kernel_sel == 6) ? 0 : -1));
-    conv_ht_set_shape((kernel_sel == 5 || kernel_sel == 6) ? 0 : 1);
-    conv_ht_set_persistent(kernel_sel == 7 ? 2 : (kernel_sel == 3 ? 0 : 1));
-    conv_stream_set_mode(force);
-    conv_gemm8_set_mode(force);
-    conv_hs_set_mode(force);
-    const int rc = op_conv2d_any("hmv_op_conv2d_f16", device, HMV_F16, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad,
-                                 residual, relu, out_f16, true, kernel_name, stream, kernel_sel >= 3 && kernel_sel <= 7);   // (3 .. 7: the tall-tile packing)
-    conv_ht_set_mode(-1);
-    conv_ht_set_shape(1);
-    conv_ht_set_persistent(1);
-    conv_gemm8_set_persistent(1);
-    conv_stream_set_mode(-1);
-    conv_gemm8_set_mode(-1);
-    conv_hs_set_mode(-1);
-    return rc;
 }

@@ -335,25 +335,19 @@ hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s) {
         return ((size_t)2 * rows * (p.ld + 4) + hreg + (size_t)2 * p.ld) * sizeof(float);
     };
     // 32-row tiles once 16-row ones would not fit one round of workgroups (one per CU: 90 KB of LDS, 240 registers), if they fit LDS
+    static DeviceOnce once;
+    static int ncu[64] = {};   // CUs per device, written once by `once`
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    static int ncu[64] = {};
-    if (!ncu[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
-        ncu[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (const hipError_t e = once.run([](int d) {
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, d) != hipSuccess) return hipErrorInvalidDevice;
+            ncu[d] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+            return set_max_lds(160 * 1024, ff_block_kernel<128, 1>, ff_block_kernel<256, 1>, ff_block_kernel<128, 2>, ff_block_kernel<256, 2>);
+        }, &dev);
+        e != hipSuccess)
+        return e;
     const int rb = ((p.rows + 15) / 16 > ncu[dev] && lds_of(2) <= 160 * 1024) ? 2 : 1;
     const size_t lds = lds_of(rb);
-    static bool configured[64] = {};
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ff_block_kernel<128, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(ff_block_kernel<256, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(ff_block_kernel<128, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(ff_block_kernel<256, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
     const dim3 grid((p.rows + 16 * rb - 1) / (16 * rb)), block(64 * FF_WAVES);
     if (p.hid == 128) {
         if (rb == 2) hipLaunchKernelGGL((ff_block_kernel<128, 2>), grid, block, lds, s, p);
@@ -536,15 +530,8 @@ hipError_t launch_cheb_fused(const ChebFusedParams &p, hipStream_t s) {
     if (!cheb_fusable(p.K, p.ldx, p.ldw1, p.c1, p.ldw2, p.c2, p.ldw3, p.c3) || !p.scratch) return hipErrorInvalidValue;
     const size_t lds1 = ((size_t)32 * (p.K + CH_LDX_PAD) + 3 * 32 * 16 + 3 * 21 * 21) * sizeof(float);
     const size_t lds2 = ((size_t)32 * (p.c1 + 4) + 32 * (3 * p.c2 + 4) + 32 * (p.c2 + 4) + 3 * 21 * 21 + 32 * 16) * sizeof(float);
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cheb_layer1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(cheb_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([](int) { return set_max_lds(160 * 1024, cheb_layer1_kernel, cheb_tail_kernel); }); e != hipSuccess) return e;
     hipLaunchKernelGGL(cheb_layer1_kernel, dim3(p.B, p.c1 / 16), dim3(384), lds1, s, p.x, p.ldx, p.K, p.w1, p.ldw1, p.c1, p.tk, p.bias1, 1,
                        p.scratch, p.c1);
     hipError_t e = hipGetLastError();

@@ -406,10 +406,9 @@ __global__ __launch_bounds__(512, 2) void gemm_x3k16_f16(const ConvParams p) {
 
 // the launches it takes: the split-pair GEMM rule below with a SHORT reduction (the long ones run gemm_x3_f16), whole 256-column tiles,
 // and enough of them to fill most of the chip -- a size rule, legitimate because the bits equal the fused split loop's
-static int g_x3k16_mode = -1;   // -1 the size rule, 0 never, 1 whenever the shape allows (op-level tests)
-void gemm_x3k16_set_mode(int mode) { g_x3k16_mode = mode; }
-bool gemm_x3k16_ok(const ConvParams &p) {
-    if (g_x3k16_mode == 0) return false;
+// (route.x3k16: the size rule, never, or whenever the shape allows -- op-level tests)
+bool gemm_x3k16_ok(const ConvParams &p, const ConvRoute &route) {
+    if (route.x3k16 == ROUTE_NEVER) return false;
     if (!p.in_f16 || (p.out_f16 && !p.out_split) || (p.out_split && (p.ldc & 15)) || p.res || p.in2 || p.up || p.ksl > 1 || p.phases > 1 || p.cwrap || !p.x3_plane || p.rd_cout ||
         p.scatter || p.rg_out || p.nx_wgt || p.pool || p.tall || p.act != ACT_NONE || p.fill)
         return false;
@@ -417,20 +416,14 @@ bool gemm_x3k16_ok(const ConvParams &p) {
     if (!(p.R == 1 && p.S == 1 && p.stride == 1 && !p.pad_h && !p.pad_w && p.x3_plane % 32 == 0 && p.x3_plane < 1024 && p.Kpad == 2 * p.x3_plane &&
           p.lda >= 2 * p.x3_plane && !(p.lda & 7) && !(ldw & 7) && !(p.ldc & 3) && p.Ho == p.H && p.Wo == p.W && p.Cout % 256 == 0))
         return false;
-    if (g_x3k16_mode > 0) return true;
+    if (route.x3k16 == ROUTE_FORCE) return true;
     return (long long)((p.M + 255) / 256) * (p.Cout / 256) >= 200;
 }
-hipError_t launch_gemm_x3k16(ConvParams p, hipStream_t s, const char **name) {
-    if (!gemm_x3k16_ok(p)) return hipErrorInvalidValue;
+hipError_t launch_gemm_x3k16(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route) {
+    if (!gemm_x3k16_ok(p, route)) return hipErrorInvalidValue;
     if (!p.ldw) p.ldw = p.Kpad;
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_x3k16_f16), hipFuncAttributeMaxDynamicSharedMemorySize, XK_LDS);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([](int) { return set_max_lds(XK_LDS, gemm_x3k16_f16); }); e != hipSuccess) return e;
     p.mtiles = (p.M + 255) / 256;
     p.ntiles = p.Cout / 256;
     if (name) *name = "gemm_x3k16_f16<256x256>";
@@ -458,14 +451,8 @@ bool gemm_x3_rule(const ConvParams &p) {
 template <int BM, int BN, int WGM, int WGN>
 static hipError_t launch_x3(ConvParams p, hipStream_t s) {
     constexpr int lds = X3_NS * (BM + BN) * 128;
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_x3_f16<BM, BN, WGM, WGN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([](int) { return set_max_lds(lds, gemm_x3_f16<BM, BN, WGM, WGN>); }); e != hipSuccess) return e;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = (p.Cout + BN - 1) / BN;
     // column ranges per XCD when the weights do not fit an XCD's L2 and the N-tiles divide evenly (placement: speed only, never results)

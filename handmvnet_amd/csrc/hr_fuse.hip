@@ -281,15 +281,8 @@ bool hr_fuse_up_plan(HrFuseParams &p) {
 
 hipError_t launch_hr_fuse_up(const HrFuseParams &p, hipStream_t s) {
     if (!p.th || p.lds <= 0) return hipErrorInvalidValue;
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(hr_fuse_up_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(hr_fuse_up_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([](int) { return set_max_lds(160 * 1024, hr_fuse_up_kernel<float>, hr_fuse_up_kernel<_Float16>); }); e != hipSuccess) return e;
     const int tyn = (p.H + p.th - 1) / p.th, txn = (p.W + HRF_TW - 1) / HRF_TW;
     const dim3 grid((unsigned)(p.N * tyn * txn)), block(64 * HRF_WAVES);
     if (p.f16) hipLaunchKernelGGL(hr_fuse_up_kernel<_Float16>, grid, block, p.lds, s, p);

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+#include <mutex>
+
 // Development knobs (A/B switches, probes: DESIGN.md section 9) exist only in a -DHMV_DEV_KNOBS build
 // (`python -m handmvnet_amd.build --variant dev HMV_DEV_KNOBS` -> build/libhandmv_dev.so, loaded with HMV_LIB=...).  The product
 // library reads ONE environment variable, HMV_GRAPHS; tests/test_abi_cpu.py holds its strings to that.
@@ -12,10 +15,41 @@
 #else
 #define HMV_DEV_ENV(name) (static_cast<const char *>(nullptr))
 #endif
+// an integer knob, `dflt` when unset: `static const int x = HMV_DEV_INT("HMV_...", 0);`.  A macro, so that the product build drops the
+// name literal along with the getenv call
+#define HMV_DEV_INT(name, dflt) (HMV_DEV_ENV(name) ? atoi(HMV_DEV_ENV(name)) : (dflt))
 
 namespace hmv {
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_LEAKY = 3 };
+
+// Runs a body at most once per device ordinal (hipFuncSetAttribute for a kernel, a per-device buffer): `static DeviceOnce once;
+// e = once.run([&](int dev) { ...; return hipSuccess; });` (dev_out, optional, receives the current device).  Lock-free once the
+// current device is done; bodies run under a lock, and one that fails is run again by the next call.
+class DeviceOnce {
+    std::atomic<bool> done_[64] = {};
+    std::mutex m_;
+public:
+    template <typename F>
+    hipError_t run(F &&body, int *dev_out = nullptr) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+        if (dev_out) *dev_out = dev;
+        if (done_[dev].load(std::memory_order_acquire)) return hipSuccess;
+        std::lock_guard<std::mutex> lock(m_);
+        if (done_[dev].load(std::memory_order_relaxed)) return hipSuccess;
+        const hipError_t e = body(dev);
+        if (e == hipSuccess) done_[dev].store(true, std::memory_order_release);
+        return e;
+    }
+};
+// the dynamic LDS limit of one or more kernels (in order, up to the first failure): the usual body of a DeviceOnce
+template <typename... K>
+hipError_t set_max_lds(size_t bytes, K... kerns) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(kerns), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)), ...);
+    return e;
+}
 
 // Implicit-GEMM convolution / plain GEMM on fp32 MFMA.
 //   out[m][n] = act( sum_k A[m][k] * Wt[n][k] + bias[n] + res[m'][n] )
@@ -104,16 +138,40 @@ const char *conv_tile_name_f16(ConvTile t, int mode);
 ConvTile conv_pick_tile(int M, int Cout, int K, bool f16 = false, bool has_res = false);
 ConvTile conv_dense_tile(ConvTile t, bool f16);     // the tile a dense-K (Cin % 32 != 0) launch really uses
 bool conv_partial_n(ConvTile t, int Cout);          // launch_conv uses the block-skipping instantiation
+
+// Which kernel families launch_conv may route a conv to: host-side state of the caller (a Runner, an op-level entry), passed along with
+// each launch and never part of ConvParams.  Per family: ROUTE_RULE the launcher's rule, ROUTE_NEVER, ROUTE_FORCE whenever the shape
+// has an instantiation (op-level tests).  Every family's kernels give conv_igemm's bits, so a route changes speed, not results --
+// except ht_m16 = 0, the 32x32x16 partner of the tall-tile layers (an A/B of the op-level tests).
+enum { ROUTE_RULE = -1, ROUTE_NEVER = 0, ROUTE_FORCE = 1 };
+struct ConvRoute {
+    int stream = ROUTE_RULE, gemm8 = ROUTE_RULE, hs = ROUTE_RULE, rds = ROUTE_RULE, ht = ROUTE_RULE, x3k16 = ROUTE_RULE;
+    int gemm8_persist = 1, ht_persist = 1;   // persistent forms: 1 from two tiles per CU up, 0 never, 2 wherever they exist
+    int ht_m16 = 1;                          // MFMA shape of the tall-tile layers: 1 16x16x32 (the engine's), 0 32x32x16
+};
+// the launcher's rule.  A -DHMV_DEV_KNOBS build reads the whole-family knobs into it once (HMV_NO_STREAM / HMV_NO_GEMM8 / HMV_NO_HS /
+// HMV_NO_RDS=1: that family never runs unless a route forces it)
+inline const ConvRoute &conv_rule() {
+    static const ConvRoute r = [] {
+        ConvRoute q;
+        if (HMV_DEV_ENV("HMV_NO_STREAM")) q.stream = ROUTE_NEVER;
+        if (HMV_DEV_ENV("HMV_NO_GEMM8")) q.gemm8 = ROUTE_NEVER;
+        if (HMV_DEV_ENV("HMV_NO_HS")) q.hs = ROUTE_NEVER;
+        if (HMV_DEV_ENV("HMV_NO_RDS")) q.rds = ROUTE_NEVER;
+        return q;
+    }();
+    return r;
+}
+
 // fills mtiles/ntiles and launches
 // `name` (optional) receives the kernel family actually launched ("conv_igemm_f32<256x128,dense,skipN>" ...)
-hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **name = nullptr);
+hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **name = nullptr, const ConvRoute &route = conv_rule());
 // conv_stream.hip: persistent weight-stationary 1x1 convolution (fp16 rows, residual-bearing, short reductions, many pixels);
 // launch_conv routes to it when conv_stream_supported(p).  Bit-identical to conv_igemm's result.
-bool conv_stream_supported(const ConvParams &p);
+bool conv_stream_supported(const ConvParams &p, const ConvRoute &route = conv_rule());
 // true when launch_conv(p) would run on a conv_stream instantiation that can also compute a following 1x1 conv with nx_cout output
-// channels (p as for the launch itself, nx_* fields unset or set)
-bool conv_stream_chain_ok(const ConvParams &p, int nx_cout);
-void conv_stream_set_mode(int mode);   // -1 launcher's rule, 0 never, 1 whenever the shape has an instantiation (op-level tests)
+// channels (p as for the launch itself, nx_* fields unset or set).  Ask with the route of the launch.
+bool conv_stream_chain_ok(const ConvParams &p, int nx_cout, const ConvRoute &route = conv_rule());
 hipError_t launch_conv_stream(const ConvParams &p, hipStream_t s, const char **name);
 
 // ---- small kernels
@@ -173,37 +231,27 @@ hipError_t launch_cheb_mix(const float *y, int ldy, int B, int co, const float *
                            float *out, int ldo, hipStream_t s);
 // conv_gemm8.hip: the fp16 256 x 256 1x1 tile (no residual; optional second source) on the counted-vmcnt, phase-interleaved
 // main loop; launch_conv routes to it when conv_gemm8_supported(p).  Bit-identical to conv_igemm's result.
-bool conv_gemm8_supported(const ConvParams &p);
-void conv_gemm8_set_mode(int mode);   // -1 launcher's rule, 0 never, 1 whenever supported (op-level tests)
-hipError_t launch_conv_gemm8(ConvParams p, hipStream_t s, const char **name);
-void conv_gemm8_set_persistent(int on);   // 1 (default): the persistent form from two tiles per CU up; 0: one workgroup per tile; 2: wherever it exists (tests)
+bool conv_gemm8_supported(const ConvParams &p, const ConvRoute &route = conv_rule());
+hipError_t launch_conv_gemm8(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route = conv_rule());
 
 // conv_hs.hip: persistent weight-stationary R x S convolution for few-channel fp16 layers (3x3 64 -> 64; the 4x4 space-to-depth
 // stem): weights in registers, one halo image per 16 x 16 output block.  Bit-identical to conv_igemm's result.
-bool conv_hs_supported(const ConvParams &p);
-void conv_hs_set_mode(int mode);
+bool conv_hs_supported(const ConvParams &p, const ConvRoute &route = conv_rule());
 hipError_t launch_conv_hs(const ConvParams &p, hipStream_t s, const char **name);
 // conv_rds.hip: fp32 row-decomposed 3x3 convs (HRNet-w40's 40- / 80-channel branches) on the persistent weight-stationary
 // structure; bit-identical to conv_igemm's row-decomposed tiles
-bool conv_rds_supported(const ConvParams &p);
-void conv_rds_set_mode(int mode);   // -1 launch_conv's rule, 0 never, 1 whenever supported (op-level tests)
+bool conv_rds_supported(const ConvParams &p, const ConvRoute &route = conv_rule());
 hipError_t launch_conv_rds(const ConvParams &p, hipStream_t s, const char **name);
 // conv_ht.hip: fp16 3x3 stride-1 convs on tall 512-pixel x 128-channel tiles (K order (32-channel chunk, r, s, c % 32)); the
 // shape rule is asked at weight-packing time, so a layer it takes runs there at every batch size
 bool conv_ht_shape_ok(int R, int S, int stride, int pad, int Cin, int Cout, int H, int W);
-hipError_t launch_conv_ht(ConvParams p, hipStream_t s, const char **name);
-void conv_ht_set_mode(int mode);   // -1 launch_conv's rule, 0 never (the c32 tiles of conv_igemm.hip), 1 always: op-level tests
-int conv_ht_mode();
-void conv_ht_set_shape(int m16);   // MFMA shape of the tall-tile layers: 1 = 16x16x32 (the engine's, round 4), 0 = 32x32x16 (the A/B partner)
-int conv_ht_shape();
-void conv_ht_set_persistent(int on);   // 1 (default): the persistent form from two tiles per CU up; 0: one workgroup per tile; 2: wherever it exists (tests)
+hipError_t launch_conv_ht(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route = conv_rule());
 // conv_m16.hip: the small-launch companion of the 16x16x32-MFMA kernels (64 x 64 / 128 x 128 tiles; 3x3 in conv_ht's K order, plain
 // 1x1): same bits as conv_ht<..., m16>, so a layer's result does not depend on which of the two its batch size selects
 bool conv_m16_supported(const ConvParams &p);
 // the plain 1x1 layers that take the 16x16x32 MFMA: a rule on the layer's SHAPE and epilogue only (never on M), so that the large
 // launches (conv_gemm8<..., m16>) and the small ones (conv_m16's tiles) of one layer agree bit for bit
 bool conv_m16_rule(const ConvParams &p);
-void conv_m16_set_rule(int on);   // 1 (default) / 0: op-level A/B against the 32x32x16 kernels
 hipError_t launch_conv_m16(ConvParams p, hipStream_t s, const char **name);
 
 // gemm_x3.hip: token GEMMs over (hi, lo) fp16 pairs with fp32 output rows (Loader::linear_x3's packing), at every size
@@ -211,9 +259,8 @@ bool gemm_x3_rule(const ConvParams &p);
 hipError_t launch_gemm_x3(ConvParams p, hipStream_t s, const char **name);
 // ... and the short-reduction ones (q / k / v projections) at large row counts: 256 x 256 tiles on a deep ring, bit-identical to
 // conv_igemm's fused split loop (so chosen by size)
-bool gemm_x3k16_ok(const ConvParams &p);
-void gemm_x3k16_set_mode(int mode);   // -1 the size rule, 0 never, 1 whenever the shape allows (op-level tests)
-hipError_t launch_gemm_x3k16(ConvParams p, hipStream_t s, const char **name);
+bool gemm_x3k16_ok(const ConvParams &p, const ConvRoute &route = conv_rule());
+hipError_t launch_gemm_x3k16(ConvParams p, hipStream_t s, const char **name, const ConvRoute &route = conv_rule());
 
 // ---- fusion_kernels.hip: the launch-bound tail as fused kernels
 // Everything of a fusion block behind its to_out GEMM (layers.py:224-233 / 161-174; learnable-query blocks: layers.py:293-299):

@@ -1131,15 +1131,9 @@ __global__ __launch_bounds__(64 * AX_WAVES, 2) void attention_x3_kernel(const _F
 template <int D, int W>
 static hipError_t launch_attention_w(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T, int Tq,
                                      int Tk, float *out, hipStream_t s, int pairs, int nqb) {
-    static bool configured[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     const int lds = AttShape<D, W>::LDS_FLOATS * (int)sizeof(float);
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attention_mfma_kernel<D, W>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        configured[dev] = true;
-    }
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, attention_mfma_kernel<D, W>); }); e != hipSuccess) return e;
     hipLaunchKernelGGL((attention_mfma_kernel<D, W>), dim3((unsigned)B * 8 * nqb), dim3(64 * W), lds, s, q, q_ld, q_bstride, k, v, kv_ld, T, Tq,
                        Tk, nqb, out, pairs);
     return hipGetLastError();
@@ -1158,14 +1152,8 @@ hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, in
     if (x3) {   // the fp16-kernel modes: qkv holds rows of (hi, lo) fp16 pairs [hi 3072 | lo 3072] (the projection GEMMs' pair epilogue) and both
                 // products run on the fp16 matrix cores (attention_x3_kernel); by the arithmetic mode alone, never by a size
         if (Tk <= 0 || Tq <= 0 || B <= 0) return hipErrorInvalidValue;
-        static bool configured[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(attention_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, AX_LDS_BYTES);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
+        static DeviceOnce once;
+        if (const hipError_t e = once.run([](int) { return set_max_lds(AX_LDS_BYTES, attention_x3_kernel); }); e != hipSuccess) return e;
         const int nqb = (Tq + 31) >> 5;
         const _Float16 *ph = reinterpret_cast<const _Float16 *>(qkv);
         hipLaunchKernelGGL(attention_x3_kernel, dim3((unsigned)B * 8 * nqb), dim3(64 * AX_WAVES), AX_LDS_BYTES, s, ph, 6 * 1024, T,

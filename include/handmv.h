@@ -20,7 +20,9 @@
  *   - single-stream at a time: a forward may be enqueued behind another forward of the SAME handle only on the same
  *     stream; to move a handle to another stream, synchronise (or event-order) the first stream before the next
  *     hmv_forward.  Two forwards of one handle in flight on two streams race on the workspace.
- * Concurrency comes from several handles (one per stream / rank), which share nothing.
+ * Concurrency comes from several handles (one per stream / rank), which share nothing.  Kernel selection is per call, not
+ * shared state, so the hmv_op_* entries (a kernel_sel applies to that one call) may run on any thread while other threads run
+ * forwards of their handles.
  * hmv_set_tensor + hmv_finalize_weights may be repeated on a live handle: finalisation synchronises the device and drops
  * every cached graph before it frees the previous weight buffers.
  */
@@ -138,7 +140,8 @@ int hmv_poison_workspace(hmv_handle h, int32_t value, void *stream);
 int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic,
                 float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
 
-/* Human-readable description of the last failure on this handle (or on creation when h is NULL). */
+/* Human-readable description of the last failure on this handle, or with h == NULL of the calling thread's last failed call
+ * without a handle (hmv_create, the hmv_op_* entries ...): per thread, like errno. */
 const char *hmv_last_error(hmv_handle h);
 
 void hmv_destroy(hmv_handle h);
@@ -176,12 +179,6 @@ int hmv_op_conv2d(int32_t device, const float *in, int32_t N, int32_t H, int32_t
                   const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S,
                   int32_t stride, int32_t pad, const float *residual, int32_t relu, float *out, void *stream);
 
-/* TEST HOOK (process-global, single-threaded like the kernel_sel entries below): which kernel the split-pair token GEMMs with a short
- * reduction (the q / k / v projections of the fp16-kernel modes: layers.py:213-215) take -- -1 the engine's size rule (gemm_x3.hip's
- * 256 x 256 tiles from ~200 tiles up, conv_igemm's fused split loop below), 0 never the 256 x 256 tiles, 1 whenever the shape allows.
- * The two give the same bits; the identity test drives both through hmv_op_conv2d_ex(dtype = HMV_F32X3). */
-int hmv_set_x3k16_mode(int32_t mode);
-
 /* The same op in any arithmetic mode (dtype = HMV_F32 | HMV_F16 | HMV_F32X3): the fp32 input / residual are converted to the
  * mode's storage format on the device, the layer is packed exactly as hmv_finalize_weights packs it (no BatchNorm), the
  * output is fp32.  Cin must be a multiple of 8 for the fp16-based modes. */
@@ -218,13 +215,20 @@ int hmv_op_conv2d_sel(int32_t device, const float *in, int32_t N, int32_t H, int
  * its tiles with the next tile's operands in flight; what a launch of two or more tiles per CU runs on; 3 is one workgroup per tile
  * whatever the size; same bits; channel-tile counts other than 1, 2, 4 have no persistent form and run as 3); 8 = as 2 with conv_gemm8's
  * PERSISTENT form wherever it exists (2 is one workgroup per tile whatever the size; same bits).  *kernel_name (optional) receives the family that ran.
- * TEST HOOKS: the hmv_op_* entries with a kernel_sel argument switch PROCESS-GLOBAL kernel-selection state for the duration of the
- * call.  They are single-threaded test / probe entries: never call one concurrently with any other hmv_* call of the process
- * (an hmv_forward running on another thread would see the forced selection). */
+ * The kernel_sel of the hmv_op_* entries applies to that call alone. */
 int hmv_op_conv2d_f16(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
                       const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
                       int32_t pad, const float *residual, int32_t relu, void *out_f16, int32_t kernel_sel,
                       const char **kernel_name, void *stream);
+
+/* hmv_op_conv2d_ex(dtype = HMV_F32X3) with a kernel selector for the split-pair token GEMMs with a short reduction (the q / k / v
+ * projections of the fp16-kernel modes: layers.py:213-215): 0 = the launcher's choice (gemm_x3.hip's 256 x 256 tiles from ~200 tiles
+ * up, conv_igemm's fused split loop below), 1 = conv_igemm's fused split loop only, 2 = gemm_x3k16 whenever the shape allows.  The two
+ * give the same bits.  fp32 output rows; *kernel_name (optional) receives the family that ran. */
+int hmv_op_conv2d_x3(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                     const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
+                     int32_t pad, const float *residual, int32_t relu, float *out, int32_t kernel_sel, const char **kernel_name,
+                     void *stream);
 
 /* The up-sampling terms of an HRNet fuse layer (hrnet.py:194-212) through hr_fuse.hip alone (op-level parity tests):
  *   out = act(base + sum_s Upsample_{2^shift_s, nearest}(W_s x_s + b_s)),   terms added in the order given (1 <= nsrc <= 3, 1 <= shift <= 3).

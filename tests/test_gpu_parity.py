@@ -388,7 +388,7 @@ X3K16_SHAPES = [(2, 21, 8, 544, 3072, 1, 1, 0, False, False), (1, 1, 300, 256, 7
 
 
 @pytest.mark.parametrize("shape", X3K16_SHAPES)
-def test_split_pair_gemm_large_tiles_are_bit_identical(shape):
+def test_split_pair_gemm_large_tiles_by_kernel_sel(shape):
     """gemm_x3k16_f16 (256 x 256 tiles, k-steps of 16 channels on a four-stage ring: what the projections run on at large row counts)
     against conv_igemm's fused split loop (what they run on otherwise): the same per-element sequence of 32x32x16 MFMAs, the same
     bits -- which is what lets the launcher choose by size -- and torch fp64 at fp32-grade error."""
@@ -399,17 +399,16 @@ def test_split_pair_gemm_large_tiles_are_bit_identical(shape):
     dev = torch.device("cuda:0")
     xin = x.permute(0, 2, 3, 1).contiguous().to(dev)
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
-    outs = []
-    try:
-        for mode in (1, 0):
-            assert lib.hmv_set_x3k16_mode(mode) == 0
-            out = torch.full((N, H, W, Cout), float("nan"), device=dev)
-            rc = lib.hmv_op_conv2d_ex(0, 2, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p), Cout, 1, 1, 1, 0,
-                                      None, 0, out.data_ptr(), None)
-            assert rc == 0, lib.hmv_last_error(None)
-            outs.append(out.cpu())
-    finally:
-        lib.hmv_set_x3k16_mode(-1)
+    outs, names = [], []
+    for sel in (2, 1):   # gemm_x3k16 whenever the shape allows / the fused split loop only
+        out = torch.full((N, H, W, Cout), float("nan"), device=dev)
+        kname = ctypes.c_char_p()
+        rc = lib.hmv_op_conv2d_x3(0, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p), Cout, 1, 1, 1, 0,
+                                  None, 0, out.data_ptr(), sel, ctypes.byref(kname), None)
+        assert rc == 0, lib.hmv_last_error(None)
+        outs.append(out.cpu())
+        names.append(kname.value.decode())
+    assert names[0].startswith("gemm_x3k16_f16") and "gemm_x3k16" not in names[1], names
     assert torch.isfinite(outs[0]).all()
     assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), (outs[0] - outs[1]).abs().max()
     got = outs[0].permute(0, 3, 1, 2).double()
@@ -653,6 +652,61 @@ def test_tall_tile_kernel_mfma_16x16x32(shape):
             ref = ref.clamp_min(0)
         err = (a.double() - ref).abs().max().item() / ref.abs().max().item()
         assert err < 1e-3, err
+
+
+def test_op_hooks_run_beside_forwards_of_other_handles():
+    """Kernel selection is no process-wide switch: an op-level kernel_sel is an argument of that one call.  While one thread runs
+    hmv_op_conv2d_f16 with kernel_sel 5 / 6 (the 32x32x16 partner of the tall-tile layers: other bits than the engine's 16x16x32
+    kernels), the main thread runs fp16 forwards of a cfg-2-shaped handle (its layer2 3x3 convs are tall-tile layers) on a stream of
+    its own: each forward returns the bits of the handle's solo run."""
+    import threading
+    from handmvnet_amd import _lib
+    lib = _lib.load()
+    m, cfg, sd, (x, bbox, intr), _ = _model("cfg2s_r18_v4_256")
+    m.half()
+    m.use_graphs(False)   # eager: every forward plans and launches again
+    dev = torch.device("cuda:0")
+    xd, bd, cam = torch.from_numpy(x).to(dev), torch.from_numpy(bbox).to(dev), {"intrinsic": torch.from_numpy(intr).to(dev)}
+    stream = torch.cuda.Stream()
+
+    def forward():
+        with torch.cuda.stream(stream):
+            out = m(xd, bd, cam)
+        stream.synchronize()
+        return {k: v.cpu() for k, v in out.items()}
+
+    solo = forward()
+    N, H, W, Cin, Cout, k, stride, pad, _, relu = HT_SHAPES[0]
+    g = torch.Generator().manual_seed(11)
+    xo = torch.randn(N, H, W, Cin, generator=g).to(dev)
+    wc = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).numpy()
+    bc = torch.randn(Cout, generator=g).numpy()
+    outs = {sel: torch.empty(N, H, W, Cout, device=dev, dtype=torch.float16) for sel in (5, 6)}
+    torch.cuda.synchronize()
+    names, errors = set(), []
+
+    def hooks():
+        for _ in range(10):
+            for sel in (5, 6):
+                kname = ctypes.c_char_p()
+                rc = lib.hmv_op_conv2d_f16(0, xo.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p),
+                                           Cout, k, k, stride, pad, None, int(relu), outs[sel].data_ptr(), sel, ctypes.byref(kname), None)
+                if rc != 0:
+                    errors.append(lib.hmv_last_error(None))
+                    return
+                names.add(kname.value.decode())
+
+    t = threading.Thread(target=hooks)
+    t.start()
+    try:
+        for i in range(10):
+            got = forward()
+            for key in solo:
+                assert torch.equal(got[key], solo[key]), (i, key)
+    finally:
+        t.join()
+    assert not errors, errors
+    assert len(names) == 2 and "conv_ht_f16<512x128,3x3>" in names and all("m16" not in n for n in names), names
 
 
 # fp32 residual 1x1 convs on the persistent weight-stationary kernel (conv_stream_f32): K = 64 / 128 / 256, one to four channel slices,

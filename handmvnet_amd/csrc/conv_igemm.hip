@@ -737,12 +737,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                                 const bool st = m < p.M && col < cend;
                                 if constexpr (SPLIT) {
                                     f16x8 hv, lv8;
+                                    bool ov = false;
 #pragma unroll
                                     for (int u = 0; u < 8; ++u) {
+                                        ov |= out_of_pair_range(t[u]);
                                         const float c = fminf(fmaxf(t[u], -65504.f), 65504.f);
                                         hv[u] = (_Float16)c;
                                         lv8[u] = (_Float16)(c - (float)hv[u]);
                                     }
+                                    note_range(p.sat, st && ov);
                                     // every lane stores twice (the vmcnt arithmetic counts on it): lanes outside the tensor hit the trash page
                                     _Float16 *dst = st ? orow + col : reinterpret_cast<_Float16 *>(trash);
                                     *reinterpret_cast<f16x8 *>(dst) = hv;
@@ -863,12 +866,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                             if (!(m < p.M && col < cend)) continue;
                             if (p.out_split) {   // fp32 value -> (hi, lo) fp16 pair, hi + lo == value to ~2^-22
                                 f16x8 hv, lv8;
+                                bool ov = false;
 #pragma unroll
                                 for (int u = 0; u < 8; ++u) {
+                                    ov |= out_of_pair_range(t[u]);
                                     const float c = fminf(fmaxf(t[u], -65504.f), 65504.f);
                                     hv[u] = (_Float16)c;
                                     lv8[u] = (_Float16)(c - (float)hv[u]);
                                 }
+                                note_range(p.sat, ov);
                                 *reinterpret_cast<f16x8 *>(orow + col) = hv;
                                 *reinterpret_cast<f16x8 *>(orow + col + rowc) = lv8;
                             } else {
@@ -1010,12 +1016,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                         if (okr[u]) {
                             if (p.out_split) {   // fp32 value -> (hi, lo) fp16 pair, hi + lo == value to ~2^-22
                                 f16x4 hv, lv;
+                                bool ov = false;
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
+                                    ov |= out_of_pair_range(t[j]);
                                     const float c = fminf(fmaxf(t[j], -65504.f), 65504.f);
                                     hv[j] = (_Float16)c;
                                     lv[j] = (_Float16)(c - (float)hv[j]);
                                 }
+                                note_range(p.sat, ov);
                                 _Float16 *op = reinterpret_cast<_Float16 *>(outv) + orow[u] * p.ldc + col;
                                 *reinterpret_cast<f16x4 *>(op) = hv;
                                 *reinterpret_cast<f16x4 *>(op + (p.ldc >> 1)) = lv;
@@ -1110,12 +1119,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                         if (!okr[u]) continue;
                         if (p.out_split) {   // fp32 value -> (hi, lo) fp16 pair, hi + lo == value to ~2^-22
                             _Float16 hv[W], lv[W];
+                            bool ov = false;
 #pragma unroll
                             for (int j = 0; j < W; ++j) {
+                                ov |= out_of_pair_range(t[j >> 2][j & 3]);
                                 const float c = fminf(fmaxf(t[j >> 2][j & 3], -65504.f), 65504.f);
                                 hv[j] = (_Float16)c;
                                 lv[j] = (_Float16)(c - (float)hv[j]);
                             }
+                            note_range(p.sat, ov);
                             _Float16 *op = reinterpret_cast<_Float16 *>(outv) + orow[u] * p.ldc + col;
                             if constexpr (W == 8) {
                                 *reinterpret_cast<f16x8 *>(op) = f16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]};

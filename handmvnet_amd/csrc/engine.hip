@@ -33,6 +33,24 @@ inline int cpad(int c) { return (c + 3) / 4 * 4; }   // NHWC channel stride: 16-
 
 thread_local std::string g_create_err;   // hmv_last_error(NULL): per thread, like errno
 
+// The range word of ONE op-level call (hmv_op_* entries in the (hi, lo) pair modes): the call's pair conversions report a clamped value
+// into it (note_range, kernels.h) and the entry returns HMV_ERR_RANGE after synchronising.
+struct RangeWord {
+    int *p = nullptr;
+    hipError_t alloc() {
+        const int zero = 0;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(p, &zero, sizeof(int), hipMemcpyHostToDevice);
+        return e;
+    }
+    bool saturated() const {   // after the call's stream has been synchronised
+        int v = 0;
+        return p && hipMemcpy(&v, p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && v != 0;
+    }
+    ~RangeWord() { if (p) (void)hipFree(p); }
+};
+const char *const kRangeMsg = "a value outside the (hi, lo) fp16 pair range (|v| > 65504) was clamped: the result is not fp32-equivalent";
+
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct HostTensor {
@@ -231,6 +249,9 @@ struct hmv_engine {
     std::vector<ProfRec> prof;
     size_t prof_used = 0;
     int launches = 0;      // device operations (kernels, memsets, copies) enqueued by the last eager / captured forward
+    // range word: every (hi, lo) pair conversion of a forward that clamps a value (|v| > 65504) sets it to 1 (note_range, kernels.h); sticky
+    // until hmv_range_status reads it.  Its own allocation, outside the workspace arena: hmv_poison_workspace and cached graphs leave it alone
+    int *sat = nullptr;
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -316,6 +337,7 @@ struct Loader {
     }
 
     bool split = false;   // HMV_F32X3: fp16 layers carry [W_hi | W_hi | W_lo] against the activation sequence hi, lo, hi
+    std::string src_key;  // the state_dict key(s) of the layer being packed (conv(): weight key + BatchNorm prefix), for errors
 
     // Generic finish: `wt(o, k)` supplies the un-scaled weight for output o, packed index k.
     template <typename F>
@@ -335,6 +357,14 @@ struct Loader {
             double bb = shift ? (*shift)[o] : 0.0;
             if (conv_bias) bb += (double)conv_bias[o] * sc;
             b[o] = (float)bb;
+        }
+        if (f16 && !lo_plane) {   // plain fp16 storage: a folded weight past fp16's range would be packed as +-inf
+            for (size_t i = 0; i < w.size(); ++i)
+                if (!(std::fabs(w[i]) < 65520.f)) {
+                    rc = h->fail(HMV_ERR_RANGE, "%s: folded weight %g (output channel %d) is outside the fp16 range (|w| < 65520)",
+                                 src_key.empty() ? label.c_str() : src_key.c_str(), (double)w[i], (int)(i / L.Kpad));
+                    return;
+                }
         }
         if (f16) {   // BN scale is folded in fp32/double first, THEN rounded once to fp16
             std::vector<_Float16> wh(w.size());
@@ -366,6 +396,8 @@ struct Loader {
               int Cout, int Cin, int R, int S, int cin_pad = 0, bool f16 = false, bool rd = false, const float *wsrc = nullptr, bool tall = false) {
         const HostTensor *w = wsrc ? nullptr : get(wkey, {Cout, Cin, R, S});
         const HostTensor *cb = bkey.empty() ? nullptr : get(bkey, {Cout});
+        src_key = wkey + (bn.empty() ? std::string() : " (folded with " + bn + ")");
+        struct Clear { std::string &k; ~Clear() { k.clear(); } } clear_key{src_key};
         std::vector<double> sc, sh;
         const bool has_bn = !bn.empty();
         if (has_bn && !bn_fold(bn, Cout, sc, sh)) return;
@@ -546,6 +578,21 @@ int hmv_create(const hmv_config *cfg, hmv_handle *out) {
     }
     if (cfg->device < 0 || cfg->device >= ndev) return bad("device ordinal out of range");
     hmv_engine *h = new hmv_engine();
+    {   // the range word, on the handle's device (the calling thread's current device is left as it was)
+        int prev = 0;
+        hipError_t e = hipGetDevice(&prev);
+        if (e == hipSuccess) e = hipSetDevice(cfg->device);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->sat), sizeof(int));
+        if (e == hipSuccess) e = hipMemset(h->sat, 0, sizeof(int));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        (void)hipSetDevice(prev);
+        if (e != hipSuccess) {
+            g_create_err = std::string("range word allocation failed: ") + hipGetErrorString(e);
+            if (h->sat) (void)hipFree(h->sat);
+            delete h;
+            return HMV_ERR_HIP;
+        }
+    }
     if (const char *g = getenv("HMV_GRAPHS")) h->graphs = atoi(g) != 0;
     h->ff_fuse = HMV_DEV_ENV("HMV_NO_FFFUSE") == nullptr;
     h->cheb_fuse = HMV_DEV_ENV("HMV_NO_CHEBFUSE") == nullptr;
@@ -1180,7 +1227,7 @@ struct Runner {
             if (L.x3n) p.x3_plane = L.plane;
             else p.cwrap = 2 * L.plane;
             p.acc_shift = L.acc_shift;
-            if (out_f16) { p.out_split = 1; p.ldc = 2 * ldc; }
+            if (out_f16) { p.out_split = 1; p.ldc = 2 * ldc; p.sat = h->sat; }
             if (res) { p.res_split = 1; p.ldr = 2 * ldr; }
         }
         const bool pooled = pool.h > 0;
@@ -1339,7 +1386,7 @@ struct Runner {
             p.rows = rows; p.d = d; p.ld = ldt;
             p.n1g = n1g; p.n1b = n1b; p.fg = fg; p.fb = fb; p.n2g = n2g; p.n2b = n2b;
             p.w1 = ff1.w; p.b1 = ff1.bias; p.ldw1 = ff1.Kpad; p.w2 = ff2.w; p.b2 = ff2.bias; p.ldw2 = ff2.Kpad;
-            p.out = y; p.ldo = ldt; p.hid = ff1.Cout; p.out_pairs = y_pairs;
+            p.out = y; p.ldo = ldt; p.hid = ff1.Cout; p.out_pairs = y_pairs; p.sat = h->sat;
 #ifdef HMV_DEV_KNOBS
             static unsigned long long *ffdbg = nullptr;   // HMV_FF_DBG=1: phase stamps of the last launch, printed by the next one (never under graph capture)
             if (HMV_DEV_ENV("HMV_FF_DBG")) {
@@ -1408,7 +1455,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         const HrNet &hr = h->hr;
         float *in4 = R.alloc((size_t)N * H * W * (split ? 8 : 4));
         if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4, s));
-        else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4, N, H, W, s));
+        else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4, N, H, W, s, h->sat));
         else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4, N, H, W, s));
         else LAUNCH(launch_nchw_to_nhwc4(x, in4, N, H, W, s));
         const int H1 = (H + 2 - 3) / 2 + 1, W1 = (W + 2 - 3) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
@@ -1602,7 +1649,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
     float *in4 = R.alloc((size_t)N * Hs * Ws * (split ? 16 : (h16 ? 8 : 12)));
     if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4, s, /*s2d=*/true));
-    else LAUNCH(launch_nchw_to_s2d(x, in4, N, H, W, smode, s));
+    else LAUNCH(launch_nchw_to_s2d(x, in4, N, H, W, smode, s, h->sat));
     const int H1 = (H + 6 - 7) / 2 + 1, W1 = (W + 6 - 7) / 2 + 1;   // == Hs, Ws
     int hh = (H1 + 2 - 3) / 2 + 1, ww = (W1 + 2 - 3) / 2 + 1, C = 64;
     // fp16, many frames: conv1 + BN + ReLU + maxpool as ONE launch (conv_hs.hip's pooled epilogue: the 64-channel conv map, 8x the
@@ -1797,7 +1844,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     if (!h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = R.alloc((size_t)N * NJ * ldt);
     LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc,
                                   (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe,   // the learnable-query blocks add their own PE
-                                  (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs));
+                                  (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
     R.release(coords);
 
     float *X = tokens;
@@ -1810,7 +1857,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         float *pairs = ready_pairs;
         if (!pairs) {
             pairs = R.alloc((size_t)rows * ldt);                           // [hi ldt | lo ldt] halfs per row
-            LAUNCH(launch_rows_f32_to_half(a, pairs, (size_t)rows, ldt, 2, s));
+            LAUNCH(launch_rows_f32_to_half(a, pairs, (size_t)rows, ldt, 2, s, h->sat));
         }
         R.conv(L, pairs, rows, 1, 1, 1, 0, 0, out, ldc, nullptr, 0, ACT_NONE, 1, 1, 0, 0, 0, 0, 0, pairs_out);
         R.release(pairs);
@@ -1829,12 +1876,12 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
             if (cross) {
                 float *kv = R.alloc((size_t)rows * 2 * INNER_LQ);
                 project(a.kv, xp, rows, kv, 2 * INNER_LQ);
-                LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0));
+                LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
                 R.release(kv);
             } else {
                 float *qkv = R.alloc((size_t)rows * 3 * INNER_LQ);
                 project(a.qkv, xp, rows, qkv, 3 * INNER_LQ);
-                LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0));
+                LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
                 R.release(qkv);
             }
             if (R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, tx3)) {
@@ -1891,7 +1938,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         float *att = R.alloc((size_t)qrows * INNER);
         // fp16-kernel modes, fused tail: the attention rows leave the kernel as (hi, lo) pairs and to_out is a split-pair GEMM
         const bool tx3 = a.out_x3.plane != 0 && R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, true);
-        if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3));
+        if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
         else LAUNCH(hipMemsetAsync(att, 0, (size_t)qrows * INNER * sizeof(float), s));   // (zero rows are zero pairs)
         R.release(qkv);
         if (R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, tx3)) {   // norm1(to_out + _q) -> FeedForward -> norm2 in one launch behind the GEMM
@@ -2165,6 +2212,7 @@ void hmv_destroy(hmv_handle h) {
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (void *p : h->dev_allocs) (void)hipFree(p);
+    if (h->sat) (void)hipFree(h->sat);
     if (h->arena) (void)hipFree(h->arena);
     for (float *p : {h->cap_feat0, h->cap_coords, h->cap_tokens, h->cap_fused})
         if (p) (void)hipFree(p);
@@ -2251,6 +2299,24 @@ int hmv_profile_count(hmv_handle h) { return h ? (int)h->prof_used : 0; }
 /* Device operations (kernel launches, memsets, device copies) the last eagerly run forward enqueued. */
 int hmv_launch_count(hmv_handle h) { return h ? h->launches : 0; }
 
+int hmv_range_status(hmv_handle h, int32_t *saturated, void *stream) {
+    if (!h || !saturated) {
+        if (h) h->fail(HMV_ERR_ARG, "hmv_range_status: null argument");
+        return HMV_ERR_ARG;
+    }
+    *saturated = 0;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // (a second stream of the handle is joined into this one)
+    int v = 0;
+    HIPCHK(h, hipMemcpy(&v, h->sat, sizeof(int), hipMemcpyDeviceToHost));
+    if (v) {
+        const int zero = 0;
+        HIPCHK(h, hipMemcpy(h->sat, &zero, sizeof(int), hipMemcpyHostToDevice));
+    }
+    *saturated = v != 0;
+    return HMV_OK;
+}
+
 int hmv_profile_get(hmv_handle h, int32_t index, const char **name, const char **label, float *ms, double *flops) {
     if (!h || index < 0 || (size_t)index >= h->prof_used) return HMV_ERR_ARG;
     ProfRec &r = h->prof[index];
@@ -2291,12 +2357,15 @@ int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, 
     // the kernel takes rows of (hi, lo) fp16 pairs (what the projection GEMMs write in those modes): split the fp32 rows first
     hipStream_t s = static_cast<hipStream_t>(stream);
     void *pairs = nullptr;
-    hipError_t e = hipMalloc(&pairs, (size_t)B * T * 3072 * 4);
-    if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, (size_t)B * T, 3072, 2, s);
-    if (e == hipSuccess) e = launch_attention(static_cast<const float *>(pairs), B, T, Tq, koff, Tk, out, s, 0, 1);
+    RangeWord rw;
+    hipError_t e = rw.alloc();
+    if (e == hipSuccess) e = hipMalloc(&pairs, (size_t)B * T * 3072 * 4);
+    if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, (size_t)B * T, 3072, 2, s, rw.p);
+    if (e == hipSuccess) e = launch_attention(static_cast<const float *>(pairs), B, T, Tq, koff, Tk, out, s, 0, 1, rw.p);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (pairs) (void)hipFree(pairs);
     if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
+    if (rw.saturated()) { g_create_err = "hmv_op_attention_x3: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
     return HMV_OK;
 }
 
@@ -2360,14 +2429,16 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
     const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
     const void *x = in, *res = residual;
     void *din = nullptr, *dres = nullptr;
-    hipError_t e = hipSuccess;
-    if (rc == HMV_OK && half) {   // fp16 rows, or (hi, lo) pairs in HMV_F32X3
+    RangeWord rw;
+    hipError_t e = rc == HMV_OK ? rw.alloc() : hipSuccess;
+    eng.sat = rw.p;
+    if (rc == HMV_OK && e == hipSuccess && half) {   // fp16 rows, or (hi, lo) pairs in HMV_F32X3
         const int mode = dtype == HMV_F32X3 ? 2 : 1;
         const size_t rows_in = (size_t)N * H * W, rows_out = (size_t)N * Ho * Wo;
         e = hipMalloc(&din, rows_in * Cin * 2 * mode);
         if (e == hipSuccess && residual) e = hipMalloc(&dres, rows_out * Cout * 2 * mode);
-        if (e == hipSuccess) e = launch_rows_f32_to_half(in, din, rows_in, Cin, mode, s);
-        if (e == hipSuccess && residual) e = launch_rows_f32_to_half(residual, dres, rows_out, Cout, mode, s);
+        if (e == hipSuccess) e = launch_rows_f32_to_half(in, din, rows_in, Cin, mode, s, rw.p);
+        if (e == hipSuccess && residual) e = launch_rows_f32_to_half(residual, dres, rows_out, Cout, mode, s, rw.p);
         x = din;
         res = dres;
     }
@@ -2386,6 +2457,7 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
     for (void *ptr : eng.dev_allocs) (void)hipFree(ptr);
     if (rc != HMV_OK) { g_create_err = std::string(who) + ": " + eng.err; return rc; }
     if (e != hipSuccess) { g_create_err = std::string(who) + ": " + hipGetErrorString(e); return HMV_ERR_HIP; }
+    if (rw.saturated()) { g_create_err = std::string(who) + ": " + kRangeMsg; return HMV_ERR_RANGE; }
     return HMV_OK;
 }
 

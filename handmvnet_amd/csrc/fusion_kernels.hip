@@ -304,12 +304,15 @@ __global__ __launch_bounds__(64 * FF_WAVES) void ff_block_kernel(const FfBlockPa
                     *reinterpret_cast<ff32x4 *>(p.out + (size_t)row * p.ldo + c) = v[r][i];
                     if (p.out_pairs) {   // hi = fp16(clamp(v)), lo = fp16(clamp(v) - hi): split_f16 of misc_kernels.hip
                         ff16x4 hi, lo;
+                        bool ov = false;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
+                            ov |= out_of_pair_range(v[r][i][e]);
                             const float cv = fminf(fmaxf(v[r][i][e], -65504.f), 65504.f);
                             hi[e] = (_Float16)cv;
                             lo[e] = (_Float16)(cv - (float)hi[e]);
                         }
+                        note_range(p.sat, ov);
                         _Float16 *pr = reinterpret_cast<_Float16 *>(p.out_pairs) + (size_t)row * 2 * p.ldo + c;
                         *reinterpret_cast<ff16x4 *>(pr) = hi;
                         *reinterpret_cast<ff16x4 *>(pr + p.ldo) = lo;

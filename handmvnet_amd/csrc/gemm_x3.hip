@@ -370,14 +370,17 @@ __global__ __launch_bounds__(512, 2) void gemm_x3k16_f16(const ConvParams p) {
                     }
                     const int col = nb0 + 32 * b + 8 * (2 * qp + kh);
                     xf16x8 hv, lv;
+                    bool ov = false;
 #pragma unroll
                     for (int t = 0; t < 8; ++t) {
                         // kh = 0: columns 0 .. 3 are its own, 4 .. 7 came from the kh = 1 lane; kh = 1: the other way round
                         const float x = (t < 4) == (kh == 0) ? own[t & 3] : got[t & 3];
+                        ov |= out_of_pair_range(x);
                         const float c = fminf(fmaxf(x, -65504.f), 65504.f);
                         hv[t] = (_Float16)c;
                         lv[t] = (_Float16)(c - (float)hv[t]);
                     }
+                    note_range(p.sat, ov && m < p.M && col < cend);
                     if (m < p.M && col < cend) {
                         *reinterpret_cast<xf16x8 *>(prow + col) = hv;
                         *reinterpret_cast<xf16x8 *>(prow + col + rowc) = lv;

@@ -205,15 +205,15 @@ __global__ __launch_bounds__(64 * HRF_WAVES) void hr_fuse_up_kernel(const HrFuse
 bool hr_fuse_up_plan(HrFuseParams &p) {
     p.th = 0;
     p.lds = 0;
-    if (p.nsrc < 1 || p.nsrc > 3 || p.C % (p.f16 ? 8 : 4) || p.C > 256 || p.ldc % 4 || p.N <= 0 || p.H <= 0 || p.W <= 0) return false;
+    const int epu = p.f16 ? 8 : 4;   // elements per 16-byte unit: row strides are whole units (the loads / stores move 16 bytes)
+    if (p.nsrc < 1 || p.nsrc > 3 || p.C % epu || p.C > 256 || p.ldc % epu || p.N <= 0 || p.H <= 0 || p.W <= 0) return false;
     if ((long long)p.H * p.W * p.ldc >= (1ll << 31) || p.C < 8) return false;   // 32-bit element offsets inside an image
     const int esz = p.f16 ? 2 : 4;
     for (int s = 0; s < p.nsrc; ++s) {
         const HrFuseSrc &S = p.src[s];
-        if (S.shift < 1 || S.shift > 3 || S.C % 16 || S.C > 512 || S.ld % 4 || S.ldw % 4 || S.ldw < S.C) return false;
+        if (S.shift < 1 || S.shift > 3 || S.C % 16 || S.C > 512 || S.ld % epu || S.ldw % 4 || S.ldw < S.C) return false;
         if (S.H != (p.H >> S.shift) || S.W != (p.W >> S.shift) || (S.H << S.shift) != p.H || (S.W << S.shift) != p.W) return false;
     }
-    const int epu = p.f16 ? 8 : 4;   // elements per 16-byte unit
     p.rcpu = (unsigned)(((1ull << 32) + (unsigned)(p.C / epu) - 1) / (unsigned)(p.C / epu));   // ceil(2^32 / units per pixel): exact quotients for units < 2^16
     for (int s = 0; s < p.nsrc; ++s) p.src[s].rcpu = (unsigned)(((1ull << 32) + (unsigned)(p.src[s].C / epu) - 1) / (unsigned)(p.src[s].C / epu));
     const int nbn = (p.C + 15) / 16;   // 16-channel blocks (the weight / bias rows past C are zeros: Layer's Cout_pad)

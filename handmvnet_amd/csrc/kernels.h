@@ -51,6 +51,16 @@ hipError_t set_max_lds(size_t bytes, K... kerns) {
     return e;
 }
 
+// (hi, lo) fp16 pairs hold |v| <= 65504 only; every pair conversion clamps to that range.  A conversion site passes `over`
+// (this lane clamped a value it stores: |v| > 65504, or NaN) and the wave reports it once: the lowest firing lane writes 1 to
+// *sat (the handle's range word; hmv_range_status reads and clears it) with a plain vector store.  sat == nullptr: no report.
+// The stored bits never depend on it.
+__device__ __forceinline__ void note_range(int *sat, bool over) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(over);
+    if (m != 0ull && sat != nullptr && __lane_id() == (unsigned)__builtin_ctzll(m)) *reinterpret_cast<volatile int *>(sat) = 1;
+}
+__device__ __forceinline__ bool out_of_pair_range(float v) { return !(__builtin_fabsf(v) <= 65504.f); }
+
 // Implicit-GEMM convolution / plain GEMM on fp32 MFMA.
 //   out[m][n] = act( sum_k A[m][k] * Wt[n][k] + bias[n] + res[m'][n] )
 // A[m][k] is gathered on the fly from an NHWC tensor: m = (img, ho, wo), k = (chunk, r, s, c % 32).
@@ -90,6 +100,7 @@ struct ConvParams {
     int acc_shift;      // split layers: the packed weights are W * 2^acc_shift (keeps W_lo out of the fp16 subnormals);
     float acc_scale;    //   the epilogue multiplies the accumulator by 2^-acc_shift (filled in by launch_conv)
     int out_split;      // write (hi, lo) pairs (plane stride ldc / 2) instead of one fp16 value
+    int *sat;           // out_split: range word of the caller (note_range), may be null
     int ngroup;         // gemm_x3.hip: > 0 = N-tiles per XCD (each XCD owns a column range of the weights, which then stay in ITS L2)
     int m16;            // fp16 1x1 that multiplies on v_mfma_f32_16x16x32_f16 at every batch size (filled in by launch_conv from conv_m16_rule)
     int tall;           // fp16 3x3 whose weights are packed in conv_ht.hip's K order: that kernel or an error, at every batch size
@@ -192,12 +203,12 @@ hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N
                                   const float *std, int out_mode, void *out, hipStream_t s, bool s2d = false);
 // HMV_F32X3 helpers: tensors whose rows are [hi plane | lo plane] fp16 pairs
 // space-to-depth stem input (misc_kernels.hip): mode 0 fp32 [12], 1 fp16 [16], 2 split [hi16 | lo16] per 2x2 pixel block
-hipError_t launch_nchw_to_s2d(const float *x, void *out, int N, int H, int W, int mode, hipStream_t s);
-hipError_t launch_nchw_to_nhwc_split(const float *x, void *out, int N, int H, int W, hipStream_t s);
+hipError_t launch_nchw_to_s2d(const float *x, void *out, int N, int H, int W, int mode, hipStream_t s, int *sat = nullptr);
+hipError_t launch_nchw_to_nhwc_split(const float *x, void *out, int N, int H, int W, hipStream_t s, int *sat = nullptr);
 hipError_t launch_maxpool3s2_split(const void *in, void *out, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 hipError_t launch_nhwc_split_to_nchw(const void *in, float *out, int N, int H, int W, int C, hipStream_t s);
 // fp32 rows -> fp16 rows (mode 1) / split [hi | lo] rows (mode 2)
-hipError_t launch_rows_f32_to_half(const float *in, void *out, size_t rows, int C, int mode, hipStream_t s);
+hipError_t launch_rows_f32_to_half(const float *in, void *out, size_t rows, int C, int mode, hipStream_t s, int *sat = nullptr);
 hipError_t launch_maxpool3s2_f16(const void *in, void *out, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 hipError_t launch_nhwc_f16_to_nchw(const void *in, float *out, int N, int H, int W, int C, hipStream_t s);
 // tokens[(n*21+j)][col0 + c] = sum_t w_t * s[(n*21+j)*4+t][c]
@@ -206,18 +217,19 @@ hipError_t launch_sample_blend(const float *s4, int lds4, int C, int N, int H, i
 // pos2d / FoV columns, zero padding columns; optional raw copy (before PE) and PE add
 hipError_t launch_tokens_finalize(float *tokens, int ldt, int d, int fdim, int N, int V, const float *coords,
                                   const float *bbox, const float *intr, int pos_mask, const float *pe,
-                                  float *raw_copy, hipStream_t s, void *pairs = nullptr);   // pairs: rows again as [hi ldt | lo ldt] halfs
+                                  float *raw_copy, hipStream_t s, void *pairs = nullptr, int *sat = nullptr);   // pairs: rows again as [hi ldt | lo ldt] halfs
 // y = LN(x) ; optional second LN applied to y -> y2.  Pads [d, ld) are written as zeros.
 hipError_t launch_layernorm(const float *x, int ldx, int rows, int d, const float *g1, const float *b1, float *y,
                             int ldy, const float *g2, const float *b2, float *y2, hipStream_t s);
 // softmax(q k^T / sqrt(128)) v per (sample, head); qkv rows are [q | k | v] of width 3*1024.
-hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, int Tk, float *out, hipStream_t s, int pairs = 0, int x3 = 0);
+hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, int Tk, float *out, hipStream_t s, int pairs = 0, int x3 = 0,
+                            int *sat = nullptr);
 // (x3: the fp16-kernel modes' form -- every operand as fp16 (hi, lo) pairs on the fp16 matrix cores, fp32-equivalent: attention_x3_kernel)   // pairs: the rows as (hi, lo) fp16 pairs [hi 1024 | lo 1024] instead of fp32
 // MultiHeadAttentionLearnableQuery (layers.py:240-301): softmax(q k^T / sqrt(256)) v per (sample, head), 8 heads x 256.
 // q rows: q + (b * q_bstride + i) * q_ld (q_bstride = 0: the same 21 probe queries for every sample); k / v rows:
 // k + (b * T + j) * kv_ld, j < T.  out [B*Tq][2048].
 hipError_t launch_attention_d256(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T,
-                                 int Tq, float *out, hipStream_t s, int pairs = 0);
+                                 int Tq, float *out, hipStream_t s, int pairs = 0, int *sat = nullptr);
 // y[r][c] = x[r][c] + pe[r % T][c] for c < d, 0 for d <= c < ldy (PositionalEncoding inside every learnable-query block)
 hipError_t launch_add_pe(const float *x, int ldx, int rows, int T, int d, const float *pe, float *y, int ldy, hipStream_t s);
 // split-K GEMM tail: out[r][c] = act(sum_s slab[s][r][c] + bias[c] + res[r'][c]) for c < N (slices summed in index order)
@@ -277,6 +289,7 @@ struct FfBlockParams {
     float *out; int ldo;
     void *out_pairs;                       // optional: the output rows once more as (hi, lo) fp16 pairs [row][hi ldo | lo ldo] (the next
                                            // block's q/k/v projection reads them in the fp16-kernel modes: rows_f32_to_half's arithmetic)
+    int *sat;                              // out_pairs: range word of the caller (note_range), may be null
     int hid;                               // 128 | 256
     unsigned long long *dbg;               // diagnostic builds only: 100 MHz stamps at the phase boundaries of workgroup 0
 };

@@ -98,33 +98,37 @@ hipError_t launch_maxpool3s2_f16(const void *in, void *out, int N, int H, int W,
 
 // ------------------------------------------------------------------ HMV_F32X3: fp32 values as (hi, lo) fp16 pairs
 // A tensor row is [hi plane (C halfs) | lo plane (C halfs)]: hi = fp16(v), lo = fp16(v - hi); hi + lo == v to ~2^-22.
-__device__ __forceinline__ void split_f16(float v, _Float16 &hi, _Float16 &lo) {
+// Returns true where the clamp changed v (|v| > 65504 or NaN): the caller reports it through note_range (kernels.h).
+__device__ __forceinline__ bool split_f16(float v, _Float16 &hi, _Float16 &lo) {
     const float c = fminf(fmaxf(v, -65504.f), 65504.f);
     hi = (_Float16)c;
     lo = (_Float16)(c - (float)hi);
+    return out_of_pair_range(v);
 }
 // frames NCHW fp32 -> per pixel [hi: r g b 0 0 0 0 0 | lo: r g b 0 0 0 0 0] (32 bytes)
-__global__ void nchw_to_nhwc_split_kernel(const float *__restrict__ x, f16x8 *__restrict__ out, int HW, size_t total) {
+__global__ void nchw_to_nhwc_split_kernel(const float *__restrict__ x, f16x8 *__restrict__ out, int HW, size_t total, int *sat) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
         const size_t n = i / HW, pix = i - n * HW;
         const float *src = x + n * 3 * (size_t)HW + pix;
         f16x8 h = {0, 0, 0, 0, 0, 0, 0, 0}, l = {0, 0, 0, 0, 0, 0, 0, 0};
+        bool ov = false;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             _Float16 a, b;
-            split_f16(src[c * (size_t)HW], a, b);
+            ov |= split_f16(src[c * (size_t)HW], a, b);
             h[c] = a; l[c] = b;
         }
+        note_range(sat, ov);
         out[2 * i] = h;
         out[2 * i + 1] = l;
     }
 }
-hipError_t launch_nchw_to_nhwc_split(const float *x, void *out, int N, int H, int W, hipStream_t s) {
+hipError_t launch_nchw_to_nhwc_split(const float *x, void *out, int N, int H, int W, hipStream_t s, int *sat) {
     const size_t total = (size_t)N * H * W;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(nchw_to_nhwc_split_kernel, dim3(grid), dim3(256), 0, s, x, reinterpret_cast<f16x8 *>(out), H * W, total);
+    hipLaunchKernelGGL(nchw_to_nhwc_split_kernel, dim3(grid), dim3(256), 0, s, x, reinterpret_cast<f16x8 *>(out), H * W, total, sat);
     return hipGetLastError();
 }
 // ------------------------------------------------------------------ space-to-depth stem input (ResNet backbones, round 2)
@@ -135,7 +139,7 @@ hipError_t launch_nchw_to_nhwc_split(const float *x, void *out, int N, int H, in
 // Channel order inside an s2d pixel: (dy, dx, c).  MODE 0: fp32 [12]; 1: fp16 [12 + 4 zeros]; 2: split [hi 16 | lo 16].
 // Rows / columns beyond an odd H / W are zeros.
 template <int MODE>
-__device__ __forceinline__ void s2d_store(void *__restrict__ out, size_t q, const float (&v)[12]) {
+__device__ __forceinline__ void s2d_store(void *__restrict__ out, size_t q, const float (&v)[12], int *sat = nullptr) {
     if (MODE == 0) {
         f32x4 *o = reinterpret_cast<f32x4 *>(out) + 3 * q;
 #pragma unroll
@@ -150,18 +154,20 @@ __device__ __forceinline__ void s2d_store(void *__restrict__ out, size_t q, cons
         o[0] = a; o[1] = b;
     } else {
         f16x8 h0 = {0, 0, 0, 0, 0, 0, 0, 0}, h1 = h0, l0 = h0, l1 = h0;
+        bool ov = false;
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
             _Float16 a, b;
-            split_f16(v[j], a, b);
+            ov |= split_f16(v[j], a, b);
             if (j < 8) { h0[j] = a; l0[j] = b; } else { h1[j - 8] = a; l1[j - 8] = b; }
         }
+        note_range(sat, ov);
         f16x8 *o = reinterpret_cast<f16x8 *>(out) + 4 * q;
         o[0] = h0; o[1] = h1; o[2] = l0; o[3] = l1;
     }
 }
 template <int MODE>
-__global__ void nchw_to_s2d_kernel(const float *__restrict__ x, void *__restrict__ out, int H, int W, int Hs, int Ws, size_t total) {
+__global__ void nchw_to_s2d_kernel(const float *__restrict__ x, void *__restrict__ out, int H, int W, int Hs, int Ws, size_t total, int *sat) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
@@ -179,20 +185,20 @@ __global__ void nchw_to_s2d_kernel(const float *__restrict__ x, void *__restrict
 #pragma unroll
                 for (int c = 0; c < 3; ++c) v[(dy * 2 + dx) * 3 + c] = in ? x[((n * 3 + c) * H + yy) * (size_t)W + xx] : 0.f;
             }
-        s2d_store<MODE>(out, i, v);
+        s2d_store<MODE>(out, i, v, sat);
     }
 }
-hipError_t launch_nchw_to_s2d(const float *x, void *out, int N, int H, int W, int mode, hipStream_t s) {
+hipError_t launch_nchw_to_s2d(const float *x, void *out, int N, int H, int W, int mode, hipStream_t s, int *sat) {
     const int Hs = (H + 1) / 2, Ws = (W + 1) / 2;
     const size_t total = (size_t)N * Hs * Ws;
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (mode == 2) hipLaunchKernelGGL(nchw_to_s2d_kernel<2>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total);
-    else if (mode == 1) hipLaunchKernelGGL(nchw_to_s2d_kernel<1>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total);
-    else hipLaunchKernelGGL(nchw_to_s2d_kernel<0>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total);
+    if (mode == 2) hipLaunchKernelGGL(nchw_to_s2d_kernel<2>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total, sat);
+    else if (mode == 1) hipLaunchKernelGGL(nchw_to_s2d_kernel<1>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total, nullptr);
+    else hipLaunchKernelGGL(nchw_to_s2d_kernel<0>, dim3(grid), dim3(256), 0, s, x, out, H, W, Hs, Ws, total, nullptr);
     return hipGetLastError();
 }
 // fp32 rows [rows][C] -> fp16 rows [rows][C] (mode 1) or split rows [rows][hi C | lo C] (mode 2): op-level tests
-__global__ void rows_f32_to_half_kernel(const float *__restrict__ in, _Float16 *__restrict__ out, int C, int mode, size_t total) {
+__global__ void rows_f32_to_half_kernel(const float *__restrict__ in, _Float16 *__restrict__ out, int C, int mode, size_t total, int *sat) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
@@ -200,7 +206,7 @@ __global__ void rows_f32_to_half_kernel(const float *__restrict__ in, _Float16 *
         const int c = (int)(i - r * C);
         if (mode == 2) {
             _Float16 a, b;
-            split_f16(in[i], a, b);
+            note_range(sat, split_f16(in[i], a, b));
             out[r * 2 * C + c] = a;
             out[r * 2 * C + C + c] = b;
         } else {
@@ -208,11 +214,11 @@ __global__ void rows_f32_to_half_kernel(const float *__restrict__ in, _Float16 *
         }
     }
 }
-hipError_t launch_rows_f32_to_half(const float *in, void *out, size_t rows, int C, int mode, hipStream_t s) {
+hipError_t launch_rows_f32_to_half(const float *in, void *out, size_t rows, int C, int mode, hipStream_t s, int *sat) {
     const size_t total = rows * (size_t)C;
     if (!total) return hipSuccess;
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(rows_f32_to_half_kernel, dim3(grid), dim3(256), 0, s, in, reinterpret_cast<_Float16 *>(out), C, mode, total);
+    hipLaunchKernelGGL(rows_f32_to_half_kernel, dim3(grid), dim3(256), 0, s, in, reinterpret_cast<_Float16 *>(out), C, mode, total, sat);
     return hipGetLastError();
 }
 // MaxPool2d(3, 2, 1) on split tensors: the maximum of the reconstructed values, re-split
@@ -532,7 +538,7 @@ hipError_t launch_sample_blend(const float *s4, int lds4, int C, int N, int H, i
 // projection reads in the fp16-kernel modes (rows_f32_to_half_kernel's arithmetic: same bits, one launch less)
 __global__ void tokens_finalize_kernel(float *tokens, int ldt, int d, int fdim, int V, const float *coords,
                                        const float *bbox, const float *intr, int pos_mask, const float *pe,
-                                       float *raw_copy, _Float16 *pairs) {
+                                       float *raw_copy, _Float16 *pairs, int *sat) {
     const int row = blockIdx.x;           // n*21 + j, n = b*V + v
     const int n = row / 21, j = row - n * 21;
     float *t = tokens + (size_t)row * ldt;
@@ -561,7 +567,7 @@ __global__ void tokens_finalize_kernel(float *tokens, int ldt, int d, int fdim, 
         if (pe) { v = v + pe[(size_t)pos * d + c]; t[c] = v; }
         if (pairs) {
             _Float16 a, b;
-            split_f16(v, a, b);
+            note_range(sat, split_f16(v, a, b));
             pairs[(size_t)row * 2 * ldt + c] = a;
             pairs[(size_t)row * 2 * ldt + ldt + c] = b;
         }
@@ -571,9 +577,9 @@ __global__ void tokens_finalize_kernel(float *tokens, int ldt, int d, int fdim, 
 }
 hipError_t launch_tokens_finalize(float *tokens, int ldt, int d, int fdim, int N, int V, const float *coords,
                                   const float *bbox, const float *intr, int pos_mask, const float *pe, float *raw_copy,
-                                  hipStream_t s, void *pairs) {
+                                  hipStream_t s, void *pairs, int *sat) {
     hipLaunchKernelGGL(tokens_finalize_kernel, dim3(N * 21), dim3(128), 0, s, tokens, ldt, d, fdim, V, coords, bbox, intr,
-                       pos_mask, pe, raw_copy, reinterpret_cast<_Float16 *>(pairs));
+                       pos_mask, pe, raw_copy, reinterpret_cast<_Float16 *>(pairs), sat);
     return hipGetLastError();
 }
 
@@ -705,7 +711,8 @@ template <int D, int ATT_WAVES> struct AttShape {
 // k / v to the first key);  out rows [B * Tq][8 * D]
 template <int D, int ATT_WAVES>
 __global__ __launch_bounds__(64 * ATT_WAVES, D == 128 ? HMV_ATT_OCC : 1) void attention_mfma_kernel(const float *__restrict__ q, int q_ld, int q_bstride,
-        const float *__restrict__ k, const float *__restrict__ v, int kv_ld, int T, int Tq, int Tk, int nqb, float *__restrict__ out, int pairs) {
+        const float *__restrict__ k, const float *__restrict__ v, int kv_ld, int T, int Tq, int Tk, int nqb, float *__restrict__ out, int pairs,
+        int *sat) {
     using SH = AttShape<D, ATT_WAVES>;
     constexpr int NC = SH::NC, NU = D / 8, NV = D / 32;   // K vectors per lane, V vectors per lane and quarter chunk
     extern __shared__ __attribute__((aligned(16))) float att_smem[];
@@ -884,12 +891,14 @@ __global__ __launch_bounds__(64 * ATT_WAVES, D == 128 ? HMV_ATT_OCC : 1) void at
                 if (row < Tq) {
                     if (pairs) {   // the rows as (hi, lo) fp16 pairs [hi 8 D | lo 8 D] for a split-pair to_out GEMM (gemm_x3.hip): split_f16's arithmetic
                         f16x4 hi4, lo4;
+                        bool ov = false;
 #pragma unroll
                         for (int e2 = 0; e2 < 4; ++e2) {
                             _Float16 a_, b_;
-                            split_f16(r4[e2], a_, b_);
+                            ov |= split_f16(r4[e2], a_, b_);
                             hi4[e2] = a_; lo4[e2] = b_;
                         }
+                        note_range(sat, ov);
                         _Float16 *pr = reinterpret_cast<_Float16 *>(out) + ((size_t)b * Tq + row) * (16 * D) + h * D + 32 * c + 8 * g + 4 * kh;
                         *reinterpret_cast<f16x4 *>(pr) = hi4;
                         *reinterpret_cast<f16x4 *>(pr + 8 * D) = lo4;
@@ -1116,6 +1125,8 @@ __global__ __launch_bounds__(64 * AX_WAVES, 2) void attention_x3_kernel(const _F
             if (row < Tq) {
                 if (pairs) {
                     f16x4 hi4, lo4;
+                    // (no range report here: a row is a convex combination of value rows that are pairs already, |r4| <= 65504 up to
+                    // rounding -- and a report in this loop changes how the compiler contracts the merge above, i.e. the bits)
                     ax_split4(r4, hi4, lo4);
                     _Float16 *pr = reinterpret_cast<_Float16 *>(out) + ((size_t)b * Tq + row) * (16 * D) + h * D + 32 * c + 8 * g + 4 * kh;
                     *reinterpret_cast<f16x4 *>(pr) = hi4;
@@ -1130,25 +1141,25 @@ __global__ __launch_bounds__(64 * AX_WAVES, 2) void attention_x3_kernel(const _F
 
 template <int D, int W>
 static hipError_t launch_attention_w(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T, int Tq,
-                                     int Tk, float *out, hipStream_t s, int pairs, int nqb) {
+                                     int Tk, float *out, hipStream_t s, int pairs, int nqb, int *sat) {
     const int lds = AttShape<D, W>::LDS_FLOATS * (int)sizeof(float);
     static DeviceOnce once;
     if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, attention_mfma_kernel<D, W>); }); e != hipSuccess) return e;
     hipLaunchKernelGGL((attention_mfma_kernel<D, W>), dim3((unsigned)B * 8 * nqb), dim3(64 * W), lds, s, q, q_ld, q_bstride, k, v, kv_ld, T, Tq,
-                       Tk, nqb, out, pairs);
+                       Tk, nqb, out, pairs, sat);
     return hipGetLastError();
 }
 template <int D>
 static hipError_t launch_attention_any(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T, int Tq,
-                                       int Tk, float *out, hipStream_t s, int pairs = 0) {
+                                       int Tk, float *out, hipStream_t s, int pairs = 0, int *sat = nullptr) {
     if (Tk <= 0 || Tq <= 0 || B <= 0) return hipErrorInvalidValue;
     const int nqb = (Tq + 31) >> 5;
     // (measured in round 4, tools/att_probe.py: TWO waves per workgroup -- six chunks as 3 : 3 instead of 2 : 2 : 1 : 1, four workgroups per CU --
     // take 86.4 us where four take 88.7 at B = 32 x 168 tokens and 22.7 against 18.4 us at B = 1: the launch is bound by its fp32 MFMA time
     // plus the latencies two waves per SIMD cannot hide, not by the split)
-    return launch_attention_w<D, 4>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, Tk, out, s, pairs, nqb);
+    return launch_attention_w<D, 4>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, Tk, out, s, pairs, nqb, sat);
 }
-hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, int Tk, float *out, hipStream_t s, int pairs, int x3) {
+hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, int Tk, float *out, hipStream_t s, int pairs, int x3, int *sat) {
     if (x3) {   // the fp16-kernel modes: qkv holds rows of (hi, lo) fp16 pairs [hi 3072 | lo 3072] (the projection GEMMs' pair epilogue) and both
                 // products run on the fp16 matrix cores (attention_x3_kernel); by the arithmetic mode alone, never by a size
         if (Tk <= 0 || Tq <= 0 || B <= 0) return hipErrorInvalidValue;
@@ -1160,7 +1171,8 @@ hipError_t launch_attention(const float *qkv, int B, int T, int Tq, int koff, in
                            ph + (size_t)koff * 6144 + 1024, ph + (size_t)koff * 6144 + 2048, 6 * 1024, 3 * 1024, T, Tq, Tk, nqb, out, pairs);
         return hipGetLastError();
     }
-    return launch_attention_any<128>(qkv, 3 * 1024, T, qkv + (size_t)koff * 3072 + 1024, qkv + (size_t)koff * 3072 + 2048, 3 * 1024, B, T, Tq, Tk, out, s, pairs);
+    return launch_attention_any<128>(qkv, 3 * 1024, T, qkv + (size_t)koff * 3072 + 1024, qkv + (size_t)koff * 3072 + 2048, 3 * 1024, B, T, Tq, Tk, out, s, pairs,
+                                     sat);
 }
 
 // ------------------------------------------------------------------ learnable-query fusion
@@ -1224,11 +1236,11 @@ __global__ __launch_bounds__(256) void attention_d256_kernel(const float *__rest
     }
 }
 hipError_t launch_attention_d256(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T,
-                                 int Tq, float *out, hipStream_t s, int pairs) {
+                                 int Tq, float *out, hipStream_t s, int pairs, int *sat) {
     if (T <= 0 || Tq <= 0) return hipErrorInvalidValue;
     // QK^T and PV on the fp32 matrix cores like the 128-wide heads (the same kernel template, D = 256); HMV_LQ_SCALAR_ATT=1
     // keeps the wave-per-query-row form below (A/B runs, read per launch)
-    if (pairs || !HMV_DEV_ENV("HMV_LQ_SCALAR_ATT")) return launch_attention_any<256>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, T, out, s, pairs);
+    if (pairs || !HMV_DEV_ENV("HMV_LQ_SCALAR_ATT")) return launch_attention_any<256>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, T, out, s, pairs, sat);
     hipLaunchKernelGGL(attention_d256_kernel, dim3(B * 8), dim3(256), 0, s, q, q_ld, q_bstride, k, v, kv_ld, T, Tq, out);
     return hipGetLastError();
 }

@@ -359,6 +359,22 @@ class HandMvNet(torch.nn.Module):
         for h in self._engines.values():
             _lib.check(_lib.load().hmv_set_hr_fusion(h, mode), h)
 
+    def check_range(self):
+        """Raises FloatingPointError if a forward since the last call clamped a value to the (hi, lo) fp16 pair range (|v| > 65504:
+        float32x3 everywhere, half() in its fusion transformer; include/handmv.h "Range contract").  Synchronises every engine's
+        current stream and clears the report; forward() never checks (that would add a synchronisation to every step)."""
+        lib = _lib.load()
+        names = {0: "float32", 1: "half", 2: "float32x3"}
+        hit = []
+        for (hh, ww, idx, dt), h in self._engines.items():
+            stream = torch.cuda.current_stream(torch.device(f"cuda:{idx}")).cuda_stream
+            sat = ctypes.c_int32(0)
+            _lib.check(lib.hmv_range_status(h, ctypes.byref(sat), ctypes.c_void_p(stream)), h)
+            if sat.value:
+                hit.append(f"{names.get(dt, dt)} engine {hh}x{ww} on cuda:{idx}")
+        if hit:
+            raise FloatingPointError("values outside the fp16 pair range (|v| > 65504) were clamped: " + "; ".join(hit))
+
     def poison_workspace(self, value: int = 0xFF):
         """Test hook: fills the workspace of the engine the last forward ran on with `value` bytes (0xFF = NaN patterns)."""
         hh, ww, idx, _, dt = self._last_key

@@ -39,7 +39,7 @@ extern "C" {
 typedef struct hmv_engine *hmv_handle;
 
 enum { HMV_OK = 0, HMV_ERR_ARG = 1, HMV_ERR_STATE = 2, HMV_ERR_MISSING_TENSOR = 3, HMV_ERR_SHAPE = 4, HMV_ERR_HIP = 5,
-       HMV_ERR_UNSUPPORTED = 6 };
+       HMV_ERR_UNSUPPORTED = 6, HMV_ERR_RANGE = 7 /* a value outside the fp16 range of its mode: see "Range contract" below */ };
 
 /* model_params["backbone"] = "resnet": backbone_type "18" | "34" | "50_paper"   (handmvnet.py:59-68)
  * model_params["backbone"] = "hrnet":  backbone_type "w40" | "w64"            (handmvnet.py:41-57, hrnet.py:430-447) */
@@ -55,6 +55,19 @@ enum { HMV_DECODER_NN = 0, HMV_DECODER_GCN = 1 };
  * evaluated as hi*hi + lo*hi + hi*lo with fp32 accumulation -- three 2.5 PFLOP/s fp16 MFMAs instead of one 157 TFLOP/s fp32
  * MFMA.  Same bytes in HBM as fp32.  Heat-map logits, soft-argmax, tokens, fusion and decoder are plain fp32 as always. */
 enum { HMV_F32 = 0, HMV_F16 = 1, HMV_F32X3 = 2 };
+/* Range contract of the three modes.
+ *   HMV_F32    no range limit beyond fp32's own.
+ *   HMV_F32X3  fp32-equivalent for values v with 2^-3 <= |v| < 65504 (2^-22 relative per operand).  Below 2^-3 lo = fp16(v - hi) is an fp16
+ *              subnormal: a pair then carries an ABSOLUTE error of at most 2^-25 (half of fp16's subnormal step 2^-24), so a dot
+ *              product over weights w has an extra error of at most ~2^-25 * sum|w| (measured on MI355X: the MFMA keeps fp16 subnormals; the
+ *              sweep of tests/test_gpu_range.py holds every result to that floor down to 2^-14).  Weights are shifted out of that region at packing
+ *              (a power of two per layer, undone in the fp32 epilogue), activations are not.  Above 65504 a pair cannot hold the value:
+ *              every pair conversion clamps to +-65504 and reports it (sites whose values are pairs already -- max-pooling, the rows of the
+ *              pair attention -- or are normalised frame pixels are not re-checked) -- a forward sets the handle's range word (hmv_range_status), an
+ *              hmv_op_* entry returns HMV_ERR_RANGE with hmv_last_error(NULL) naming it.  Pairs are also what the q / k / v projections and
+ *              the attention rows of the fusion transformer use in HMV_F16, so the same report covers that mode's tokens.
+ *   HMV_F16    the conv stack behaves like model.half(): values cast round-to-nearest, |v| >= 65520 becomes +-inf (and propagates), no
+ *              report.  hmv_finalize_weights returns HMV_ERR_RANGE, naming the state_dict key, for a folded weight with |w| >= 65520. */
 /* model_params["fusion"] (handmvnet.py:137-149): "cross_attn" = CrossAttentionFusion (fusion.py:7-30, every release config);
  * "cross_attn_learnable_query" = CrossAttentionFusionLearnableQuery (fusion.py:33-49; layers.py:240-301): five blocks of
  * heads 8 x 256, a learnable 21-token probe as the query of the middle block, a positional embedding inside every block,
@@ -90,7 +103,8 @@ int hmv_create(const hmv_config *cfg, hmv_handle *out);
 int hmv_set_tensor(hmv_handle h, const char *key, const float *host, const int64_t *shape, int32_t ndim);
 
 /* After the last hmv_set_tensor: checks every key the forward reads is present with the
- * right shape (HMV_ERR_MISSING_TENSOR / HMV_ERR_SHAPE name the key in hmv_last_error),
+ * right shape (HMV_ERR_MISSING_TENSOR / HMV_ERR_SHAPE name the key in hmv_last_error; HMV_F16: HMV_ERR_RANGE names the key of a
+ * folded weight that fp16 cannot hold),
  * folds BatchNorm into conv scale/bias, repacks to the MFMA-friendly K-major layout and
  * uploads.  Replaces .to(device).eval().freeze() (eval_fps.py:63-65). */
 int hmv_finalize_weights(hmv_handle h);
@@ -172,6 +186,12 @@ int hmv_profile_get_bytes(hmv_handle h, int32_t index, double *bytes);
  * enqueued: the "launches per forward" figure of bench.py (a hipGraph replay enqueues ONE graph of as many nodes). */
 int hmv_launch_count(hmv_handle h);
 
+/* Range report of the (hi, lo) pair modes (HMV_F32X3; the fusion transformer of HMV_F16): synchronises `stream`, sets *saturated to 1 if any
+ * forward of this handle since the last call clamped a value to the pair range (|v| > 65504, see "Range contract"), else 0, and clears it.
+ * Sticky: one call after an evaluation loop covers every forward in it.  The forward itself adds nothing for it (no launch, memset or
+ * synchronisation; the word lives outside the workspace, so hmv_poison_workspace and cached graphs leave it alone). */
+int hmv_range_status(hmv_handle h, int32_t *saturated, void *stream);
+
 /* One NHWC convolution through the engine's conv kernel (op-level parity tests).
  * in [N][H][W][Cin] device; weight OIHW host (Cin must be a multiple of 4);
  * bias host[Cout] or NULL; residual device [N][Ho][Wo][Cout] or NULL; out device NHWC. */
@@ -181,7 +201,8 @@ int hmv_op_conv2d(int32_t device, const float *in, int32_t N, int32_t H, int32_t
 
 /* The same op in any arithmetic mode (dtype = HMV_F32 | HMV_F16 | HMV_F32X3): the fp32 input / residual are converted to the
  * mode's storage format on the device, the layer is packed exactly as hmv_finalize_weights packs it (no BatchNorm), the
- * output is fp32.  Cin must be a multiple of 8 for the fp16-based modes. */
+ * output is fp32.  Cin must be a multiple of 8 for the fp16-based modes.  HMV_F32X3: HMV_ERR_RANGE when a value was clamped to the
+ * pair range (also hmv_op_conv2d_x3, hmv_op_attention_x3); HMV_F16 (also hmv_op_conv2d_f16): out-of-range values become +-inf. */
 int hmv_op_conv2d_ex(int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
                      const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
                      int32_t pad, const float *residual, int32_t relu, float *out, void *stream);
@@ -230,7 +251,8 @@ int hmv_op_conv2d_x3(int32_t device, const float *in, int32_t N, int32_t H, int3
                      int32_t pad, const float *residual, int32_t relu, float *out, int32_t kernel_sel, const char **kernel_name,
                      void *stream);
 
-/* The up-sampling terms of an HRNet fuse layer (hrnet.py:194-212) through hr_fuse.hip alone (op-level parity tests):
+/* The up-sampling terms of an HRNet fuse layer (hrnet.py:194-212) through hr_fuse.hip alone (op-level parity tests; the fp16 instantiation
+ * needs row strides of whole 16-byte units: ldc % 8 == 0, source ld % 8 == 0):
  *   out = act(base + sum_s Upsample_{2^shift_s, nearest}(W_s x_s + b_s)),   terms added in the order given (1 <= nsrc <= 3, 1 <= shift <= 3).
  * base [N][H][W][C] and src[s] [N][H >> shift_s][W >> shift_s][src_c[s]]: device fp32 NHWC; w_host[s] [C][src_c[s]] and bias_host[s] [C] on
  * the host.  f16 != 0: the fp16 instantiation on fp16 copies of base / src, `out` receives fp16 rows; else fp32 rows.  HMV_ERR_ARG for

@@ -20,6 +20,14 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.hmv_version()
 
 
+def test_range_error_code():
+    """HMV_ERR_RANGE (a value outside the fp16 range of its mode, include/handmv.h "Range contract") is 7 in the header and the binding."""
+    header = open(os.path.join(ROOT, "include", "handmv.h")).read()
+    m = re.search(r"\bHMV_ERR_RANGE\s*=\s*(\d+)", header)
+    assert m and int(m.group(1)) == 7
+    assert _lib.HMV_ERR_RANGE == 7
+
+
 def test_product_library_reads_one_environment_variable():
     """Development knobs (A/B switches, probes) exist only in a -DHMV_DEV_KNOBS build: a stray HMV_* variable on a user's box must
     not be able to change kernels, K orders or numerics.  Every "HMV_[A-Z0-9_]+" token in the product library's bytes is either the

@@ -991,6 +991,13 @@ def test_hr_fuse_up_refuses_shapes_without_a_fused_form():
     rc = lib.hmv_op_hr_fuse_up(0, 0, vp(base.data_ptr()), 1, 10, 16, 40, 1, (vp * 1)(vp(x.data_ptr())), (ctypes.c_int32 * 1)(80), (ctypes.c_int32 * 1)(2),
                                (vp * 1)(w.ctypes.data_as(vp)), (vp * 1)(b.ctypes.data_as(vp)), 1, vp(out.data_ptr()), None)
     assert rc != 0 and b"fused form" in lib.hmv_last_error(None)
+    # fp16 rows move in 16-byte units: 36 channels (a multiple of 4, not of 8) have no fp16 form
+    base16, out16 = torch.zeros(1, 8, 16, 36, device=dev), torch.zeros(1, 8, 16, 36, device=dev, dtype=torch.float16)
+    x16 = torch.zeros(1, 4, 8, 16, device=dev)
+    w16, b16 = np.zeros((36, 16), np.float32), np.zeros(36, np.float32)
+    rc = lib.hmv_op_hr_fuse_up(0, 1, vp(base16.data_ptr()), 1, 8, 16, 36, 1, (vp * 1)(vp(x16.data_ptr())), (ctypes.c_int32 * 1)(16),
+                               (ctypes.c_int32 * 1)(1), (vp * 1)(w16.ctypes.data_as(vp)), (vp * 1)(b16.ctypes.data_as(vp)), 1, vp(out16.data_ptr()), None)
+    assert rc != 0 and b"fused form" in lib.hmv_last_error(None)
 
 
 @pytest.mark.parametrize("case,size,nb", [("hr40_v4_128", 128, 2), ("hr40_v4_128", 256, 3), ("hr40_v4_128", 96, 2), ("hr64_tiny", 64, 2), ("hr64_tiny", 160, 1)])

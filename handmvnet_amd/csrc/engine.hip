@@ -1132,6 +1132,46 @@ int hmv_op_conv2d_ex(int32_t device, int32_t dtype, const float *in, int32_t N, 
 // ====================================================================== forward
 namespace {
 
+// second A source of a conv (Bottleneck conv3 + downsample as one GEMM over [t2 | x(strided)])
+struct Dual { const float *in2 = nullptr; int ksplit = 0, H2 = 0, W2 = 0, lda2 = 0, stride2 = 1; };
+
+// One conv / GEMM launch of a packed Layer, said whole: what is not named at the call site has its default here
+struct ConvCall {
+    const Layer *L;
+    const float *in; int N, H, W;             // NHWC [N][H][W][L.Cin]
+    float *out; int ldc, Ho, Wo;
+    int stride = 1, pad_h = 0, pad_w = 0;
+    const float *res = nullptr; int ldr = 0;
+    int activation = ACT_NONE;
+    bool out_f16 = false, fill = false;
+    int up = 0;
+    int rg_out = 0, rg_in = 0;                // residual row remap
+    int scatter = 0, ooy = 0, oox = 0;        // transposed-conv phase placement
+    int ksplit = 1;                           // split-K slices
+    int phases = 0; size_t phase_stride = 0;  // 4: the four transposed-conv phases in one launch (weights phase_stride apart)
+    Dual dual;
+    const Layer *next = nullptr; float *next_out = nullptr;   // chained 1x1 conv + ReLU (conv_stream.hip)
+    int pool_h = 0, pool_w = 0;               // MaxPool2d(3, 2, 1) fused behind it (conv_hs.hip, the fp16 stem): `out` is then the pooled map
+
+    ConvCall(const Layer &L_, const float *in_, int N_, int H_, int W_, float *out_, int ldc_, int Ho_, int Wo_)
+        : L(&L_), in(in_), N(N_), H(H_), W(W_), out(out_), ldc(ldc_), Ho(Ho_), Wo(Wo_) {}
+    ConvCall &s(int v) { stride = v; return *this; }
+    ConvCall &pad(int ph, int pw) { pad_h = ph; pad_w = pw; return *this; }
+    ConvCall &pad(int v) { return pad(v, v); }   // both ways
+    ConvCall &add(const float *r, int ld) { res = r; ldr = ld; return *this; }
+    ConvCall &res_rows(int out_group, int in_group) { rg_out = out_group; rg_in = in_group; return *this; }
+    ConvCall &act(int a) { activation = a; return *this; }
+    ConvCall &f16(bool v) { out_f16 = v; return *this; }
+    ConvCall &filled() { fill = true; return *this; }
+    ConvCall &upsample(int shift) { up = shift; return *this; }
+    ConvCall &phase(int oy, int ox) { scatter = 1; ooy = oy; oox = ox; return *this; }
+    ConvCall &all_phases(int n, size_t wstride) { scatter = 1; phases = n; phase_stride = wstride; return *this; }
+    ConvCall &split_k(int slices) { ksplit = slices; return *this; }
+    ConvCall &second(const float *x, int k0, int Hx, int Wx, int ldx, int sx) { dual = Dual{x, k0, Hx, Wx, ldx, sx}; return *this; }
+    ConvCall &chain(const Layer &nx, float *nx_out) { next = &nx; next_out = nx_out; return *this; }
+    ConvCall &pooled(int ph, int pw) { pool_h = ph; pool_w = pw; return *this; }
+};
+
 struct Runner {
     hmv_engine *h;
     hipStream_t s;
@@ -1174,52 +1214,36 @@ struct Runner {
         if (e != hipSuccess && rc == HMV_OK) rc = h->fail(HMV_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     }
 
-    // One conv / GEMM launch.  in: NHWC [N][H][W][L.Cin] ; returns output dims through Ho/Wo.
-    int ksplit = 1;   // split-K slices of the next conv() call (gemm() below)
-    int phases = 0;   // 4: the next conv() call runs the four transposed-conv phases in one launch (weights phase_stride apart)
-    size_t phase_stride = 0;
-    // second A source of the next conv() call (conv3 + downsample as one GEMM); consumed by that call
-    struct Dual { const float *in2 = nullptr; int ksplit = 0, H2 = 0, W2 = 0, lda2 = 0, stride2 = 1; } dual;
-    const char **kernel_name = nullptr;   // op-level entries: receives the kernel family of the last launch
-    ConvRoute route = conv_rule();        // the kernel families its launches may take (op-level entries: from a kernel_sel); planning asks with it too
-    // chained 1x1 conv of the next conv() call (conv_stream.hip: Bottleneck i's conv3 -> Bottleneck i + 1's conv1 from the output tile
-    // while it is in LDS); consumed by that call.  `probe`: the next conv() call only fills *probe with the launch it WOULD make (also
-    // in the planning run) -- what chain_ok() asks conv_stream_chain_ok about
-    struct Chain { const Layer *L = nullptr; float *out = nullptr; } chain;
-    ConvParams *probe = nullptr;
-    // MaxPool2d(3, 2, 1) fused into the next conv() call (conv_hs.hip, the fp16 stem): `out` is then the pooled map; consumed by that call
-    struct Pool { int h = 0, w = 0; } pool;
-
-    // Bottleneck conv3 + BN3 + downsample conv + BN + ReLU in one launch: out = relu([t2 | x(strided)] . Wcat + b)
-    void conv_dual(const Layer &L, const float *t2, int planes, const float *x, int inpl, int N, int Hx, int Wx, int stride, float *out,
-                   int ldc, int Ho, int Wo, bool out_f16) {
-        dual.in2 = x; dual.ksplit = planes; dual.H2 = Hx; dual.W2 = Wx; dual.lda2 = inpl; dual.stride2 = stride;
-        conv(L, t2, N, Ho, Wo, 1, 0, 0, out, ldc, nullptr, 0, ACT_RELU, Ho, Wo, 0, 0, 0, 0, 0, out_f16);
-        dual = Dual();
+    // every launch that is not a conv: `f` is not evaluated in a planning run or after an error; n = launches behind the one call
+    template <class F> void launch(const char *what, F &&f, int n = 1) {
+        if (!dry && rc == HMV_OK) { check(f(), what); h->launches += n; }
     }
 
-    void conv(const Layer &L, const float *in, int N, int H, int W, int stride, int pad_h, int pad_w, float *out, int ldc,
-              const float *res, int ldr, int act, int Ho, int Wo, int rg_out = 0, int rg_in = 0, int scatter = 0, int ooy = 0,
-              int oox = 0, bool out_f16 = false, int up = 0, bool fill = false) {
-        if ((dry && !probe) || rc != HMV_OK) { probe = nullptr; return; }
+    const char **kernel_name = nullptr;   // op-level entries: receives the kernel family of the last launch
+    ConvRoute route = conv_rule();        // the kernel families its launches may take (op-level entries: from a kernel_sel); planning asks with it too
+
+    // The launch `c` describes, as the launchers see it.  Pure: no launch, no allocation, no state -- the planning run asks the same
+    // questions of it (chains_into(), the pooled stem) as the real one
+    ConvParams params(const ConvCall &c) const {
+        const Layer &L = *c.L;
         ConvParams p{};
-        p.in = in; p.wgt = L.w; p.bias = L.bias; p.res = res; p.out = out;
-        if (ksplit > 1) { p.ksl = ksplit; p.kslice = L.Kpad / ksplit; p.out_slice = (size_t)N * Ho * Wo * ldc; }
-        if (phases > 1) { p.phases = phases; p.phase_stride = phase_stride; }
-        if (dual.in2) {
-            p.in2 = dual.in2; p.ksplit = dual.ksplit; p.H2 = dual.H2; p.W2 = dual.W2; p.lda2 = dual.lda2; p.stride2 = dual.stride2;
-            p.lda = dual.ksplit;   // the first source's pixel stride is its own channel count, not the concatenated one
+        p.in = c.in; p.wgt = L.w; p.bias = L.bias; p.res = c.res; p.out = c.out;
+        if (c.ksplit > 1) { p.ksl = c.ksplit; p.kslice = L.Kpad / c.ksplit; p.out_slice = (size_t)c.N * c.Ho * c.Wo * c.ldc; }
+        if (c.phases > 1) { p.phases = c.phases; p.phase_stride = c.phase_stride; }
+        if (c.dual.in2) {
+            p.in2 = c.dual.in2; p.ksplit = c.dual.ksplit; p.H2 = c.dual.H2; p.W2 = c.dual.W2; p.lda2 = c.dual.lda2; p.stride2 = c.dual.stride2;
+            p.lda = c.dual.ksplit;   // the first source's pixel stride is its own channel count, not the concatenated one
         }
-        p.in_f16 = L.f16; p.out_f16 = out_f16; p.res_f16 = L.f16 && res != nullptr;   // a residual always has the layer's dtype
-        p.N = N; p.H = H; p.W = W; p.Cin = L.Cin;
-        p.Ho = Ho; p.Wo = Wo; p.Cout = L.Cout;
-        p.R = L.R; p.S = L.S; p.stride = stride; p.pad_h = pad_h; p.pad_w = pad_w;
+        p.in_f16 = L.f16; p.out_f16 = c.out_f16; p.res_f16 = L.f16 && c.res != nullptr;   // a residual always has the layer's dtype
+        p.N = c.N; p.H = c.H; p.W = c.W; p.Cin = L.Cin;
+        p.Ho = c.Ho; p.Wo = c.Wo; p.Cout = L.Cout;
+        p.R = L.R; p.S = L.S; p.stride = c.stride; p.pad_h = c.pad_h; p.pad_w = c.pad_w;
         p.K = L.K; p.Kpad = L.Kpad;
-        p.M = N * Ho * Wo;
-        p.ldc = ldc; p.ldr = ldr; p.act = act;
-        p.rg_out = rg_out; p.rg_in = rg_in;
-        p.scatter = scatter; p.osy = scatter ? 2 : 1; p.osx = scatter ? 2 : 1; p.ooy = ooy; p.oox = oox;
-        p.up = up; p.fill = fill ? 1 : 0;
+        p.M = c.N * c.Ho * c.Wo;
+        p.ldc = c.ldc; p.ldr = c.ldr; p.act = c.activation;
+        p.rg_out = c.rg_out; p.rg_in = c.rg_in;
+        p.scatter = c.scatter; p.osy = c.scatter ? 2 : 1; p.osx = c.scatter ? 2 : 1; p.ooy = c.ooy; p.oox = c.oox;
+        p.up = c.up; p.fill = c.fill ? 1 : 0;
         p.tall = L.tall;
         if (L.rd_cout) { p.rd_cout = L.rd_cout; p.pad_w = 0; }   // L.R x L.S is the 3x1 GEMM, the epilogue sums the s groups
         if (L.plane) {   // HMV_F32X3: [hi | lo] rows in, pairs out (unless this layer writes fp32), pairs as residual
@@ -1227,66 +1251,94 @@ struct Runner {
             if (L.x3n) p.x3_plane = L.plane;
             else p.cwrap = 2 * L.plane;
             p.acc_shift = L.acc_shift;
-            if (out_f16) { p.out_split = 1; p.ldc = 2 * ldc; p.sat = h->sat; }
-            if (res) { p.res_split = 1; p.ldr = 2 * ldr; }
+            if (c.out_f16) { p.out_split = 1; p.ldc = 2 * c.ldc; p.sat = h->sat; }
+            if (c.res) { p.res_split = 1; p.ldr = 2 * c.ldr; }
         }
-        const bool pooled = pool.h > 0;
-        if (pooled) { p.pool = 1; p.pool_h = pool.h; p.pool_w = pool.w; pool = Pool(); }
-        if (probe) { *probe = p; probe = nullptr; return; }
-        const Layer *Lx = chain.L;
-        if (Lx) {
-            p.nx_wgt = Lx->w; p.nx_bias = Lx->bias; p.nx_out = chain.out; p.nx_cout = Lx->Cout; p.nx_ldw = Lx->Kpad; p.nx_ldc = Lx->Cout;
+        if (c.pool_h > 0) { p.pool = 1; p.pool_h = c.pool_h; p.pool_w = c.pool_w; }
+        if (const Layer *Lx = c.next) {
+            p.nx_wgt = Lx->w; p.nx_bias = Lx->bias; p.nx_out = c.next_out; p.nx_cout = Lx->Cout; p.nx_ldw = Lx->Kpad; p.nx_ldc = Lx->Cout;
             p.nx_act = ACT_RELU;
-            chain = Chain();
         }
+        return p;
+    }
+
+    // Would the conv3 launch `c3` also compute conv1 + BN + ReLU of the block behind it (conv_stream.hip "chain")?  That block's conv1
+    // reads this launch's output and nothing else, so a workgroup that holds all channels of its pixels computes it from the tile in
+    // LDS (fp16 layer1 at large batches: the 256-channel tensor is read once less per block).  Bit-identical to the two launches, so
+    // the answer may depend on the launch size (conv_stream_chain_ok).  `c3` as it would launch WITHOUT the chain
+    bool chains_into(const ConvCall &c3, const Block *nb) const {
+        if (!h->chain_fuse || !nb || h->cfg.dtype != HMV_F16) return false;
+        const Layer &n1 = nb->c1;
+        const int outc = c3.L->Cout;
+        return n1.f16 && !n1.plane && n1.R == 1 && n1.S == 1 && n1.Cin == outc && n1.K == outc && n1.Kpad == outc && !n1.tall && !n1.rd_cout &&
+               conv_stream_chain_ok(params(c3), n1.Cout, route);
+    }
+
+    // One profiled launch: take a record (its events are made once and reused), stamp e0; the caller fills flops and bytes
+    ProfRec *prof_begin(std::string label) {
+        if (h->prof_used == h->prof.size()) {
+            ProfRec r{};
+            check(hipEventCreate(&r.e0), "hipEventCreate");
+            check(hipEventCreate(&r.e1), "hipEventCreate");
+            h->prof.push_back(r);
+        }
+        ProfRec *pr = &h->prof[h->prof_used++];
+        pr->label = std::move(label);
+        check(hipEventRecord(pr->e0, s), "hipEventRecord");
+        return pr;
+    }
+    void prof_end(ProfRec *pr, const char *kernel) {
+        if (pr) { pr->name = kernel; check(hipEventRecord(pr->e1, s), "hipEventRecord"); }
+    }
+
+    // Algorithmic cost of one conv launch (what bench.py's roofline divides by).  FLOPs: the real (un-padded) reduction length -- the
+    // stem's 4th channel is padding.  Bytes: each input pixel the window touches once, the weights once, residual and output rows once;
+    // a (hi, lo) pair is 4 bytes like fp32; a strided 1x1 conv reads only the pixels it keeps.  (FLOPs count L.Cout, bytes the real
+    // output channels of a row-decomposed layer.)  pooled, dual and phases never meet in one launch; if they did, the first in that
+    // order would decide the bytes
+    static void conv_cost(const ConvCall &c, const ConvParams &p, double &flops, double &bytes) {
+        const Layer &L = *c.L;
+        const double kreal = L.Kreal ? (double)L.Kreal : (double)L.K;   // real channels only (no padding FLOPs)
+        const double cout_real = L.rd_cout ? (double)L.rd_cout : (double)L.Cout;
+        const double eb_in = L.f16 ? (L.plane ? 4.0 : 2.0) : 4.0;
+        const double eb_out = (L.f16 && c.out_f16) ? (L.plane ? 4.0 : 2.0) : 4.0;
+        const double cin_real = L.in_real ? (double)L.in_real : kreal / (double)(L.R * L.S);   // (the row-decomposed form has R x S = 3 x 1 and Kreal = 3 * Cin)
+        const bool pointwise = L.R == 1 && L.S == 1;
+        const double in_px = (pointwise && c.stride > 1) ? (double)p.M : (double)c.N * c.H * c.W;
+        const double in_b = in_px * cin_real * eb_in, w_b = (double)L.Cout * kreal * eb_in, out_b = (double)p.M * cout_real * eb_out;
+        flops = 2.0 * (double)p.M * (double)L.Cout * kreal;
+        if (c.phases > 1) flops *= c.phases;
+        if (p.pool)   // the conv map never reaches HBM: input, weights, the pooled map
+            bytes = in_b + w_b + (double)c.N * p.pool_h * p.pool_w * cout_real * eb_out;
+        else if (c.dual.in2)   // [t2 | x]: t2 at every output pixel, x at the pixels the stride keeps
+            bytes = ((double)p.M * c.dual.ksplit + (double)p.M * (kreal - c.dual.ksplit)) * eb_in + w_b + out_b;
+        else if (c.phases > 1)   // every phase: its own weights and output pixels, the same input
+            bytes = in_b + c.phases * (w_b + out_b);
+        else
+            bytes = in_b + w_b + out_b + (c.res ? (double)p.M * cout_real * eb_in : 0.0);
+        if (const Layer *Lx = c.next) {   // the chained conv: its weights and output rows; its input rows never leave the CU
+            flops += 2.0 * (double)p.M * (double)Lx->Cout * (double)Lx->K;
+            bytes += (double)Lx->Cout * (double)Lx->K * eb_in + (double)p.M * (double)Lx->Cout * eb_out;
+        }
+    }
+
+    // One conv / GEMM launch
+    void conv(const ConvCall &c) {
+        if (dry || rc != HMV_OK) return;
+        const Layer &L = *c.L;
+        const ConvParams p = params(c);
         // split layers walk 3x the reduction on fp16 MFMAs: the tile rules see the real reduction length
-        const ConvTile tile = conv_pick_tile(p.M, p.Cout, L.plane ? p.K / (L.x3n ? 2 : 3) : p.K, L.f16, res != nullptr);
+        const ConvTile tile = conv_pick_tile(p.M, p.Cout, L.plane ? p.K / (L.x3n ? 2 : 3) : p.K, L.f16, c.res != nullptr);
         ProfRec *pr = nullptr;
         if (h->profiling) {
-            if (h->prof_used == h->prof.size()) {
-                ProfRec r{};
-                check(hipEventCreate(&r.e0), "hipEventCreate");
-                check(hipEventCreate(&r.e1), "hipEventCreate");
-                h->prof.push_back(r);
-            }
-            pr = &h->prof[h->prof_used++];
-            pr->label = Lx ? L.label + "+" + Lx->label : (pooled ? L.label + "+maxpool" : L.label);
-            // algorithmic FLOPs: the real (un-padded) reduction length; the stem's 4th channel is padding
-            const double kreal = L.Kreal ? (double)L.Kreal : (double)L.K;   // real channels only (no padding FLOPs)
-            const double cout_real = L.rd_cout ? (double)L.rd_cout : (double)L.Cout;
-            pr->flops = 2.0 * (double)p.M * (double)L.Cout * kreal;
-            // algorithmic bytes: each input pixel the window touches once, the weights once, residual and output rows once.
-            // A (hi, lo) pair is 4 bytes like fp32.  A strided 1x1 conv reads only the pixels it keeps.
-            const double eb_in = L.f16 ? (L.plane ? 4.0 : 2.0) : 4.0;
-            const double eb_out = (L.f16 && out_f16) ? (L.plane ? 4.0 : 2.0) : 4.0;
-            const double cin_real = L.in_real ? (double)L.in_real : kreal / (double)(L.R * L.S);   // (the row-decomposed form has R x S = 3 x 1 and Kreal = 3 * Cin)
-            const bool pointwise = L.R == 1 && L.S == 1;
-            const double in_px = (pointwise && stride > 1) ? (double)p.M : (double)N * H * W;
-            pr->bytes = in_px * cin_real * eb_in + (double)L.Cout * kreal * eb_in + (double)p.M * cout_real * eb_out +
-                        (res ? (double)p.M * cout_real * eb_in : 0.0);
-            if (phases > 1) {   // every phase: its own weights and output pixels, the same input
-                pr->flops *= phases;
-                pr->bytes = in_px * cin_real * eb_in + phases * ((double)L.Cout * kreal * eb_in + (double)p.M * cout_real * eb_out);
-            }
-            if (dual.in2)   // [t2 | x]: t2 at every output pixel, x at the pixels the stride keeps
-                pr->bytes = ((double)p.M * dual.ksplit + (double)p.M * (kreal - dual.ksplit)) * eb_in + (double)L.Cout * kreal * eb_in +
-                            (double)p.M * cout_real * eb_out;
-            if (pooled)   // the conv map never reaches HBM: input, weights, the pooled map
-                pr->bytes = in_px * cin_real * eb_in + (double)L.Cout * kreal * eb_in + (double)N * p.pool_h * p.pool_w * cout_real * eb_out;
-            if (Lx) {   // the chained conv: its weights and output rows; its input rows never leave the CU
-                pr->flops += 2.0 * (double)p.M * (double)Lx->Cout * (double)Lx->K;
-                pr->bytes += (double)Lx->Cout * (double)Lx->K * eb_in + (double)p.M * (double)Lx->Cout * eb_out;
-            }
-            check(hipEventRecord(pr->e0, s), "hipEventRecord");
+            pr = prof_begin(c.next ? L.label + "+" + c.next->label : (p.pool ? L.label + "+maxpool" : L.label));
+            conv_cost(c, p, pr->flops, pr->bytes);
         }
         const char *kname = nullptr;
         check(launch_conv(p, tile, s, &kname, route), L.label.c_str());
         ++h->launches;
         if (kernel_name) *kernel_name = kname;
-        if (pr) {
-            pr->name = kname;
-            check(hipEventRecord(pr->e1, s), "hipEventRecord");
-        }
+        prof_end(pr, kname);
     }
 
     // the up-sampling terms of an HRNet fuse layer in one launch (hr_fuse.hip)
@@ -1294,14 +1346,7 @@ struct Runner {
         if (dry || rc != HMV_OK) return;
         ProfRec *pr = nullptr;
         if (h->profiling) {
-            if (h->prof_used == h->prof.size()) {
-                ProfRec r{};
-                check(hipEventCreate(&r.e0), "hipEventCreate");
-                check(hipEventCreate(&r.e1), "hipEventCreate");
-                h->prof.push_back(r);
-            }
-            pr = &h->prof[h->prof_used++];
-            pr->label = label;
+            pr = prof_begin(label);
             const double eb = p.f16 ? 2.0 : 4.0;
             pr->flops = 0.0;
             pr->bytes = 2.0 * (double)p.N * p.H * p.W * p.C * eb;   // the map once in, once out
@@ -1310,14 +1355,10 @@ struct Runner {
                 pr->flops += 2.0 * (double)p.N * S.H * S.W * S.C * p.C;
                 pr->bytes += (double)p.N * S.H * S.W * S.C * eb + (double)S.C * p.C * 4.0;
             }
-            check(hipEventRecord(pr->e0, s), "hipEventRecord");
         }
         check(launch_hr_fuse_up(p, s), label.c_str());
         ++h->launches;
-        if (pr) {
-            pr->name = p.f16 ? "hr_fuse_up_f16" : "hr_fuse_up_f32";
-            check(hipEventRecord(pr->e1, s), "hipEventRecord");
-        }
+        prof_end(pr, p.f16 ? "hr_fuse_up_f16" : "hr_fuse_up_f32");
     }
 
     static int splitk_slices(const Layer &L, int rows) {
@@ -1325,35 +1366,39 @@ struct Runner {
         return (!no_splitk && !L.f16 && L.R == 1 && L.S == 1 && !L.plane && L.Kpad >= 1024 && L.Kpad % 128 == 0 &&
                 L.Cout <= 4096 /* zero_bias */ && rows > 0) ? 4 : 1;
     }
+    // the S partial products a . W of the K slices, one launch, [S][rows][lds] into `slab`; whoever sums them adds L's bias
+    void conv_slices(const Layer &L, const float *a, int rows, int S, float *slab, int lds) {
+        Layer Ls = L;
+        Ls.bias = h->zero_bias;
+        conv(ConvCall(Ls, a, rows, 1, 1, slab, lds, 1, 1).split_k(S));
+    }
+
+    // y = LayerNorm(...) tail of a split-K GEMM (gemm_ln below)
+    struct LnTail { const float *g1, *b1, *g2, *b2; float *y, *y2; int ldy; };
+
+    // split-K (layers.py:224 to_out: K = 1024, and 2048 in the learnable-query blocks): a long reduction over few token rows
+    // tiles into a few dozen workgroups at a small batch.  K is cut into 4 slices that run as 4x the workgroups of ONE
+    // launch; a reduction kernel adds the partial products in slice order and applies bias / residual / activation -- or, when the
+    // consumer is a LayerNorm (`ln`), slice sum, bias and residual become that kernel's load.
+    // The cut depends on K alone -- never on the batch -- so a sample's result does not depend on what it is batched with
+    // (tests/test_gpu_parity.py::test_full_size_properties).  Same alloc / release sequence in the dry (planning) run.
+    void gemm_splitk(const Layer &L, const float *a, int rows, float *out, int ldc, const float *res, int ldr, int act, int rg_out, int rg_in,
+                     const LnTail *ln) {
+        const int S = splitk_slices(L, rows), lds_ = (L.Cout + 3) / 4 * 4;
+        float *slab = alloc((size_t)S * rows * lds_);
+        conv_slices(L, a, rows, S, slab, lds_);
+        if (ln)
+            launch("splitk_layernorm", [&] { return launch_splitk_layernorm(slab, S, rows, lds_, L.Cout, L.bias, res, ldr, rg_out, rg_in, ln->g1, ln->b1,
+                                                                            ln->y, ln->ldy, ln->g2, ln->b2, ln->y2, s); });
+        else
+            launch("splitk_reduce", [&] { return launch_splitk_reduce(slab, S, rows, lds_, L.Cout, L.bias, res, ldr, rg_out, rg_in, act, out, ldc, s); });
+        release(slab);
+    }
 
     void gemm(const Layer &L, const float *a, int rows, float *out, int ldc, const float *res, int ldr, int act, int rg_out = 0,
               int rg_in = 0) {
-        // split-K (layers.py:224 to_out: K = 1024, and 2048 in the learnable-query blocks): a long reduction over few token rows
-        // tiles into a few dozen workgroups at a small batch.  K is cut into 4 slices that run as 4x the workgroups of ONE
-        // launch; a reduction kernel adds the partial products in slice order and applies bias / residual / activation.
-        // The cut depends on K alone -- never on the batch -- so a sample's result does not depend on what it is batched with
-        // (tests/test_gpu_parity.py::test_full_size_properties).  Same alloc / release sequence in the dry (planning) run.
-        const int S = splitk_slices(L, rows);
-        if (S == 1) {
-            conv(L, a, rows, 1, 1, 1, 0, 0, out, ldc, res, ldr, act, 1, 1, rg_out, rg_in);
-            return;
-        }
-        const int lds_ = (L.Cout + 3) / 4 * 4;
-        float *slab = alloc((size_t)S * rows * lds_);
-        Layer Ls = L;
-        Ls.bias = h->zero_bias;
-        ksplit = S;
-        conv(Ls, a, rows, 1, 1, 1, 0, 0, slab, lds_, nullptr, 0, ACT_NONE, 1, 1);
-        ksplit = 1;
-        if (!dry && rc == HMV_OK) {
-            ++h->launches;
-            if (ln.y)   // the consumer is a LayerNorm (gemm_ln below): slice sum, bias and residual become its load
-                check(launch_splitk_layernorm(slab, S, rows, lds_, L.Cout, L.bias, res, ldr, rg_out, rg_in, ln.g1, ln.b1, ln.y, ln.ldy,
-                                              ln.g2, ln.b2, ln.y2, s), "splitk_layernorm");
-            else
-                check(launch_splitk_reduce(slab, S, rows, lds_, L.Cout, L.bias, res, ldr, rg_out, rg_in, act, out, ldc, s), "splitk_reduce");
-        }
-        release(slab);
+        if (splitk_slices(L, rows) > 1) gemm_splitk(L, a, rows, out, ldc, res, ldr, act, rg_out, rg_in, nullptr);
+        else conv(ConvCall(L, a, rows, 1, 1, out, ldc, 1, 1).add(res, ldr).act(act).res_rows(rg_out, rg_in));
     }
 
     // Everything of a fusion block behind the attention in two launches: the split-K to_out GEMM, then ONE kernel for
@@ -1370,16 +1415,9 @@ struct Runner {
         // out_x3: `att` holds (hi, lo) pairs and to_out runs as ONE split-pair GEMM (gemm_x3.hip) instead of four fp32 split-K slices
         const int S = out_x3 ? 1 : splitk_slices(out, rows), lds_ = (out.Cout + 3) / 4 * 4;
         float *slab = alloc((size_t)S * rows * lds_);
-        if (out_x3) {
-            conv(*out_x3, att, rows, 1, 1, 1, 0, 0, slab, lds_, nullptr, 0, ACT_NONE, 1, 1);   // (its own bias is zero)
-        } else {
-            Layer Ls = out;
-            Ls.bias = h->zero_bias;
-            ksplit = S;
-            conv(Ls, att, rows, 1, 1, 1, 0, 0, slab, lds_, nullptr, 0, ACT_NONE, 1, 1);
-            ksplit = 1;
-        }
-        if (!dry && rc == HMV_OK) {
+        if (out_x3) conv(ConvCall(*out_x3, att, rows, 1, 1, slab, lds_, 1, 1));   // (its own bias is zero)
+        else conv_slices(out, att, rows, S, slab, lds_);
+        launch("ff_block", [&] {
             FfBlockParams p{};
             p.slab = slab; p.S = S; p.slice = (size_t)rows * lds_; p.lds = lds_; p.bias0 = out.bias;
             p.res = res; p.ldr = ldr; p.rg_out = rg_out; p.rg_in = rg_in;
@@ -1403,26 +1441,23 @@ struct Runner {
                 p.dbg = ffdbg;
             }
 #endif
-            check(launch_ff_block(p, s), "ff_block");
-            ++h->launches;
-        }
+            return launch_ff_block(p, s);
+        });
         release(slab);
     }
 
     // y = LayerNorm(a . W + bias + residual) (+ a chained second LayerNorm y2): layers.py:224-229 (to_out, + _q, norm1, then the
     // FeedForward's own LayerNorm).  With split-K the GEMM's reduction kernel IS the LayerNorm kernel (one launch less per block).
-    struct LnTail { const float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; float *y = nullptr, *y2 = nullptr; int ldy = 0; } ln;
     void gemm_ln(const Layer &L, const float *a, int rows, const float *res, int ldr, int rg_out, int rg_in, const float *g1,
                  const float *b1, float *y, int ldy, const float *g2, const float *b2, float *y2) {
         if (splitk_slices(L, rows) > 1) {
-            ln.g1 = g1; ln.b1 = b1; ln.g2 = g2; ln.b2 = b2; ln.y = y; ln.y2 = y2; ln.ldy = ldy;
-            gemm(L, a, rows, nullptr, 0, res, ldr, ACT_NONE, rg_out, rg_in);
-            ln = LnTail();
+            const LnTail ln{g1, b1, g2, b2, y, y2, ldy};
+            gemm_splitk(L, a, rows, nullptr, 0, res, ldr, ACT_NONE, rg_out, rg_in, &ln);
             return;
         }
         float *o = alloc((size_t)rows * ldy);
         gemm(L, a, rows, o, ldy, res, ldr, ACT_NONE, rg_out, rg_in);
-        if (!dry && rc == HMV_OK) { check(launch_layernorm(o, ldy, rows, L.Cout, g1, b1, y, ldy, g2, b2, y2, s), "layernorm"); ++h->launches; }
+        launch("layernorm", [&] { return launch_layernorm(o, ldy, rows, L.Cout, g1, b1, y, ldy, g2, b2, y2, s); });
         release(o);
     }
 };
@@ -1443,7 +1478,15 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     const bool h16 = c.dtype != HMV_F32;      // the conv stack runs on the fp16 kernels ...
     const bool split = c.dtype == HMV_F32X3;  // ... on (hi, lo) pairs: 4 bytes per element like fp32
 #define ACT(n) ((h16 && !split) ? ((size_t)(n) + 1) / 2 : (size_t)(n))
-#define LAUNCH(expr) do { if (!dry && R.rc == HMV_OK) { R.check((expr), #expr); ++h->launches; } } while (0)
+#define LAUNCH(expr) R.launch(#expr, [&] { return (expr); })
+    // conv3 of a Bottleneck (+ residual or second source, + ReLU); where chains_into() says so, the same launch also computes conv1 of the
+    // block behind it, `nb`: returns that conv1's output (allocated behind the block's own output, as the planning run does), else null
+    auto conv3 = [&](ConvCall c3, const Block *nb) -> float * {
+        float *t1 = nullptr;
+        if (R.chains_into(c3, nb)) { t1 = R.alloc(ACT((size_t)c3.N * c3.Ho * c3.Wo * nb->c1.Cout)); c3.chain(nb->c1, t1); }
+        R.conv(c3);
+        return t1;
+    };
 
     // sampled feature levels in the reference's feats[] order (handmvnet.py:165-177), channels-last with row stride ld
     float *lvl[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1460,10 +1503,10 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         else LAUNCH(launch_nchw_to_nhwc4(x, in4, N, H, W, s));
         const int H1 = (H + 2 - 3) / 2 + 1, W1 = (W + 2 - 3) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
         float *c1 = R.alloc(ACT((size_t)N * H1 * W1 * 64));
-        R.conv(hr.conv1, in4, N, H, W, 2, 1, 1, c1, 64, nullptr, 0, ACT_RELU, H1, W1, 0, 0, 0, 0, 0, h16);
+        R.conv(ConvCall(hr.conv1, in4, N, H, W, c1, 64, H1, W1).s(2).pad(1).act(ACT_RELU).f16(h16));
         R.release(in4);
         float *cur = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-        R.conv(hr.conv2, c1, N, H1, W1, 2, 1, 1, cur, 64, nullptr, 0, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
+        R.conv(ConvCall(hr.conv2, c1, N, H1, W1, cur, 64, H2, W2).s(2).pad(1).act(ACT_RELU).f16(h16));
         R.release(c1);
         float *t1_chained = nullptr;
         for (size_t bi = 0; bi < hr.layer1.size(); ++bi) {   // 4 Bottlenecks, planes 64 -> 256 channels
@@ -1472,31 +1515,21 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
             t1_chained = nullptr;
             if (!t1) {
                 t1 = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-                R.conv(b.c1, cur, N, H2, W2, 1, 0, 0, t1, 64, nullptr, 0, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
+                R.conv(ConvCall(b.c1, cur, N, H2, W2, t1, 64, H2, W2).act(ACT_RELU).f16(h16));
             }
             float *t2 = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-            R.conv(b.c2, t1, N, H2, W2, 1, 1, 1, t2, 64, nullptr, 0, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
+            R.conv(ConvCall(b.c2, t1, N, H2, W2, t2, 64, H2, W2).pad(1).act(ACT_RELU).f16(h16));
             R.release(t1);
             const float *res = cur;
             float *dsb = nullptr;
             if (b.has_ds) {
                 dsb = R.alloc(ACT((size_t)N * H2 * W2 * 256));
-                R.conv(b.ds, cur, N, H2, W2, 1, 0, 0, dsb, 256, nullptr, 0, ACT_NONE, H2, W2, 0, 0, 0, 0, 0, h16);
+                R.conv(ConvCall(b.ds, cur, N, H2, W2, dsb, 256, H2, W2).f16(h16));
                 res = dsb;
             }
             float *y = R.alloc(ACT((size_t)N * H2 * W2 * 256));
             const Block *nb = bi + 1 < hr.layer1.size() ? &hr.layer1[bi + 1] : nullptr;
-            bool ch = false;
-            if (h->chain_fuse && nb && h16 && !split && nb->c1.f16 && !nb->c1.plane && nb->c1.R == 1 && nb->c1.S == 1 && nb->c1.Cin == 256 &&
-                nb->c1.K == 256 && nb->c1.Kpad == 256 && !nb->c1.tall && !nb->c1.rd_cout) {
-                ConvParams q{};
-                R.probe = &q;
-                R.conv(b.c3, t2, N, H2, W2, 1, 0, 0, y, 256, res, 256, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
-                ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
-            }
-            if (ch) { t1_chained = R.alloc(ACT((size_t)N * H2 * W2 * 64)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
-            R.conv(b.c3, t2, N, H2, W2, 1, 0, 0, y, 256, res, 256, ACT_RELU, H2, W2, 0, 0, 0, 0, 0, h16);
-            R.chain = Runner::Chain();
+            t1_chained = conv3(ConvCall(b.c3, t2, N, H2, W2, y, 256, H2, W2).add(res, 256).act(ACT_RELU).f16(h16), nb);
             R.release(t2);
             R.release(dsb);
             R.release(cur);
@@ -1514,8 +1547,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                     hs[i] = preh[i]; ws[i] = prew[i];
                     if (!hr.trans[st][i].empty()) {
                         xs[i] = R.alloc(ACT((size_t)N * hs[i] * ws[i] * cp));
-                        R.conv(hr.trans[st][i][0], pre[i], N, preh[i], prew[i], 1, 1, 1, xs[i], cp, nullptr, 0, ACT_RELU, hs[i], ws[i],
-                               0, 0, 0, 0, 0, h16, 0, /*fill=*/true);
+                        R.conv(ConvCall(hr.trans[st][i][0], pre[i], N, preh[i], prew[i], xs[i], cp, hs[i], ws[i]).pad(1).act(ACT_RELU).f16(h16).filled());
                     } else {
                         xs[i] = pre[i];   // x_list.append(y_list[i]): the same tensor
                         moved[i] = true;
@@ -1527,7 +1559,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                     for (const Layer &l : hr.trans[st][i]) {
                         const int ho = (hh_ + 2 - 3) / 2 + 1, wo = (ww_ + 2 - 3) / 2 + 1, cpo = cpad(l.Cout);
                         float *o = R.alloc(ACT((size_t)N * ho * wo * cpo));
-                        R.conv(l, src, N, hh_, ww_, 2, 1, 1, o, cpo, nullptr, 0, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16, 0, true);
+                        R.conv(ConvCall(l, src, N, hh_, ww_, o, cpo, ho, wo).s(2).pad(1).act(ACT_RELU).f16(h16).filled());
                         R.release(tmp);
                         tmp = o; src = o; hh_ = ho; ww_ = wo;
                     }
@@ -1548,11 +1580,9 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                     if (overlap && b == 3) R.s = h->aux;
                     for (int blk = 0; blk < 4; ++blk) {
                         float *t = R.alloc(ACT((size_t)N * hs[b] * ws[b] * cp));
-                        R.conv(M.br[b][blk][0], xs[b], N, hs[b], ws[b], 1, 1, 1, t, cp, nullptr, 0, ACT_RELU, hs[b], ws[b], 0, 0, 0, 0, 0,
-                               h16, 0, true);
+                        R.conv(ConvCall(M.br[b][blk][0], xs[b], N, hs[b], ws[b], t, cp, hs[b], ws[b]).pad(1).act(ACT_RELU).f16(h16).filled());
                         float *y = R.alloc(ACT((size_t)N * hs[b] * ws[b] * cp));
-                        R.conv(M.br[b][blk][1], t, N, hs[b], ws[b], 1, 1, 1, y, cp, xs[b], cp, ACT_RELU, hs[b], ws[b], 0, 0, 0, 0, 0, h16,
-                               0, true);
+                        R.conv(ConvCall(M.br[b][blk][1], t, N, hs[b], ws[b], y, cp, hs[b], ws[b]).pad(1).add(xs[b], cp).act(ACT_RELU).f16(h16).filled());
                         R.release(t);
                         R.release(xs[b]);
                         xs[b] = y;
@@ -1588,8 +1618,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                         const int act = last ? ACT_RELU : ACT_NONE;
                         float *o = R.alloc(ACT((size_t)N * hs[i] * ws[i] * cpi));
                         if (j > i) {
-                            R.conv(M.fuse[i][j][0], xs[j], N, hs[j], ws[j], 1, 0, 0, o, cpi, res, cpi, act, hs[i], ws[i], 0, 0, 0, 0, 0,
-                                   h16, /*up=*/j - i, true);
+                            R.conv(ConvCall(M.fuse[i][j][0], xs[j], N, hs[j], ws[j], o, cpi, hs[i], ws[i]).add(res, cpi).act(act).f16(h16).upsample(j - i).filled());
                         } else {
                             const float *src = xs[j];
                             float *tmp = nullptr;
@@ -1599,11 +1628,11 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                                 const Layer &l = M.fuse[i][j][q];
                                 const int ho = (hh_ + 2 - 3) / 2 + 1, wo = (ww_ + 2 - 3) / 2 + 1;
                                 if (q == nq - 1) {
-                                    R.conv(l, src, N, hh_, ww_, 2, 1, 1, o, cpi, res, cpi, act, ho, wo, 0, 0, 0, 0, 0, h16, 0, true);
+                                    R.conv(ConvCall(l, src, N, hh_, ww_, o, cpi, ho, wo).s(2).pad(1).add(res, cpi).act(act).f16(h16).filled());
                                 } else {
                                     const int cpo = cpad(l.Cout);
                                     float *t = R.alloc(ACT((size_t)N * ho * wo * cpo));
-                                    R.conv(l, src, N, hh_, ww_, 2, 1, 1, t, cpo, nullptr, 0, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16, 0, true);
+                                    R.conv(ConvCall(l, src, N, hh_, ww_, t, cpo, ho, wo).s(2).pad(1).act(ACT_RELU).f16(h16).filled());
                                     R.release(tmp);
                                     tmp = t; src = t;
                                 }
@@ -1642,7 +1671,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         // pose_net = Conv2d(C0, 21, 3, stride 2, padding 1) on the highest-resolution branch (handmvnet.py:51-57, 180)
         hmh = (lvh[0] + 2 - 3) / 2 + 1; hmw = (lvw[0] + 2 - 3) / 2 + 1;
         hm = R.alloc((size_t)N * hmh * hmw * 32);
-        R.conv(h->pose0, lvl[0], N, lvh[0], lvw[0], 2, 1, 1, hm, 32, nullptr, 0, ACT_NONE, hmh, hmw);
+        R.conv(ConvCall(h->pose0, lvl[0], N, lvh[0], lvw[0], hm, 32, hmh, hmw).s(2).pad(1));
     } else {
     // ---- stem: conv1 7x7 s2 + BN + ReLU, maxpool 3x3 s2 (resnet.py:218-221)
     // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
@@ -1654,25 +1683,16 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     int hh = (H1 + 2 - 3) / 2 + 1, ww = (W1 + 2 - 3) / 2 + 1, C = 64;
     // fp16, many frames: conv1 + BN + ReLU + maxpool as ONE launch (conv_hs.hip's pooled epilogue: the 64-channel conv map, 8x the
     // pooled map's bytes, never reaches HBM).  Bit-identical to the two launches, so the choice may depend on the launch size
-    bool stem_pool = false;
-    if (h16 && !split && h->chain_fuse) {
-        ConvParams q{};
-        R.probe = &q;
-        R.pool.h = hh; R.pool.w = ww;
-        R.conv(h->stem, in4, N, Hs, Ws, 1, 2, 2, nullptr, 64, nullptr, 0, ACT_RELU, H1, W1, 0, 0, 0, 0, 0, h16);
-        R.pool = Runner::Pool();
-        stem_pool = q.pool && conv_hs_supported(q, R.route);
-    }
+    auto stem = [&](float *out) { return ConvCall(h->stem, in4, N, Hs, Ws, out, 64, H1, W1).pad(2).act(ACT_RELU).f16(h16); };
+    const bool stem_pool = h16 && !split && h->chain_fuse && conv_hs_supported(R.params(stem(nullptr).pooled(hh, ww)), R.route);
     float *cur;
     if (stem_pool) {
         cur = R.alloc(ACT((size_t)N * hh * ww * 64));
-        R.pool.h = hh; R.pool.w = ww;
-        R.conv(h->stem, in4, N, Hs, Ws, 1, 2, 2, cur, 64, nullptr, 0, ACT_RELU, H1, W1, 0, 0, 0, 0, 0, h16);
-        R.pool = Runner::Pool();
+        R.conv(stem(cur).pooled(hh, ww));
         R.release(in4);
     } else {
         float *c1 = R.alloc(ACT((size_t)N * H1 * W1 * 64));
-        R.conv(h->stem, in4, N, Hs, Ws, 1, 2, 2, c1, 64, nullptr, 0, ACT_RELU, H1, W1, 0, 0, 0, 0, 0, h16);
+        R.conv(stem(c1));
         R.release(in4);
         cur = R.alloc(ACT((size_t)N * hh * ww * 64));
         if (split) LAUNCH(launch_maxpool3s2_split(c1, cur, N, H1, W1, 64, hh, ww, s));
@@ -1698,49 +1718,27 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                 t1_chained = nullptr;
                 if (!t1) {
                     t1 = R.alloc(ACT((size_t)N * hh * ww * planes));
-                    R.conv(b.c1, cur, N, hh, ww, 1, 0, 0, t1, planes, nullptr, 0, ACT_RELU, hh, ww, 0, 0, 0, 0, 0, h16);
+                    R.conv(ConvCall(b.c1, cur, N, hh, ww, t1, planes, hh, ww).act(ACT_RELU).f16(h16));
                 }
                 float *t2 = R.alloc(ACT((size_t)N * ho * wo * planes));
-                R.conv(b.c2, t1, N, hh, ww, b.stride, 1, 1, t2, planes, nullptr, 0, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
+                R.conv(ConvCall(b.c2, t1, N, hh, ww, t2, planes, ho, wo).s(b.stride).pad(1).act(ACT_RELU).f16(h16));
                 R.release(t1);
-                // the block behind this one (of this layer or the first of the next): its conv1 reads this block's output and nothing
-                // else, so a conv3 launch whose workgroup holds all channels of its pixels computes it from the tile in LDS
-                // (conv_stream.hip "chain"; fp16 layer1 at large batches: the 256-channel tensor is read once less per block).
-                // Bit-identical to the two launches, so the choice may depend on the launch size (conv_stream_chain_ok)
+                // the block behind this one (of this layer or the first of the next): its conv1 may ride on this block's conv3 launch
                 const Block *nb = bi + 1 < h->blocks[li].size() ? &h->blocks[li][bi + 1] : (li + 1 < 3 && !h->blocks[li + 1].empty() ? &h->blocks[li + 1][0] : nullptr);
-                const bool nb_ok = h->chain_fuse && nb && h16 && !split && nb->c1.f16 && !nb->c1.plane && nb->c1.R == 1 && nb->c1.S == 1 &&
-                                   nb->c1.Cin == outc && nb->c1.K == outc && nb->c1.Kpad == outc && !nb->c1.tall && !nb->c1.rd_cout;
                 const float *res = cur;
                 float *dsb = nullptr;
                 if (b.fused_ds) {   // conv3 and the downsample branch as one GEMM over [t2 | x]
+                    // out = relu([t2 | x(strided)] . Wcat + b): BN3 and the downsample's BN are in Wcat and b
                     y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    bool ch = false;
-                    if (nb_ok) {
-                        ConvParams q{};
-                        R.probe = &q;
-                        R.conv_dual(b.c3ds, t2, planes, cur, C, N, hh, ww, b.stride, y, outc, ho, wo, h16);
-                        ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
-                    }
-                    if (ch) { t1_chained = R.alloc(ACT((size_t)N * ho * wo * nb->c1.Cout)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
-                    R.conv_dual(b.c3ds, t2, planes, cur, C, N, hh, ww, b.stride, y, outc, ho, wo, h16);
-                    R.chain = Runner::Chain();
+                    t1_chained = conv3(ConvCall(b.c3ds, t2, N, ho, wo, y, outc, ho, wo).second(cur, planes, hh, ww, C, b.stride).act(ACT_RELU).f16(h16), nb);
                 } else {
                     if (b.has_ds) {
                         dsb = R.alloc(ACT((size_t)N * ho * wo * outc));
-                        R.conv(b.ds, cur, N, hh, ww, b.stride, 0, 0, dsb, outc, nullptr, 0, ACT_NONE, ho, wo, 0, 0, 0, 0, 0, h16);
+                        R.conv(ConvCall(b.ds, cur, N, hh, ww, dsb, outc, ho, wo).s(b.stride).f16(h16));
                         res = dsb;
                     }
                     y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    bool ch = false;
-                    if (nb_ok) {
-                        ConvParams q{};
-                        R.probe = &q;
-                        R.conv(b.c3, t2, N, ho, wo, 1, 0, 0, y, outc, res, outc, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
-                        ch = conv_stream_chain_ok(q, nb->c1.Cout, R.route);
-                    }
-                    if (ch) { t1_chained = R.alloc(ACT((size_t)N * ho * wo * nb->c1.Cout)); R.chain.L = &nb->c1; R.chain.out = t1_chained; }
-                    R.conv(b.c3, t2, N, ho, wo, 1, 0, 0, y, outc, res, outc, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
-                    R.chain = Runner::Chain();
+                    t1_chained = conv3(ConvCall(b.c3, t2, N, ho, wo, y, outc, ho, wo).add(res, outc).act(ACT_RELU).f16(h16), nb);
                 }
                 R.release(t2);
                 R.release(dsb);
@@ -1748,16 +1746,16 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
                 const int planes = b.c1.Cout;
                 outc = planes;
                 float *t1 = R.alloc(ACT((size_t)N * ho * wo * planes));
-                R.conv(b.c1, cur, N, hh, ww, b.stride, 1, 1, t1, planes, nullptr, 0, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
+                R.conv(ConvCall(b.c1, cur, N, hh, ww, t1, planes, ho, wo).s(b.stride).pad(1).act(ACT_RELU).f16(h16));
                 const float *res = cur;
                 float *dsb = nullptr;
                 if (b.has_ds) {
                     dsb = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    R.conv(b.ds, cur, N, hh, ww, b.stride, 0, 0, dsb, outc, nullptr, 0, ACT_NONE, ho, wo, 0, 0, 0, 0, 0, h16);
+                    R.conv(ConvCall(b.ds, cur, N, hh, ww, dsb, outc, ho, wo).s(b.stride).f16(h16));
                     res = dsb;
                 }
                 y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                R.conv(b.c2, t1, N, ho, wo, 1, 1, 1, y, outc, res, outc, ACT_RELU, ho, wo, 0, 0, 0, 0, 0, h16);
+                R.conv(ConvCall(b.c2, t1, N, ho, wo, y, outc, ho, wo).pad(1).add(res, outc).act(ACT_RELU).f16(h16));
                 R.release(t1);
                 R.release(dsb);
             }
@@ -1783,28 +1781,24 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     if (h->paper) {
         hmh = fh; hmw = fw;
         float *ph = R.alloc(ACT((size_t)N * fh * fw * 512));
-        R.conv(h->pose0, feat0, N, fh, fw, 1, 0, 0, ph, 512, nullptr, 0, ACT_RELU, fh, fw, 0, 0, 0, 0, 0, h16);
+        R.conv(ConvCall(h->pose0, feat0, N, fh, fw, ph, 512, fh, fw).act(ACT_RELU).f16(h16));
         hm = R.alloc((size_t)N * hmh * hmw * 32);   // heat-map logits are ALWAYS fp32 (x1000 temperature)
-        R.conv(h->pose1, ph, N, fh, fw, 1, 0, 0, hm, 32, nullptr, 0, ACT_NONE, fh, fw);
+        R.conv(ConvCall(h->pose1, ph, N, fh, fw, hm, 32, fh, fw));
         R.release(ph);
     } else {
         hmh = 2 * fh; hmw = 2 * fw;
         float *p0 = R.alloc(ACT((size_t)N * hmh * hmw * 128));
-        if (h->deconv_all.w) {
-            R.phases = 4; R.phase_stride = h->deconv_stride;
-            R.conv(h->deconv_all, feat0, N, fh, fw, 1, 1, 1, p0, 128, nullptr, 0, ACT_RELU, fh, fw, 0, 0, /*scatter=*/1, 0, 0, h16);
-            R.phases = 0;
-        } else {
+        if (h->deconv_all.w)
+            R.conv(ConvCall(h->deconv_all, feat0, N, fh, fw, p0, 128, fh, fw).pad(1).act(ACT_RELU).f16(h16).all_phases(4, h->deconv_stride));
+        else
             for (int a = 0; a < 2; ++a)
                 for (int b = 0; b < 2; ++b)
-                    R.conv(h->deconv[a * 2 + b], feat0, N, fh, fw, 1, 1 - a, 1 - b, p0, 128, nullptr, 0, ACT_RELU, fh, fw, 0, 0,
-                           /*scatter=*/1, a, b, h16);
-        }
+                    R.conv(ConvCall(h->deconv[a * 2 + b], feat0, N, fh, fw, p0, 128, fh, fw).pad(1 - a, 1 - b).act(ACT_RELU).f16(h16).phase(a, b));
         float *p1 = R.alloc(ACT((size_t)N * hmh * hmw * 64));
-        R.conv(h->pose1, p0, N, hmh, hmw, 1, 1, 1, p1, 64, nullptr, 0, ACT_RELU, hmh, hmw, 0, 0, 0, 0, 0, h16);
+        R.conv(ConvCall(h->pose1, p0, N, hmh, hmw, p1, 64, hmh, hmw).pad(1).act(ACT_RELU).f16(h16));
         R.release(p0);
         hm = R.alloc((size_t)N * hmh * hmw * 32);
-        R.conv(h->pose2, p1, N, hmh, hmw, 1, 1, 1, hm, 32, nullptr, 0, ACT_NONE, hmh, hmw);
+        R.conv(ConvCall(h->pose2, p1, N, hmh, hmw, hm, 32, hmh, hmw).pad(1));
         R.release(p1);
     }
     for (int i = 0; i < 3; ++i) {   // feats = [layer3, layer2, layer1]; only the kept levels are non-null
@@ -1859,7 +1853,7 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
             pairs = R.alloc((size_t)rows * ldt);                           // [hi ldt | lo ldt] halfs per row
             LAUNCH(launch_rows_f32_to_half(a, pairs, (size_t)rows, ldt, 2, s, h->sat));
         }
-        R.conv(L, pairs, rows, 1, 1, 1, 0, 0, out, ldc, nullptr, 0, ACT_NONE, 1, 1, 0, 0, 0, 0, 0, pairs_out);
+        R.conv(ConvCall(L, pairs, rows, 1, 1, out, ldc, 1, 1).f16(pairs_out));
         R.release(pairs);
     };
     if (h->lq) {
@@ -1977,16 +1971,15 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
         cheb_fusable(ldt, ldt, h->gcn[0].Kpad, 256, h->gcn[1].Kpad, 64, h->gcn[2].Kpad, 3)) {
         // the three ChebConv layers in two launches (fusion_kernels.hip): layer 1 per (sample, 16 channels), layers 2 + 3 per sample
         float *scr = R.alloc((size_t)jr * 256);
-        if (!dry && R.rc == HMV_OK) {
+        R.launch("cheb_fused", [&] {
             ChebFusedParams p{};
             p.x = X; p.ldx = ldt; p.B = B; p.K = ldt;
             p.w1 = h->gcn[0].w; p.ldw1 = h->gcn[0].Kpad; p.c1 = 256; p.bias1 = h->gcn_bias[0];
             p.w2 = h->gcn[1].w; p.ldw2 = h->gcn[1].Kpad; p.c2 = 64; p.bias2 = h->gcn_bias[1];
             p.w3 = h->gcn[2].w; p.ldw3 = h->gcn[2].Kpad; p.c3 = 3; p.bias3 = h->gcn_bias[2];
             p.tk = h->cheb_t; p.scratch = scr; p.out = joints_cam; p.ldo = 3;
-            R.check(launch_cheb_fused(p, s), "cheb_fused");
-            h->launches += 2;
-        }
+            return launch_cheb_fused(p, s);
+        }, 2);
         R.release(X);
         R.release(scr);
     } else if (c.decoder == HMV_DECODER_GCN) {
@@ -2447,8 +2440,8 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
         Runner Rn{&eng, s, false, HMV_OK, dummy};
         Rn.kernel_name = kernel_name;
         Rn.route = route;
-        Rn.conv(layer, static_cast<const float *>(x), N, H, W, stride, pad, pad, static_cast<float *>(out), Cout, static_cast<const float *>(res),
-                Cout, relu ? ACT_RELU : ACT_NONE, Ho, Wo, 0, 0, 0, 0, 0, out16);
+        Rn.conv(ConvCall(layer, static_cast<const float *>(x), N, H, W, static_cast<float *>(out), Cout, Ho, Wo).s(stride).pad(pad)
+                    .add(static_cast<const float *>(res), Cout).act(relu ? ACT_RELU : ACT_NONE).f16(out16));
         rc = Rn.rc;
         if (rc == HMV_OK) e = hipStreamSynchronize(s);
     }

@@ -567,7 +567,6 @@ __global__ __launch_bounds__(512, 2) void conv_hs_stem_f32(const ConvParams p) {
 // 0: no instantiation; 1: 3x3 pad 1, 64 -> 64 channels; 2: the 4x4 space-to-depth stem, 16 -> 64 channels; 3 / 4: 3x3 pad 1, 40 -> 40 /
 // 80 -> 80 channels in the plain (r, s, c) K order (HRNet-w40's two highest-resolution branches, hrnet.py:96-221; kind 4 on 8 x 16
 // blocks under three waves)
-static bool hs_wave8() { static const bool v = HMV_DEV_ENV("HMV_HS_8WAVE") != nullptr; return v; }   // development knob (A/B runs)
 static int hs_bh(int kind) { return kind == 4 ? 8 : 16; }   // (the size rule counts 16-row blocks for kinds 1 - 3 whatever form runs)
 static int hs_kind(const ConvParams &p) {
     if (p.R == 3 && p.S == 3 && p.pad_h == 1 && p.pad_w == 1 && p.Cin == 64 && p.Cout == 64 && p.Kpad == 576) return 1;
@@ -642,32 +641,21 @@ hipError_t launch_conv_hs(const ConvParams &p, hipStream_t s, const char **name)
     switch (hs_kind(p)) {
         case 1:
             // two FOUR-wave workgroups per CU on 8 x 16 blocks (2 x 2 waves; 24 KB halo images): they drift apart, and one's halo wait
-            // and epilogue run under the other's MFMAs (the pooled stem gained 24 % that way).  HMV_HS_8WAVE=1: the eight-wave 16 x 16 form
+            // and epilogue run under the other's MFMAs (the pooled stem gained 24 % that way; +2-4 % here over the eight-wave 16 x 16 form)
             if (p.res) {
                 if (name) *name = "conv_hs_f16<3x3,64->64,res>";
-                if (hs_wave8()) return launch_hs_one<3, 3, 8, 2, 1, 4, 2, 2, true>(p, s);
                 return launch_hs_one<3, 3, 8, 2, 1, 2, 2, 2, true>(p, s);
             }
             if (name) *name = "conv_hs_f16<3x3,64->64>";
-            if (hs_wave8()) return launch_hs_one<3, 3, 8, 2, 1, 4, 2, 3, false>(p, s);   // no landing zones: three halo images (two in flight)
-            return launch_hs_one<3, 3, 8, 2, 1, 2, 2, 3, false>(p, s);
+            return launch_hs_one<3, 3, 8, 2, 1, 2, 2, 3, false>(p, s);   // no landing zones: three halo images (two in flight)
         case 2:
             // eight waves along the pixels, both 32-channel blocks per wave (128 weight registers): every pixel fragment read from LDS
             // feeds TWO MFMAs.  With one block per wave (4 x 2 waves) a k16 step is one 1 KB LDS read per 32-cycle MFMA on every SIMD --
             // exactly the LDS peak of the CU (128 B / clk), and the kernel ran at 0.34 MFMA-busy
-            {
-                static const bool old_split = HMV_DEV_ENV("HMV_STEM_4x2") != nullptr;   // development knob (A/B runs): the round-3 wave split
-                if (old_split && !p.pool) {
-                    if (name) *name = "conv_hs_f16<4x4,16->64>";
-                    return launch_hs_one<4, 4, 2, 2, 1, 4, 2, 4, false>(p, s);
-                }
-            }
             if (p.pool) {
                 if (name) *name = "conv_hs_f16<4x4,16->64,+maxpool>";
                 // two FOUR-wave workgroups per CU (each wave four pixel rows x 64 channels; 68 KB of LDS each): they drift apart, and one's
-                // epilogue + pooling (vector instructions) runs under the other's MFMAs.  HMV_STEM_POOL8=1: one eight-wave workgroup (A/B runs)
-                static const bool pool8 = HMV_DEV_ENV("HMV_STEM_POOL8") != nullptr;
-                if (pool8) return launch_hs_one<4, 4, 2, 1, 2, 8, 1, 4, false, true>(p, s);
+                // epilogue + pooling (vector instructions) runs under the other's MFMAs (280 -> 213 us against one eight-wave workgroup)
                 return launch_hs_one<4, 4, 2, 2, 2, 4, 1, 3, false, true>(p, s);
             }
             if (name) *name = "conv_hs_f16<4x4,16->64>";
@@ -675,11 +663,9 @@ hipError_t launch_conv_hs(const ConvParams &p, hipStream_t s, const char **name)
         case 3:   // 40-channel pixels: 26 KB halo images (16 KB for the four-wave form's 8 x 16 blocks)
             if (p.res) {
                 if (name) *name = "conv_hs_f16<3x3,40->40,res>";
-                if (hs_wave8()) return launch_hs_one<3, 3, 5, 2, 1, 4, 2, 3, true>(p, s);
                 return launch_hs_one<3, 3, 5, 2, 1, 2, 2, 3, true>(p, s);
             }
             if (name) *name = "conv_hs_f16<3x3,40->40>";
-            if (hs_wave8()) return launch_hs_one<3, 3, 5, 2, 1, 4, 2, 4, false>(p, s);
             return launch_hs_one<3, 3, 5, 2, 1, 2, 2, 4, false>(p, s);
         case 4:   // 80-channel pixels, 96 weight rows on three channel waves (one per SIMD, up to 512 registers each): 8 x 16 blocks, 30 KB halo images
             if (p.res) {

@@ -48,9 +48,6 @@ typedef _Float16 sf16x8 __attribute__((ext_vector_type(8)));
 #define HMV_SGLDS16(gptr, lptr)                                                                             \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                \
                                      (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-#define HMV_SGLDS16_NT(gptr, lptr)   /* aux = 2: non-temporal */                                            \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),                \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 2)
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -88,12 +85,11 @@ constexpr int sched_after_residual(int NP, int PA, int RB, int RS, int OS) {
     return n;
 }
 static_assert(sched_after_piece(4, 3, 1, 8, 0, 8, 0) == 10 && sched_after_piece(4, 3, 1, 8, 0, 8, 1) == 18 && sched_after_piece(4, 3, 1, 8, 0, 8, 2) == 18 &&
-              sched_after_piece(4, 3, 1, 8, 0, 8, 3) == 10 && sched_after_residual(4, 1, 8, 0, 8) == 23, "the K = 256 schedule, counted by hand");
+              sched_after_piece(4, 3, 1, 8, 0, 8, 3) == 10 && sched_after_residual(4, 1, 8, 0, 8) == 23, "the step-0 schedule of four pieces, counted by hand");
 static_assert(sched_after_piece(4, 3, 1, 8, 2, 8, 0) == 2 + 3 + 3 + 8 && sched_after_residual(4, 1, 8, 2, 8) == 8 + 4 * 3, "the spread K = 256 schedule");
 
 // TM x TN 32x32 blocks per wave, MW x NW waves (pixels x channels), NP 64-channel pieces of reduction, NSLOT ring slots.
-// SPREAD: the next tile's residual DMAs go out RB / NP per piece step instead of all at step 0 (a smoother request stream);
-// NT: 0 default cache policy, 1 residual rows non-temporal (read once), 2 pixel pieces too
+// SPREAD: the next tile's residual DMAs go out RB / NP per piece step instead of all at step 0 (a smoother request stream)
 // DUAL: the reduction is the concatenation [first source | second source] (conv3 + downsample of a layer's first Bottleneck as one
 // GEMM, ConvParams::in2): pieces past ksplit come from the second tensor at pixel (ho * stride2, wo * stride2)
 // N2 > 0 ("chain"): the launch also computes a FOLLOWING 1x1 conv with N2 output channels over its own output pixels (Bottleneck i's
@@ -104,7 +100,7 @@ static_assert(sched_after_piece(4, 3, 1, 8, 2, 8, 0) == 2 + 3 + 3 + 8 && sched_a
 // holds in registers for the launch (BN / 4 VGPRs) and stores its [32 pixels][32 channels] blocks.  Operand roles, bias-as-initial-
 // accumulator, k16 order and epilogue arithmetic are those of the kernel that would have read the tensor back from HBM, so the
 // chained result is BIT-IDENTICAL to the two launches it replaces; its stores join the epilogue slot of the static schedule.
-template <int TM, int TN, int MW, int NW, int NP, int NSLOT, bool HAS_RES, bool SPREAD = false, int NT_ = 0, bool DUAL = false, int N2 = 0>
+template <int TM, int TN, int MW, int NW, int NP, int NSLOT, bool HAS_RES, bool SPREAD = false, bool DUAL = false, int N2 = 0>
 __global__ __launch_bounds__(64 * MW *NW, (MW * NW) / 4) void conv_stream_f16(const ConvParams p) {
     constexpr int NWV = MW * NW, NT = 64 * NWV;
     constexpr int BM = 32 * TM * MW, BN = 32 * TN * NW;
@@ -199,8 +195,7 @@ __global__ __launch_bounds__(64 * MW *NW, (MW * NW) / 4) void conv_stream_f16(co
                 src = Ain + (size_t)m * p.lda + jj * 64 + 8 * kqs;
             }
             asm volatile("" : "+v"(src));   // ONE DMA instruction per schedule entry: keep the select out of the control flow
-            if constexpr (NT_ >= 2) HMV_SGLDS16_NT(src, sA + ((slot * BM + i * 64 + wave * 8) * 64));
-            else HMV_SGLDS16(src, sA + ((slot * BM + i * 64 + wave * 8) * 64));
+            HMV_SGLDS16(src, sA + ((slot * BM + i * 64 + wave * 8) * 64));
         }
     };
     // issue the residual DMAs of tile tt: every lane fetches ITS OWN 8 channels of its own pixel, lane-linear landing zone
@@ -217,8 +212,7 @@ __global__ __launch_bounds__(64 * MW *NW, (MW * NW) / 4) void conv_stream_f16(co
                 const bool ok = tt >= 0 && tt < ntl && m < p.M;
                 const _Float16 *src = ok ? Rin + (size_t)m * p.ldr + n0 + 32 * b + 16 * j + 8 * kh : zero16;
                 asm volatile("" : "+v"(src));
-                if constexpr (NT_ >= 1) HMV_SGLDS16_NT(src, z + idx * 1024);
-                else HMV_SGLDS16(src, z + idx * 1024);
+                HMV_SGLDS16(src, z + idx * 1024);
             }
         }
     };
@@ -585,13 +579,13 @@ __global__ __launch_bounds__(64 * MW *NW, 2) void conv_stream_f32(const ConvPara
 }
 
 // ====================================================================== host side
-template <int TM, int TN, int MW, int NW, int NP, int NSLOT, bool HAS_RES, bool SPREAD = false, int NT_ = 0, bool DUAL = false, int N2 = 0>
+template <int TM, int TN, int MW, int NW, int NP, int NSLOT, bool HAS_RES, bool SPREAD = false, bool DUAL = false, int N2 = 0>
 static hipError_t launch_stream_one(ConvParams p, hipStream_t s) {
     constexpr int BM = 32 * TM * MW, BN = 32 * TN * NW, NWV = MW * NW;
     // chain without landing zones: the output tile's LDS image has its own BM x BN x 2 bytes behind the ring
     constexpr size_t lds = (size_t)NSLOT * BM * 128 + (HAS_RES ? (size_t)2 * NWV * TM * TN * 2 * 1024 : (N2 ? (size_t)BM * BN * 2 : 0));
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = conv_stream_f16<TM, TN, MW, NW, NP, NSLOT, HAS_RES, SPREAD, NT_, DUAL, N2>;
+    auto kern = conv_stream_f16<TM, TN, MW, NW, NP, NSLOT, HAS_RES, SPREAD, DUAL, N2>;
     if (N2 && (p.Cout != BN || p.nx_cout != N2 || !p.nx_wgt || !p.nx_bias || !p.nx_out)) return hipErrorInvalidValue;
     static DeviceOnce once;
     if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, kern); }); e != hipSuccess) return e;
@@ -711,45 +705,29 @@ hipError_t launch_conv_stream(const ConvParams &p, hipStream_t s, const char **n
         if (name) *name = "conv_stream_f32<64x256,k64,res>";
         return launch_stream32<2, 1, 1, 8, 2, 4, true>(p, s);
     }
-    // development knob (A/B runs): HMV_STREAM_VARIANT = 0 residual DMAs at step 0, 1 spread over the piece steps, 2 / 3 the same with
-    // non-temporal residual loads, 4 non-temporal pixel pieces too.  Measured (profiles/r03_probe_stream_variants.txt): spreading
-    // gains 3-4 % at K = 256 (four piece steps) and loses 4 % at K = 128; non-temporal loads lose 15-25 % everywhere (the next
-    // launch finds less of its input in the Infinity Cache).  Default: spread at K = 256 only.
-    static const int knob = HMV_DEV_INT("HMV_STREAM_VARIANT", 100);
-    const int variant = knob < 0 ? 100 : knob;
-#define HMV_STREAM_VARIANTS(...)                                                                            \
-    switch (variant) {                                                                                      \
-        case 1: return launch_stream_one<__VA_ARGS__, true, true, 0>(p, s);                                 \
-        case 2: return launch_stream_one<__VA_ARGS__, true, false, 1>(p, s);                                \
-        case 3: return launch_stream_one<__VA_ARGS__, true, true, 1>(p, s);                                 \
-        case 4: return launch_stream_one<__VA_ARGS__, true, true, 2>(p, s);                                 \
-        case 100: if (p.Kpad == 256) return launch_stream_one<__VA_ARGS__, true, true, 0>(p, s);            \
-                  return launch_stream_one<__VA_ARGS__, true, false, 0>(p, s);                              \
-        default: return launch_stream_one<__VA_ARGS__, true, false, 0>(p, s);                               \
-    }
     if (p.nx_wgt) {   // chained launches (conv_stream_chain_ok): pixel ring of four pieces + the output tile's image
         if (p.nx_ldw < p.Cout || (p.nx_ldw & 7) || (p.nx_ldc & 7) || (p.nx_act != ACT_NONE && p.nx_act != ACT_RELU) || p.acc_shift) return hipErrorInvalidValue;
         if (p.in2 && p.Kpad == 128 && p.nx_cout == 64) {
             if (name) *name = "conv_stream_f16<128x256,k128,dual,+1x1:64>";
-            return launch_stream_one<2, 2, 2, 4, 2, 4, false, false, 0, true, 64>(p, s);
+            return launch_stream_one<2, 2, 2, 4, 2, 4, false, false, true, 64>(p, s);
         }
         if (p.res && p.Kpad == 64 && p.nx_cout == 64) {
             if (name) *name = "conv_stream_f16<128x256,k64,res,+1x1:64>";
-            return launch_stream_one<2, 2, 2, 4, 1, 2, true, false, 0, false, 64>(p, s);
+            return launch_stream_one<2, 2, 2, 4, 1, 2, true, false, false, 64>(p, s);
         }
         if (p.res && p.Kpad == 64 && p.nx_cout == 128) {
             if (name) *name = "conv_stream_f16<128x256,k64,res,+1x1:128>";
-            return launch_stream_one<2, 2, 2, 4, 1, 2, true, false, 0, false, 128>(p, s);
+            return launch_stream_one<2, 2, 2, 4, 1, 2, true, false, false, 128>(p, s);
         }
         return hipErrorInvalidValue;
     }
     if (p.in2) {
         if (p.Kpad == 128) {
             if (name) *name = "conv_stream_f16<128x256,k128,dual>";
-            return launch_stream_one<2, 2, 2, 4, 2, 8, false, false, 0, true>(p, s);
+            return launch_stream_one<2, 2, 2, 4, 2, 8, false, false, true>(p, s);
         }
         if (name) *name = "conv_stream_f16<64x256,k384,dual>";
-        return launch_stream_one<2, 1, 1, 8, 6, 8, false, false, 0, true>(p, s);
+        return launch_stream_one<2, 1, 1, 8, 6, 8, false, false, true>(p, s);
     }
     if (!p.res) {   // the squeezing 1x1 convs: no landing zones, the whole LDS is the pixel ring (128 KB, seven pieces ahead)
         if (p.Kpad == 256 && p.Cout == 64) {
@@ -769,17 +747,19 @@ hipError_t launch_conv_stream(const ConvParams &p, hipStream_t s, const char **n
     }
     if (p.Kpad == 256) {
         if (name) *name = "conv_stream_f16<64x512,k256,res>";
-        HMV_STREAM_VARIANTS(2, 2, 1, 8, 4, 4)
+        // the residual DMAs spread over the piece steps: measured (profiles/r03_probe_stream_variants.txt) 3-4 % faster at K = 256 (four
+        // piece steps), 4 % slower at K = 128; non-temporal residual / pixel loads lost 15-25 % everywhere (the next launch finds less of
+        // its input in the Infinity Cache)
+        return launch_stream_one<2, 2, 1, 8, 4, 4, true, true>(p, s);
     }
     if (p.Kpad == 128) {
         if (name) *name = "conv_stream_f16<64x512,k128,res>";
-        HMV_STREAM_VARIANTS(2, 2, 1, 8, 2, 4)
+        return launch_stream_one<2, 2, 1, 8, 2, 4, true>(p, s);
     }
     if (p.Kpad == 64) {
         if (name) *name = "conv_stream_f16<128x256,k64,res>";
-        HMV_STREAM_VARIANTS(2, 2, 2, 4, 1, 2)
+        return launch_stream_one<2, 2, 2, 4, 1, 2, true>(p, s);
     }
-#undef HMV_STREAM_VARIANTS
     return hipErrorInvalidValue;
 }
 

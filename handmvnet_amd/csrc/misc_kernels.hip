@@ -445,8 +445,7 @@ __global__ __launch_bounds__(256) void soft_argmax_frame_kernel(const float *__r
 }
 hipError_t launch_soft_argmax(const float *hm, int ld, int N, int h, int w, float *coords, float *crop_img,
                               float image_size, float heatmap_size, float *hm_nchw, hipStream_t s) {
-    static const bool no_frame = HMV_DEV_ENV("HMV_SOFTARGMAX_WAVE") != nullptr;   // development knob (A/B runs)
-    if (!no_frame && ld == 32 && h * w <= 1024) {
+    if (ld == 32 && h * w <= 1024) {
         hipLaunchKernelGGL(soft_argmax_frame_kernel, dim3(N), dim3(256), 0, s, hm, h, w, coords, crop_img, image_size, heatmap_size, hm_nchw);
         return hipGetLastError();
     }
@@ -1195,54 +1194,12 @@ hipError_t launch_add_pe(const float *x, int ldx, int rows, int T, int d, const 
     return hipGetLastError();
 }
 
-// Attention with 256-wide heads (layers.py:241, 284-291): the round-2 kernel, kept as the A/B reference of the MFMA one.  The
-// plain wave-per-query-row form: a lane owns 4 of the 256 head dimensions (one 16-byte vector), a score is a wave
-// reduction, softmax runs online (running max / sum are wave-uniform), K and V rows stream from L2 as 1 KiB wave loads.
-// Four query rows share each K / V row load.
-constexpr int LQ_QB = 4;
-__global__ __launch_bounds__(256) void attention_d256_kernel(const float *__restrict__ q, int q_ld, int q_bstride,
-                                                             const float *__restrict__ k, const float *__restrict__ v, int kv_ld, int T,
-                                                             int Tq, float *__restrict__ out) {
-    const int b = blockIdx.x >> 3, h = blockIdx.x & 7;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float scale = 0.0625f;   // 256 ** -0.5
-    const float *kb = k + (size_t)b * T * kv_ld + h * 256 + 4 * lane, *vb = v + (size_t)b * T * kv_ld + h * 256 + 4 * lane;
-    for (int i0 = wave * LQ_QB; i0 < Tq; i0 += 4 * LQ_QB) {
-        f32x4 qv[LQ_QB], o[LQ_QB];
-        float m[LQ_QB], l[LQ_QB];
-#pragma unroll
-        for (int r = 0; r < LQ_QB; ++r) {
-            const int i = i0 + r < Tq ? i0 + r : Tq - 1;   // rows past the end repeat the last one and are not stored
-            qv[r] = *reinterpret_cast<const f32x4 *>(q + ((size_t)b * q_bstride + i) * q_ld + h * 256 + 4 * lane);
-            o[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-            m[r] = -INFINITY;
-            l[r] = 0.f;
-        }
-        for (int j = 0; j < T; ++j) {
-            const f32x4 kv = *reinterpret_cast<const f32x4 *>(kb + (size_t)j * kv_ld);
-            const f32x4 vv = *reinterpret_cast<const f32x4 *>(vb + (size_t)j * kv_ld);
-#pragma unroll
-            for (int r = 0; r < LQ_QB; ++r) {
-                const float sc = wave_sum(qv[r].x * kv.x + qv[r].y * kv.y + qv[r].z * kv.z + qv[r].w * kv.w) * scale;
-                const float mn = fmaxf(m[r], sc), alpha = expf(m[r] - mn), pj = expf(sc - mn);   // exp(-inf) = 0 on the first key
-                l[r] = l[r] * alpha + pj;
-                o[r] = o[r] * alpha + vv * pj;
-                m[r] = mn;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < LQ_QB; ++r)
-            if (i0 + r < Tq) *reinterpret_cast<f32x4 *>(out + ((size_t)b * Tq + i0 + r) * 2048 + h * 256 + 4 * lane) = o[r] * (1.f / l[r]);
-    }
-}
+// Attention with 256-wide heads (layers.py:241, 284-291): QK^T and PV on the fp32 matrix cores like the 128-wide heads (the same
+// kernel template, D = 256)
 hipError_t launch_attention_d256(const float *q, int q_ld, int q_bstride, const float *k, const float *v, int kv_ld, int B, int T,
                                  int Tq, float *out, hipStream_t s, int pairs, int *sat) {
     if (T <= 0 || Tq <= 0) return hipErrorInvalidValue;
-    // QK^T and PV on the fp32 matrix cores like the 128-wide heads (the same kernel template, D = 256); HMV_LQ_SCALAR_ATT=1
-    // keeps the wave-per-query-row form below (A/B runs, read per launch)
-    if (pairs || !HMV_DEV_ENV("HMV_LQ_SCALAR_ATT")) return launch_attention_any<256>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, T, out, s, pairs, sat);
-    hipLaunchKernelGGL(attention_d256_kernel, dim3(B * 8), dim3(256), 0, s, q, q_ld, q_bstride, k, v, kv_ld, T, Tq, out);
-    return hipGetLastError();
+    return launch_attention_any<256>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, T, out, s, pairs, sat);
 }
 
 // ------------------------------------------------------------------ split-K reduction

@@ -274,14 +274,15 @@ int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, 
 
 /* The attention of the learnable-query fusion (MultiHeadAttentionLearnableQuery, layers.py:284-291; 8 heads x 256) through the
  * engine's kernel: q rows at q + (b * q_bstride + i) * q_ld (q_bstride = 0: the same probe queries for every sample), k / v rows
- * at k + (b * T + j) * kv_ld, j < T; softmax(q k^T / 16) v per (sample, head); out device [B][Tq][2048].  HMV_LQ_SCALAR_ATT=1 in
- * the environment selects the non-MFMA kernel (A/B). */
+ * at k + (b * T + j) * kv_ld, j < T; softmax(q k^T / 16) v per (sample, head); out device [B][Tq][2048].  QK^T and PV run
+ * on the fp32 matrix cores (the kernel template of the 128-wide heads at D = 256). */
 int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_bstride, const float *k, const float *v, int32_t kv_ld,
                         int32_t B, int32_t T, int32_t Tq, float *out, void *stream);
 
 /* Diagnostic micro-benchmark: average milliseconds of `iters` launches of one NHWC conv shape on
  * pseudo-random data.  tile: -1 = the engine's own choice, else 0..7 = 128x32, 128x64, 128x128, 256x128,
- * 128x256, 256x256, 128x128 (k-step 16), 128x256 (k-step 16) (BM x BN).  HMV_BENCH_CLOCK=1 adds in-kernel clock stamps (stderr). */
+ * 128x256, 256x256, 128x128 (k-step 16), 128x256 (k-step 16) (BM x BN); a value without an instantiation returns an error.
+ * HMV_BENCH_CLOCK=1 adds in-kernel clock stamps (stderr). */
 int hmv_bench_conv(int32_t device, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t R, int32_t S,
                    int32_t stride, int32_t pad, int32_t with_residual, int32_t tile, int32_t iters, float *avg_ms);
 

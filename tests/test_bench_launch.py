@@ -107,6 +107,12 @@ def test_pmc_summary_names_the_round3_kernels_like_the_engine_does():
     assert ps.family("void hmv::conv_stream_f16<2, 2, 2, 4, 2, 4, false, false, 0, true, 64>(hmv::ConvParams)") == "conv_stream_f16<128x256,k128,dual,+1x1:64>"
     assert ps.family("void hmv::conv_stream_f16<2, 2, 2, 4, 1, 2, true, false, 0, false, 128>(hmv::ConvParams)") == "conv_stream_f16<128x256,k64,res,+1x1:128>"
     assert ps.family("void hmv::conv_stream_f16<1, 2, 8, 1, 1, 4, false, false, 0, false, 0>(hmv::ConvParams)") == "conv_stream_f16<256x64,k64>"
+    # ... as they are named now (no cache-policy argument)
+    assert ps.family("void hmv::conv_stream_f16<2, 2, 1, 8, 4, 4, true, true, false, 0>(hmv::ConvParams)") == "conv_stream_f16<64x512,k256,res>"
+    assert ps.family("void hmv::conv_stream_f16<2, 2, 2, 4, 2, 8, false, false, true, 0>(hmv::ConvParams)") == "conv_stream_f16<128x256,k128,dual>"
+    assert ps.family("void hmv::conv_stream_f16<2, 2, 2, 4, 2, 4, false, false, true, 64>(hmv::ConvParams)") == "conv_stream_f16<128x256,k128,dual,+1x1:64>"
+    assert ps.family("void hmv::conv_stream_f16<2, 2, 2, 4, 1, 2, true, false, false, 128>(hmv::ConvParams)") == "conv_stream_f16<128x256,k64,res,+1x1:128>"
+    assert ps.family("void hmv::conv_stream_f16<1, 2, 8, 1, 1, 4, false, false, false, 0>(hmv::ConvParams)") == "conv_stream_f16<256x64,k64>"
     assert ps.family("void hmv::conv_hs_f16<4, 4, 2, 1, 2, 8, 1, 4, false, true>(hmv::ConvParams)") == "conv_hs_f16<4x4,16->64,+maxpool>"
     assert ps.family("void hmv::conv_hs_f16<4, 4, 2, 1, 2, 8, 1, 4, false, false>(hmv::ConvParams)") == "conv_hs_f16<4x4,16->64>"
     assert ps.family("void hmv::conv_hs_f16<3, 3, 8, 2, 1, 4, 2, 2, true, false>(hmv::ConvParams)") == "conv_hs_f16<3x3,64->64,res>"

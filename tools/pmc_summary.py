@@ -39,14 +39,16 @@ def family(name: str) -> str:
         k16 = ",k16" if (m.group(4) == "32" and not c32) else ""
         return f"conv_igemm_f16<{m.group(1)}x{m.group(2)}{k16}," + {"0": "taps", "1": "1x1", "2": "dense", "3": "halo"}[m.group(3)] + \
             (",rowsum" if m.group(5) == "1" else "") + (",c32" if c32 else "") + ">"
-    # round 3: conv_stream_f16<TM, TN, MW, NW, NP, NSLOT, HAS_RES, SPREAD, NT, DUAL, N2> and conv_gemm8_f16<DUAL>
+    # round 3: conv_stream_f16<TM, TN, MW, NW, NP, NSLOT, HAS_RES, SPREAD, DUAL, N2> and conv_gemm8_f16<DUAL>
     m = re.match(r"(?:void )?(?:hmv::)?conv_stream_f16<(\d+), (\d+), (\d+), (\d+), (\d+), \d+, (true|false)", name)
     if m:
         tm, tn, mw, nw, np_ = (int(m.group(i)) for i in range(1, 6))
         targs = name[name.index("<") + 1:name.index(">")].split(", ")
-        tail = ",res" if m.group(6) == "true" else (",dual" if len(targs) >= 10 and targs[9] == "true" else "")
-        if len(targs) >= 11 and targs[10] != "0":   # N2: the chained 1x1 conv (conv3 -> the next Bottleneck's conv1)
-            tail += f",+1x1:{targs[10]}"
+        if len(targs) >= 9 and targs[8].isdigit():   # recorded profiles: the former cache-policy argument (an int) in front of DUAL
+            del targs[8]
+        tail = ",res" if m.group(6) == "true" else (",dual" if len(targs) >= 9 and targs[8] == "true" else "")
+        if len(targs) >= 10 and targs[9] != "0":   # N2: the chained 1x1 conv (conv3 -> the next Bottleneck's conv1)
+            tail += f",+1x1:{targs[9]}"
         return f"conv_stream_f16<{32 * tm * mw}x{32 * tn * nw},k{64 * np_}" + tail + ">"
     # conv_stream_f32<TM, TN, MW, NW, NP, NSLOT, HAS_RES, DUAL, HALF>: 32-channel pieces
     m = re.match(r"(?:void )?(?:hmv::)?conv_stream_f32<(\d+), (\d+), (\d+), (\d+), (\d+), \d+, (true|false)(?:, (true|false))?(?:, (?:true|false))?>", name)

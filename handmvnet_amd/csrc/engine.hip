@@ -2383,7 +2383,7 @@ int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_
 static int op_conv(const char *who, int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
                    const float *w_oihw, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad,
                    const float *residual, int32_t relu, void *out, bool out16, const ConvRoute &route, const char **kernel_name,
-                   void *stream, bool tall = false, bool rd = false) {
+                   void *stream, bool tall = false, bool rd = false, int Ho_cut = 0, int Wo_cut = 0) {
     if (tall && (residual || !out16 || !conv_ht_shape_ok(R, S, stride, pad, Cin, Cout, H, W))) {
         g_create_err = std::string(who) + ": the tall-tile kernel takes 3x3 stride-1 pad-1 convs without residual, Cin % 32 == 0 (>= 64), Cout % 128 == 0, H % 16 == 0, W % 32 == 0";
         return HMV_ERR_ARG;
@@ -2419,7 +2419,9 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
     L.conv(layer, "op", "w", bias_host && !rd ? "b" : "", rd ? "bn" : "", Cout, Cin, R, S, 0, half, rd, nullptr, tall);
     int rc = L.rc;
     if (rc == HMV_OK && rd && !layer.rd_cout) { eng.err = "the layer was not packed row-decomposed"; rc = HMV_ERR_ARG; }
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+    int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+    if (Ho_cut > 0 && Ho_cut <= Ho) Ho = Ho_cut;   // (hmv_op_conv2d_as: the top-left Ho x Wo of the conv's map, residual and output rows of that size)
+    if (Wo_cut > 0 && Wo_cut <= Wo) Wo = Wo_cut;
     const void *x = in, *res = residual;
     void *din = nullptr, *dres = nullptr;
     RangeWord rw;
@@ -2529,6 +2531,20 @@ int hmv_op_conv2d_rd(int32_t device, const float *in, int32_t N, int32_t H, int3
     }
     return op_conv("hmv_op_conv2d_rd", device, HMV_F32, in, N, H, W, C, w_oihw, bias_host, C, 3, 3, 1, 1, residual, relu, out, false,
                    route_rd(kernel_sel), kernel_name, stream, false, true);
+}
+
+int hmv_op_conv2d_as(int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *w_oihw,
+                     const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride, int32_t pad, const float *residual,
+                     int32_t relu, float *out, int32_t Ho, int32_t Wo, int32_t packing, const char **kernel_name, void *stream) {
+    const int Ho_own = (H + 2 * pad - R) / stride + 1, Wo_own = (W + 2 * pad - S) / stride + 1;
+    const bool rd = packing == 1;
+    if (packing < 0 || packing > 1 || Ho < 0 || Wo < 0 || Ho > Ho_own || Wo > Wo_own ||
+        (rd && (dtype != HMV_F32 || R != 3 || S != 3 || stride != 1 || pad != 1 || Ho || Wo || Cout % 4 != 0 || 3 * Cout > 256 || W <= 0 || 128 % W != 0))) {
+        g_create_err = "hmv_op_conv2d_as: packing 0 / 1 (1: fp32 3x3 stride 1 pad 1, Cout % 4 == 0, 3 Cout <= 256, 128 % W == 0, own map size), Ho x Wo within the conv's own map";
+        return HMV_ERR_ARG;
+    }
+    return op_conv("hmv_op_conv2d_as", device, dtype, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
+                   conv_rule(), kernel_name, stream, false, rd, Ho, Wo);
 }
 
 }  // extern "C"

@@ -176,11 +176,16 @@ int hmv_read_stage(hmv_handle h, const char *stage, float *dst_device, size_t ca
  * hmv_profile_* read them back after the caller has synchronised the stream. */
 int hmv_set_profiling(hmv_handle h, int32_t enable);
 int hmv_profile_count(hmv_handle h);
-/* name: kernel family = one device symbol ("conv_igemm_f32<256x256,1x1>" ...); label: layer ("layer3.2.conv2");
- * ms: duration; flops: algorithmic 2*M*N*K of that launch. */
+/* name: kernel family = one device symbol ("conv_igemm_f32<256x256,1x1>" ...); label: layer ("layer3.2.conv2"; "a+b": one launch
+ * for both); ms: duration; flops: 2*M*N*K of that launch over the real (un-padded) channels -- M the rows the launch computes, so a
+ * SampleNet conv counts the 4 gathered pixels of each joint, not the whole map, and an up-sampling fuse term that runs alone counts
+ * the up-sampled pixels (the fused form, hr_fuse.hip, multiplies at the sources' resolution and counts that). */
 int hmv_profile_get(hmv_handle h, int32_t index, const char **name, const char **label, float *ms, double *flops);
 /* algorithmic HBM bytes of that launch: input pixels, weights, residual and output rows each moved once in the storage type of
- * the arithmetic mode (what bench.py prices the launch's HBM roofline with). */
+ * the arithmetic mode (what bench.py prices the launch's HBM roofline with).  A strided 1x1 reads only the pixels it keeps; a pooled
+ * launch never moves the conv map; a dual launch reads each source at the pixels it uses; a (hi, lo) pair is 4 bytes; the fused
+ * up-sampling launch of an HRNet fuse layer keeps fp32 weights in every mode (4 bytes each).  tests/test_gpu_launch_ledger.py
+ * recomputes flops and bytes of every launch of the benchmarked forwards from these sentences. */
 int hmv_profile_get_bytes(hmv_handle h, int32_t index, double *bytes);
 /* Device operations (kernel launches, memsets, device-to-device copies) that the last eagerly run forward of this handle
  * enqueued: the "launches per forward" figure of bench.py (a hipGraph replay enqueues ONE graph of as many nodes). */
@@ -213,6 +218,20 @@ int hmv_op_conv2d_ex(int32_t device, int32_t dtype, const float *in, int32_t N, 
  * 64 % W == 0) whatever the size.  *kernel_name (optional) receives the family that ran. */
 int hmv_op_conv2d_rd(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t C, const float *weight_oihw_host,
                      const float *bias_host, const float *residual, int32_t relu, float *out, int32_t kernel_sel,
+                     const char **kernel_name, void *stream);
+
+/* hmv_op_conv2d_ex (fp32 output rows in every mode, the launcher's own kernel choice) in the launch geometries and packings of the
+ * engine that the other entries cannot express, with the kernel family reported (op-level tests at the benchmarked shapes):
+ *   Ho, Wo > 0: only the top-left Ho x Wo of the conv's output map is computed (<= the conv's own size; residual and `out` are
+ *               [N][Ho][Wo][Cout]) -- how the ResNet stem runs: a 4x4 pad-2 conv over 2x2 space-to-depth frames cut to H x W;
+ *               0 = the conv's own size.
+ *   packing 1:  the ROW-DECOMPOSED packing of hmv_op_conv2d_rd for Cin != Cout as well (HRNet-w40's transition 256 -> 40): HMV_F32, 3x3
+ *               stride 1 pad 1, Cout % 4 == 0, 3 Cout <= 256, 128 % W == 0, Ho = Wo = 0; the bias is then applied as a BatchNorm shift.
+ *               0 = the plain packing.
+ * HMV_F16: what a layer of the fp16 path that writes fp32 rows runs (heat-map logits, SampleNet rows). */
+int hmv_op_conv2d_as(int32_t device, int32_t dtype, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                     const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
+                     int32_t pad, const float *residual, int32_t relu, float *out, int32_t Ho, int32_t Wo, int32_t packing,
                      const char **kernel_name, void *stream);
 
 /* hmv_op_conv2d with a kernel selector (op-level parity tests): 0 = the launcher's choice, 1 = conv_igemm only, 2 = the persistent

@@ -206,7 +206,8 @@ def test_hrnet_release_shape(mode):
     V = 8, 256 x 256, B = 9 -> 72 frames, above every size gate of the engine (conv_rds_f32, conv_hs<40|80>, the 256 x 192 tile,
     the >= 65 536-pixel tile rules, the layer1 chain), which the 128 x 128 HRNet fixtures never reach.  Sample 0 against the
     fixture of the REAL reference (hr40_v8_256: the same frames, synth_inputs is a counter hash) and against the f64 oracle at
-    the mode's bar; samples 0, 4, 8 bit-equal to their single-sample runs; everything finite."""
+    the mode's bar; after the workspace has been filled with NaN patterns, EVERY one of the 9 samples bit-equal to its single-sample run in
+    the outputs and the captured stages; everything finite."""
     from handmvnet_amd import HandMvNet
     from handmvnet_amd.synth import synth_inputs
     from oracle.oracle import Oracle
@@ -218,14 +219,18 @@ def test_hrnet_release_shape(mode):
     spec = CASES["hr40_v8_256"]
     x, bbox, intr = synth_inputs(cfg, 9, spec["iseed"], 256)
     assert np.array_equal(x[:1], x1) and np.array_equal(bbox[:1], bbox1) and np.array_equal(intr[:1], intr1)
+    _run(m, x, bbox, intr)
+    m.poison_workspace(0xFF)
     got = _run(m, x, bbox, intr)
-    for k in ("joints_cam", "joints_crop_img", "heatmap", "feat0", "tokens", "fused"):
+    for k in ("joints_cam", "joints_crop_img", "heatmap", "feat0", "coords_hm", "tokens", "fused"):
         assert np.isfinite(got[k]).all(), k
     assert got["heatmap"].shape == (9, 8, 21, 32, 32) and got["feat0"].shape[0] == 72
-    for i in (0, 4, 8):
+    for i in range(9):
         one = _run(m, x[i:i + 1], bbox[i:i + 1], intr[i:i + 1])
-        for k in ("joints_cam", "joints_crop_img", "heatmap"):
+        for k in ("joints_cam", "joints_crop_img", "heatmap", "tokens", "fused"):
             assert np.array_equal(one[k][0], got[k][i]), (mode, i, k)
+        for k in ("feat0", "coords_hm"):
+            assert np.array_equal(one[k], got[k][8 * i:8 * i + 8]), (mode, i, k)
         if i == 0:
             first = one
     # sample 0 vs the real reference's fixture (stages of the B = 1 run have the fixture's shapes) ...
@@ -849,8 +854,10 @@ def test_conv_kernel_random_shapes(dtype, tol):
 @pytest.mark.parametrize("mode", ["f32", "f32x3", "f16"])
 def test_full_size_properties(mode):
     """BASELINE.json configs[2] / configs[4] size (B=32, V=8, 256x256, r50-paper) in every arithmetic mode (their tile rules
-    differ): determinism and batch-independence (sample i alone == sample i inside the batch, bit for bit); and sample 0
-    against the f64 CPU oracle at the mode's own bar."""
+    differ): determinism and batch-independence -- EVERY sample alone == that sample inside the batch, bit for bit, in the two joint
+    outputs, the heat map and the captured stages (feat0, coords_hm, tokens), after the workspace has been filled with NaN patterns
+    (a tile skipped in any sample then shows as NaN instead of the previous forward's correct value); and sample 0 against the f64
+    CPU oracle at the mode's own bar."""
     from handmvnet_amd import HandMvNet
     from handmvnet_amd.synth import synth_inputs
     from oracle.oracle import Oracle
@@ -864,17 +871,27 @@ def test_full_size_properties(mode):
     x, bbox, intr = synth_inputs(cfg, 32, 99, 256)
     dev = torch.device("cuda:0")
     xt, bt, it = torch.from_numpy(x).to(dev), torch.from_numpy(bbox).to(dev), torch.from_numpy(intr).to(dev)
-    a = m(xt, bt, {"intrinsic": it})
+    m.capture_stages(True)
+    stages = ("feat0", "coords_hm", "tokens")
     b = m(xt, bt, {"intrinsic": it})
+    m.poison_workspace(0xFF)
+    a = m(xt, bt, {"intrinsic": it})
+    sa = {k: m.read_stage(k) for k in stages}
     torch.cuda.synchronize()
     assert torch.equal(a["joints_cam"], b["joints_cam"]) and torch.equal(a["joints_crop_img"], b["joints_crop_img"])
     assert torch.isfinite(a["joints_cam"]).all() and torch.isfinite(a["heatmap"]).all()
+    assert all(torch.isfinite(v).all() for v in sa.values())
     assert a["joints_cam"].shape == (32, 21, 3) and a["heatmap"].shape == (32, 8, 21, 32, 32)
-    for i in (0, 17, 31):
+    V = cfg.num_views
+    for i in range(32):
         one = m(xt[i:i + 1], bt[i:i + 1], {"intrinsic": it[i:i + 1]})
+        so = {k: m.read_stage(k) for k in stages}
         torch.cuda.synchronize()
-        assert torch.equal(one["joints_cam"][0], a["joints_cam"][i])
-        assert torch.equal(one["joints_crop_img"][0], a["joints_crop_img"][i])
+        for k in ("joints_cam", "joints_crop_img", "heatmap"):
+            assert torch.equal(one[k][0], a[k][i]), (mode, i, k)
+        assert torch.equal(so["feat0"], sa["feat0"][i * V:(i + 1) * V]), (mode, i, "feat0")
+        assert torch.equal(so["coords_hm"], sa["coords_hm"][i * V:(i + 1) * V]), (mode, i, "coords_hm")
+        assert torch.equal(so["tokens"][0], sa["tokens"][i]), (mode, i, "tokens")
     # soft-argmax coordinates live inside the heat map
     hs = 32
     assert (a["joints_crop_img"] >= -1e-3).all() and (a["joints_crop_img"] <= (hs - 1) * 8 + 1e-3).all()

@@ -13,7 +13,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_last_error", "hmv_destroy", "hmv_set_capture", "hmv_read_stage", "hmv_set_profiling", "hmv_profile_count",
            "hmv_profile_get", "hmv_op_conv2d", "hmv_op_conv2d_ex", "hmv_op_conv2d_f16", "hmv_op_conv2d_sel", "hmv_op_conv2d_rd", "hmv_op_conv2d_as", "hmv_op_attention", "hmv_op_attention_lq", "hmv_bench_conv", "hmv_pose_metrics", "hmv_forward_frames",
            "hmv_op_prepare_frames", "hmv_set_graphs", "hmv_graph_stats", "hmv_version", "hmv_tile_rule", "hmv_profile_get_bytes", "hmv_poison_workspace", "hmv_launch_count", "hmv_set_tail_fusion", "hmv_set_chain_fusion", "hmv_set_hr_fusion", "hmv_op_conv2d_x3", "hmv_op_hr_fuse_up", "hmv_op_attention_x3",
-           "hmv_range_status"]
+           "hmv_range_status", "hmv_op_target_heatmaps", "hmv_project_joints", "hmv_pose_losses", "hmv_pose_losses_scratch_bytes"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -25,6 +25,20 @@ class HmvConfig(ctypes.Structure):
                 ("width", ctypes.c_int32), ("image_size", ctypes.c_int32), ("heatmap_size", ctypes.c_int32),
                 ("pos_enc", ctypes.c_int32), ("fusion_layers", ctypes.c_int32), ("decoder", ctypes.c_int32),
                 ("dtype", ctypes.c_int32), ("device", ctypes.c_int32), ("fusion", ctypes.c_int32)]
+
+
+class HmvLossArgs(ctypes.Structure):
+    """hmv_loss_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("hm_h", ctypes.c_int32),
+                ("hm_w", ctypes.c_int32), ("image_size", ctypes.c_int32), ("sigma", ctypes.c_int32), ("root_idx", ctypes.c_int32),
+                ("mask_invisible_joints", ctypes.c_int32), ("with_projection", ctypes.c_int32),
+                ("w_heatmap", ctypes.c_float), ("w_joints_2d", ctypes.c_float), ("w_joints_3d", ctypes.c_float),
+                ("w_g2d", ctypes.c_float), ("w_p2d", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("pred_heatmap", ctypes.c_void_p), ("target_heatmap", ctypes.c_void_p), ("pred_joints_2d", ctypes.c_void_p),
+                ("gt_joints_2d", ctypes.c_void_p), ("joints_mask", ctypes.c_void_p), ("pred_joints_cam", ctypes.c_void_p),
+                ("gt_joints_cam", ctypes.c_void_p), ("root_joint", ctypes.c_void_p), ("intrinsic", ctypes.c_void_p),
+                ("extrinsic", ctypes.c_void_p), ("bbox", ctypes.c_void_p), ("projected", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
 
 
 class HandMvError(RuntimeError):
@@ -96,6 +110,14 @@ def load() -> ctypes.CDLL:
     lib.hmv_bench_conv.restype = ctypes.c_int
     lib.hmv_pose_metrics.argtypes = [ci, fp, fp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, ci, fp, fp, vp]
     lib.hmv_pose_metrics.restype = ctypes.c_int
+    lib.hmv_op_target_heatmaps.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, vp]
+    lib.hmv_op_target_heatmaps.restype = ctypes.c_int
+    lib.hmv_project_joints.argtypes = [ci, fp, ci, ci, ci, fp, fp, fp, fp, vp]
+    lib.hmv_project_joints.restype = ctypes.c_int
+    lib.hmv_pose_losses.argtypes = [ci, ctypes.POINTER(HmvLossArgs), fp, vp]
+    lib.hmv_pose_losses.restype = ctypes.c_int
+    lib.hmv_pose_losses_scratch_bytes.argtypes = [ci, ci]
+    lib.hmv_pose_losses_scratch_bytes.restype = ctypes.c_size_t
     lib.hmv_forward_frames.argtypes = [vp, ci, fp, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                        fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames.restype = ctypes.c_int

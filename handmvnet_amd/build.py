@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libhandmv.so")
-SOURCES = ["conv_igemm.hip", "conv_stream.hip", "conv_gemm8.hip", "conv_hs.hip", "conv_ht.hip", "conv_m16.hip", "gemm_x3.hip", "conv_rds.hip", "misc_kernels.hip", "fusion_kernels.hip", "hr_fuse.hip", "engine.hip", "metrics.hip"]
+SOURCES = ["conv_igemm.hip", "conv_stream.hip", "conv_gemm8.hip", "conv_hs.hip", "conv_ht.hip", "conv_m16.hip", "gemm_x3.hip", "conv_rds.hip", "misc_kernels.hip", "fusion_kernels.hip", "hr_fuse.hip", "engine.hip", "metrics.hip", "losses.hip"]
 HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(os.path.dirname(HERE), "include", "handmv.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 
@@ -29,6 +29,8 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not force and not _stale(LIB, [os.path.join(CSRC, src) for src in SOURCES] + HEADERS):
+        return LIB   # newer than every source and header: nothing to do, whether or not the object files are still around
     os.makedirs(OBJ, exist_ok=True)
     objs = []
     for src in SOURCES:

@@ -549,6 +549,9 @@ const char *hmv_tile_rule(int32_t M, int32_t Cout, int32_t K, int32_t f16, int32
 
 const char *hmv_last_error(hmv_handle h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+// the handle-less entries of the other translation units (losses.hip) report through the same per-thread text
+extern "C++" void hmv::set_thread_error(const std::string &msg) { g_create_err = msg; }
+
 int hmv_create(const hmv_config *cfg, hmv_handle *out) {
     auto bad = [&](const char *m) { g_create_err = m; return HMV_ERR_ARG; };
     if (!cfg || !out) return bad("null argument");

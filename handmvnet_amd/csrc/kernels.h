@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <string>
 
 // Development knobs (A/B switches, probes: DESIGN.md section 9) exist only in a -DHMV_DEV_KNOBS build
 // (`python -m handmvnet_amd.build --variant dev HMV_DEV_KNOBS` -> build/libhandmv_dev.so, loaded with HMV_LIB=...).  The product
@@ -323,5 +324,8 @@ bool cheb_fusable(int K, int ldx, int ldw1, int c1, int ldw2, int c2, int ldw3, 
 // NHWC -> NCHW copy (stage capture)
 hipError_t launch_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C, hipStream_t s, int ld = 0);
 hipError_t launch_copy_rows(const float *in, int ldi, float *out, int ldo, int rows, int cols, hipStream_t s);
+
+// Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
+void set_thread_error(const std::string &msg);
 
 }  // namespace hmv

@@ -4,8 +4,8 @@ Same constructor, same ``forward(x, bbox, cam_params) -> dict`` and the same ``s
 key layout as /root/reference/src/models/handmvnet.py:27-266, routed to the MI355X engine
 (libhandmv.so) through the C ABI of include/handmv.h.  The evaluation side of ``test_step``
 (handmvnet.py:352-383, 493-517: MPJPE / PA-MPJPE / PCK-AUC) runs on the device as well
-(handmvnet_amd/metrics.py); training hooks, losses and the MANO mesh step are outside the
-accelerated hot path.
+(handmvnet_amd/metrics.py), and so do the losses that step logs (handmvnet.py:279-351, handmvnet_amd/losses.py); training
+(backward, optimiser) and the MANO mesh step are outside the accelerated hot path.
 """
 from __future__ import annotations
 
@@ -57,6 +57,10 @@ class HandMvNet(torch.nn.Module):
         self._profiling = False
         self._graphs = None   # None: the engine's default (off unless HMV_GRAPHS=1)
         self._last_key: Optional[tuple] = None
+        # where the evaluation step's heat-map targets come from: "batch" = inputs["heatmap"] (the reference's DataLoader product),
+        # "joints" = rebuilt inside the loss kernel from inputs["joints_crop_img"] (no target tensor has to exist)
+        self.heatmap_targets = "batch"
+        self.last_losses: Dict[str, object] = {}   # what the reference logs from _calculate_loss, by its log names
 
     # ------------------------------------------------------------------ Lightning-style protocol
     def freeze(self):
@@ -301,16 +305,52 @@ class HandMvNet(torch.nn.Module):
             raise NotImplementedError("get_vertices needs manopth + MANO assets (joints_to_vertices.py:14-23), absent here")
         return out_metrics
 
+    def _calculate_loss(self, out, inputs, cam_params, mode="train"):
+        """handmvnet.py:279-351 for a root-relative model as ONE device call (hmv_pose_losses): returns the total as a 0-dim device
+        tensor, leaves every term in self.last_losses under the names the reference logs (f"{mode}/heatmap_loss" ...; root_3d_loss
+        is the constant 0.) and, when "g2d" is a configured weight, sets out["projected_joints_crop_img"].  Labels on the host are
+        moved to the device.  heatmap_targets == "joints": inputs["heatmap"] is not read; the kernel rebuilds each target pixel from
+        inputs["joints_crop_img"], data_params["image_size"] and the predicted map's size."""
+        from .losses import pose_losses
+        if not self.train_params["root_relative"]:
+            raise NotImplementedError("root_relative: false is not supported (no root-joint head in this build)")
+        if self.heatmap_targets not in ("batch", "joints"):
+            raise ValueError('heatmap_targets must be "batch" or "joints"')
+        weights = self.train_params["loss_weights"]
+        kw = {}
+        if "joints_img_mask" in inputs:
+            kw.update(joints_mask=inputs["joints_img_mask"], mask_invisible_joints=self.train_params["mask_invisible_joints"])
+        if "g2d" in weights:
+            root_idx = inputs["root_idx"]
+            kw.update(root_joint=inputs["root_joint"], root_idx=int(root_idx[0]) if hasattr(root_idx, "__len__") else int(root_idx),
+                      intrinsic=cam_params["intrinsic"], extrinsic=cam_params["extrinsic"], bbox=inputs["bboxes"])
+        if self.heatmap_targets == "batch":
+            kw.update(target_heatmap=inputs["heatmap"])
+        else:
+            kw.update(image_size=self.data_params["image_size"], sigma=2)   # ho3d.py:161
+        res, projected = pose_losses(out["heatmap"], out["joints_crop_img"], out["joints_cam"], inputs["joints_crop_img"],
+                                     inputs["joints_cam"], weights, **kw)
+        if projected is not None:
+            out["projected_joints_crop_img"] = projected
+        has_proj = "g2d" in weights
+        self.last_losses = {f"{mode}/heatmap_loss": res[0], f"{mode}/joints_2d_loss": res[1], f"{mode}/joints_3d_loss": res[2],
+                            f"{mode}/root_3d_loss": 0., f"{mode}/g2d_loss": res[3] if has_proj else 0.,
+                            f"{mode}/p2d_loss": res[4] if has_proj else 0., f"{mode}/loss": res[5]}
+        return res[5]
+
     def _eval_step(self, batch, mode):
-        """The body validation_step and test_step share in the reference (handmvnet.py:468-491 / 493-517): forward +
-        metrics.  The training losses are not part of this build, so "loss" is None.  Like the reference, converts
-        inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE."""
+        """The body validation_step and test_step share in the reference (handmvnet.py:468-491 / 493-517): forward + loss +
+        metrics.  "loss" is _calculate_loss(...) when the batch carries inputs["heatmap"] (or heatmap_targets == "joints"), and None
+        for a batch without loss labels.  Like the reference, converts inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE."""
         inputs = batch["data"]
         out = self.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
         inputs["joints_cam"] /= 1000
         if "root_joint" in inputs:
             inputs["root_joint"] /= 1000
-        return {"loss": None, "metrics": self._calculate_mpjpe(out, inputs, mode=mode)}
+        loss = None
+        if "heatmap" in inputs or self.heatmap_targets == "joints":
+            loss = self._calculate_loss(out, inputs, batch["cam_params"], mode=mode)
+        return {"loss": loss, "metrics": self._calculate_mpjpe(out, inputs, mode=mode)}
 
     def validation_step(self, batch, batch_idx=0):
         """handmvnet.py:468-491: metric keys carry the "val_" prefix (val_mpjpe is what ModelCheckpoint monitors, train.py:34)."""

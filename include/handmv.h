@@ -343,6 +343,85 @@ int hmv_pose_metrics(int32_t device, const float *pred, const float *target, int
                      float thr_min, float thr_max, int32_t steps, int32_t procrustes, float *aligned, float *result,
                      void *stream);
 
+/* ---- evaluation-step losses (HandMvNet._calculate_loss, handmvnet.py:279-351) ----
+ * Stateless like the metrics entry: a device ordinal and a stream, asynchronous, device pointers throughout.  A bad argument returns
+ * HMV_ERR_ARG and the text behind a NULL handle's last error names it.  Sums are fp64 and every reduction has a fixed order, so
+ * results are bit-reproducible; per-element arithmetic is fp64 where the reference's is fp32 (parity is stated against the
+ * reference evaluated in float64).
+ *
+ * Three behaviours of the reference are worth knowing:
+ *   - a label whose whole Gaussian lies outside the image (truncated coordinate c >= S + 3 sigma or c <= -3 sigma - 2 on either
+ *     axis): the reference's generate_heatmap returns a tuple there (datasets/utils.py:105) and the dataset transform raises; this
+ *     library writes the all-zero map that line's comment intends (c = -3 sigma - 1 is an all-zero map in the reference too);
+ *   - the crop mapping of the reprojection always scales by 256: handmvnet.py:332 passes no image_size, so datasets/utils.py:128-129
+ *     uses its default even for a 128-pixel configuration.  Reproduced as is;
+ *   - a singular extrinsic makes torch.inverse raise; a kernel cannot, so the coordinates (and the terms built on them) come out
+ *     non-finite. */
+
+/* The dataset's ground-truth heat maps (datasets/ho3d.py:155-166): per joint generate_heatmap on a zero image_size x image_size image
+ * (datasets/utils.py:86-121; the label truncated toward zero, 6 sigma + 1 taps exp(-d^2 / (2 sigma^2)) per axis, cropped to the image)
+ * -> ToTensor in float64 -> Resize((hm_h, hm_w), antialias=True) -> fp32.  Evaluated separably in fp64 (row profile x column profile,
+ * one rounding), which matches the reference's float64 pipeline to the last fp32 bit or the one next to it.
+ *   joints [n_frames][21][2] crop-image x, y;  out [n_frames][21][hm_h][hm_w];  sigma an integer in 1 .. 8 (the reference uses 2);
+ *   hm_h, hm_w >= 1 with hm_h + hm_w <= 256, independent of each other and of image_size (the scales need not be integers). */
+int hmv_op_target_heatmaps(int32_t device, const float *joints, int32_t n_frames, int32_t image_size, int32_t hm_h, int32_t hm_w,
+                           int32_t sigma, float *out, void *stream);
+
+/* get_2d_joints_from_3d_joints (utils/camera.py:25-44) as one launch instead of a Python loop over batch x views:
+ *   X_w = extrinsic[b][root_idx] [X; 1],  X_i = inverse(extrinsic[b][i]) X_w  (a GENERAL 4x4 inverse in fp64, as torch.inverse is:
+ *   not [R^T | -R^T t]),  x1000,  u = x fx / (z + 1e-6) + cx,  v = y fy / (z + 1e-6) + cy.
+ *   joints_abs [B][21][3] metres in camera root_idx;  extrinsic [B][V][4][4];  intrinsic [B][V][4] = fx, fy, cx, cy;
+ *   bbox NULL: out [B][V][21][2] in image pixels (what the reference function returns);
+ *   bbox [B][V][4] = x1, y1, x2, y2: followed by batch_joints_img_to_cropped_joints, (u - x1) 256 / (x2 - x1), (v - y1) 256 / (y2 - y1). */
+int hmv_project_joints(int32_t device, const float *joints_abs, int32_t B, int32_t V, int32_t root_idx, const float *intrinsic,
+                       const float *extrinsic, const float *bbox, float *out, void *stream);
+
+typedef struct hmv_loss_args {
+    int32_t struct_size;            /* sizeof(hmv_loss_args), ABI guard */
+    int32_t B, V;                   /* samples, views */
+    int32_t hm_h, hm_w;             /* size of the predicted heat maps */
+    int32_t image_size, sigma;      /* read when target_heatmap is NULL: the S and sigma of hmv_op_target_heatmaps */
+    int32_t root_idx;               /* inputs["root_idx"][0]: the camera joints_cam + root_joint live in (with_projection) */
+    int32_t mask_invisible_joints;  /* train_params["mask_invisible_joints"] */
+    int32_t with_projection;        /* "g2d" in train_params["loss_weights"]: the g2d / p2d terms exist */
+    float w_heatmap, w_joints_2d, w_joints_3d, w_g2d, w_p2d;   /* train_params["loss_weights"] */
+    int32_t reserved;               /* 0 */
+    const float *pred_heatmap;      /* out["heatmap"]            [B][V][21][hm_h][hm_w] */
+    const float *target_heatmap;    /* inputs["heatmap"], same shape; NULL: synthesised per joint from gt_joints_2d exactly as
+                                     * hmv_op_target_heatmaps would (same device function: the two forms give the same bits) */
+    const float *pred_joints_2d;    /* out["joints_crop_img"]    [B][V][21][2] */
+    const float *gt_joints_2d;      /* inputs["joints_crop_img"] [B][V][21][2] */
+    const uint8_t *joints_mask;     /* inputs["joints_img_mask"] [B][V][21], non-zero = invisible; may be NULL */
+    const float *pred_joints_cam;   /* out["joints_cam"]         [B][21][3] metres, root-relative */
+    const float *gt_joints_cam;     /* inputs["joints_cam"]      [B][21][3] metres */
+    const float *root_joint;        /* inputs["root_joint"]      [B][3] metres; NULL = zeros (with_projection) */
+    const float *intrinsic;         /* [B][V][4]     (with_projection) */
+    const float *extrinsic;         /* [B][V][4][4]  (with_projection) */
+    const float *bbox;              /* [B][V][4]     (with_projection) */
+    float *projected;               /* out["projected_joints_crop_img"] [B][V][21][2], optional output (with_projection) */
+    void *scratch;                  /* caller-owned device buffer, 8-byte aligned */
+    size_t scratch_bytes;           /* >= what the scratch sizing entry below gives for B, V */
+} hmv_loss_args;
+
+/* Bytes of scratch one loss call over B samples of V views needs (one fp64 partial per frame). */
+size_t hmv_pose_losses_scratch_bytes(int32_t B, int32_t V);
+
+/* Every term of _calculate_loss for a root-relative model.  result: device fp32 [6] =
+ *   { heatmap_loss, joints_2d_loss, joints_3d_loss, g2d_loss, p2d_loss, loss }   (root_3d_loss is the constant 0; [3], [4] are 0 without
+ *   with_projection; loss is the sum of the terms present)
+ *   heatmap_loss   = w_heatmap   * mean (pred - target)^2 over [B][V][21][hm_h][hm_w]
+ *   joints_2d_loss = w_joints_2d * mean |p - g| over [B][V][21][2]; with a mask AND mask_invisible_joints, masked joints are zeroed
+ *                    on both sides and the divisor stays the full count (models/utils.py:123-131)
+ *   joints_3d_loss = w_joints_3d * mean |pred_joints_cam - gt_joints_cam|
+ *   g2d_loss / p2d_loss = w * mean |proj - gt_joints_2d| / |proj - pred_joints_2d|, unmasked like the reference; proj is the crop-mapped
+ *                    projection of pred_joints_cam + root_joint (the projection entry above with a bbox), used at fp64 before the
+ *                    rounding that `projected` receives.
+ * Two launches: one workgroup per frame writes the fp64 sum of its 21 * hm_h * hm_w squared differences to scratch (16-byte loads
+ * where the frame's base addresses allow, scalar loads otherwise, added in the same order either way); one workgroup then adds the
+ * frame sums in index order and computes the small terms.  The bits depend on neither the number of workgroups in flight, nor
+ * alignment, nor the target form. */
+int hmv_pose_losses(int32_t device, const hmv_loss_args *args, float *result, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

@@ -1,0 +1,204 @@
+// Device code shared by the evaluation kernels (metrics.hip: one step's metrics; eval_epoch.hip: an epoch's running sums), so
+// that the two cannot drift apart: the workgroup reduction, the 3x3 SVD, and the per-row arithmetic of models/metrics.py --
+// thresholds as torch.linspace builds them, the fp32 joint distance, its PCK bin, the similarity alignment of one pose (two macros, below).
+// The arithmetic that decides a comparison (joint distance vs threshold) is fp32 like the reference's; sums and the 3x3 Procrustes
+// problem run in fp64.  Both kernels are single-workgroup launches of kThreads lanes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kMaxSteps = 256;
+
+// Fixed-order tree reduction over the workgroup; every lane gets the total.
+__device__ double block_sum(double v, double* red) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// One-sided Jacobi (Hestenes) SVD of a 3x3 matrix: a = u * diag(s) * v^T, s descending.
+// A column of u that belongs to a zero singular value is completed with the cross product of the others.
+__device__ void svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3]) {
+    double w[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            w[i][j] = a[i][j];
+            v[i][j] = i == j ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double al = 0, be = 0, ga = 0;
+                for (int i = 0; i < 3; ++i) {
+                    al += w[i][p] * w[i][p];
+                    be += w[i][q] * w[i][q];
+                    ga += w[i][p] * w[i][q];
+                }
+                if (fabs(ga) <= 1e-300 || fabs(ga) <= 1e-17 * sqrt(al * be)) continue;
+                off = fmax(off, fabs(ga) / sqrt(al * be));
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+                for (int i = 0; i < 3; ++i) {
+                    const double wp = w[i][p], wq = w[i][q];
+                    w[i][p] = c * wp - sn * wq;
+                    w[i][q] = sn * wp + c * wq;
+                    const double vp = v[i][p], vq = v[i][q];
+                    v[i][p] = c * vp - sn * vq;
+                    v[i][q] = sn * vp + c * vq;
+                }
+            }
+        if (off < 1e-15) break;
+    }
+    double n[3];
+    for (int j = 0; j < 3; ++j) n[j] = sqrt(w[0][j] * w[0][j] + w[1][j] * w[1][j] + w[2][j] * w[2][j]);
+    int ord[3] = {0, 1, 2};
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2 - i; ++j)
+            if (n[ord[j]] < n[ord[j + 1]]) {
+                const int tmp = ord[j];
+                ord[j] = ord[j + 1];
+                ord[j + 1] = tmp;
+            }
+    double vs[3][3];
+    for (int j = 0; j < 3; ++j) {
+        const int o = ord[j];
+        s[j] = n[o];
+        for (int i = 0; i < 3; ++i) {
+            vs[i][j] = v[i][o];
+            u[i][j] = n[o] > 0 ? w[i][o] / n[o] : 0.0;
+        }
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) v[i][j] = vs[i][j];
+    const double tiny = 1e-14 * s[0];
+    if (s[2] <= tiny) {
+        if (s[1] <= tiny) {   // rank <= 1: any orthonormal completion
+            int k = 0;
+            if (s[0] > 0) {
+                for (int i = 1; i < 3; ++i)
+                    if (fabs(u[i][0]) < fabs(u[k][0])) k = i;
+            } else {
+                u[0][0] = 1; u[1][0] = 0; u[2][0] = 0;
+                k = 1;
+            }
+            double e[3] = {0, 0, 0};
+            e[k] = 1.0;
+            const double d = e[0] * u[0][0] + e[1] * u[1][0] + e[2] * u[2][0];
+            double nn = 0;
+            for (int i = 0; i < 3; ++i) {
+                u[i][1] = e[i] - d * u[i][0];
+                nn += u[i][1] * u[i][1];
+            }
+            nn = sqrt(nn);
+            for (int i = 0; i < 3; ++i) u[i][1] /= nn;
+        }
+        u[0][2] = u[1][0] * u[2][1] - u[2][0] * u[1][1];
+        u[1][2] = u[2][0] * u[0][1] - u[0][0] * u[2][1];
+        u[2][2] = u[0][0] * u[1][1] - u[1][0] * u[0][1];
+    }
+}
+
+__device__ double det3(const double m[3][3]) {
+    return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+}
+
+// thr[0 .. steps) = torch.linspace(tmin, tmax, steps) in fp32: symmetric fill from both ends, one fma per value (metrics.py:105).
+// Lanes 0 .. steps - 1 write one value each; the caller synchronises.
+__device__ __forceinline__ void fill_thresholds(float* thr, float tmin, float tmax, int steps) {
+    const int t = threadIdx.x;
+    if (t < steps) {
+        const float step = steps > 1 ? (tmax - tmin) / (float)(steps - 1) : 0.f;
+        thr[t] = t < steps / 2 ? fmaf(step, (float)t, tmin) : fmaf(-step, (float)(steps - 1 - t), tmax);
+        if (steps == 1) thr[t] = tmin;
+    }
+}
+
+// |p - g| of one row of `dim` coordinates, in fp32 (metrics.py:12, 77)
+__device__ __forceinline__ float row_distance(const float* p, const float* g, int dim) {
+    float acc = 0.f;
+    for (int c = 0; c < dim; ++c) {
+        const float d = p[c] - g[c];
+        acc += d * d;
+    }
+    return sqrtf(acc);
+}
+
+// PCK histogram bin of a distance: the first threshold with dist <= thr (thresholds ascend), `steps` when there is none
+__device__ __forceinline__ int threshold_bin(float dist, const float* thr, int steps) {
+    int b = 0;
+    while (b < steps && !(dist <= thr[b])) ++b;
+    return b;
+}
+
+}  // namespace
+
+// The similarity transform of one predicted pose p [n_pts][3] (const float*) onto its target g (metrics.py:128-176), in two pieces.
+// Macros on purpose.  As inlined functions the same statements reach the optimiser in another order, svd3's arrays are promoted
+// differently and pose_metrics_kernel's code changes; shared as text, that kernel's device assembly stays what it was before the
+// epoch kernel existed (tools/isa_diff.py), and both kernels still have one copy of the arithmetic.
+
+// Declares, in the enclosing scope, the means mu1 / mu2 (double[3]), the variance var1 of p and the cross-covariance K (double[3][3]).
+#define POSE_MOMENTS(p, g, n_pts, mu1, mu2, var1, K)                                                                              \
+    double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};                                                                                \
+    for (int j = 0; j < (n_pts); ++j)                                                                                             \
+        for (int c = 0; c < 3; ++c) {                                                                                             \
+            mu1[c] += (p)[j * 3 + c];                                                                                             \
+            mu2[c] += (g)[j * 3 + c];                                                                                             \
+        }                                                                                                                         \
+    for (int c = 0; c < 3; ++c) {                                                                                                 \
+        mu1[c] /= (n_pts);                                                                                                        \
+        mu2[c] /= (n_pts);                                                                                                        \
+    }                                                                                                                             \
+    double var1 = 0.0, K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};                                                               \
+    for (int j = 0; j < (n_pts); ++j) {                                                                                           \
+        double x1[3], x2[3];                                                                                                      \
+        for (int c = 0; c < 3; ++c) {                                                                                             \
+            x1[c] = (p)[j * 3 + c] - mu1[c];                                                                                      \
+            x2[c] = (g)[j * 3 + c] - mu2[c];                                                                                      \
+            var1 += x1[c] * x1[c];                                                                                                \
+        }                                                                                                                         \
+        for (int a = 0; a < 3; ++a)                                                                                               \
+            for (int b = 0; b < 3; ++b) K[a][b] += x1[a] * x2[b];                                                                 \
+    }
+
+// From the moments and svd3(K, U, S, V): adds to the double `sum`, point by point, the distance that remains after the transform.
+// aligned (float*, may be null): the base of a [poses][n_pts][3] output whose rows row0 .. row0 + n_pts - 1 receive the transformed points.
+#define POSE_ADD_ALIGNED_ERROR(p, g, n_pts, mu1, mu2, var1, K, U, V, aligned, row0, sum)                                          \
+    /* Z = diag(1, 1, sign(det(U V^T)));  R = V Z U^T */                                                                          \
+    double UVt[3][3];                                                                                                             \
+    for (int a = 0; a < 3; ++a)                                                                                                   \
+        for (int b = 0; b < 3; ++b) UVt[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + U[a][2] * V[b][2];                        \
+    const double dd = det3(UVt);                                                                                                  \
+    const double z = dd > 0 ? 1.0 : (dd < 0 ? -1.0 : 0.0);                                                                        \
+    double R[3][3];                                                                                                               \
+    for (int a = 0; a < 3; ++a)                                                                                                   \
+        for (int b = 0; b < 3; ++b) R[a][b] = V[a][0] * U[b][0] + V[a][1] * U[b][1] + z * V[a][2] * U[b][2];                      \
+    double trace = 0.0; /* trace(R K) */                                                                                          \
+    for (int a = 0; a < 3; ++a)                                                                                                   \
+        for (int b = 0; b < 3; ++b) trace += R[a][b] * K[b][a];                                                                   \
+    const double scale = trace / var1;                                                                                            \
+    double tr[3];                                                                                                                 \
+    for (int a = 0; a < 3; ++a)                                                                                                   \
+        tr[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);                                        \
+    for (int j = 0; j < (n_pts); ++j) {                                                                                           \
+        double e2 = 0.0;                                                                                                          \
+        for (int a = 0; a < 3; ++a) {                                                                                             \
+            const double y = scale * (R[a][0] * (p)[j * 3] + R[a][1] * (p)[j * 3 + 1] + R[a][2] * (p)[j * 3 + 2]) + tr[a];        \
+            if (aligned) (aligned)[((row0) + j) * 3 + a] = (float)y;                                                              \
+            const double e = y - (double)(g)[j * 3 + a];                                                                          \
+            e2 += e * e;                                                                                                          \
+        }                                                                                                                         \
+        (sum) += sqrt(e2);                                                                                                        \
+    }

@@ -61,6 +61,7 @@ class HandMvNet(torch.nn.Module):
         # "joints" = rebuilt inside the loss kernel from inputs["joints_crop_img"] (no target tensor has to exist)
         self.heatmap_targets = "batch"
         self.last_losses: Dict[str, object] = {}   # what the reference logs from _calculate_loss, by its log names
+        self.last_loss_vector: Optional[torch.Tensor] = None   # the same call's device fp32 [6], in the order of losses.TERMS
 
     # ------------------------------------------------------------------ Lightning-style protocol
     def freeze(self):
@@ -333,6 +334,7 @@ class HandMvNet(torch.nn.Module):
         if projected is not None:
             out["projected_joints_crop_img"] = projected
         has_proj = "g2d" in weights
+        self.last_loss_vector = res
         self.last_losses = {f"{mode}/heatmap_loss": res[0], f"{mode}/joints_2d_loss": res[1], f"{mode}/joints_3d_loss": res[2],
                             f"{mode}/root_3d_loss": 0., f"{mode}/g2d_loss": res[3] if has_proj else 0.,
                             f"{mode}/p2d_loss": res[4] if has_proj else 0., f"{mode}/loss": res[5]}
@@ -359,6 +361,20 @@ class HandMvNet(torch.nn.Module):
     def test_step(self, batch, batch_idx=0):
         """handmvnet.py:493-517: metric keys carry the "test_" prefix."""
         return self._eval_step(batch, "test")
+
+    def evaluate(self, batches, mode: str = "test", group=None) -> dict:
+        """What trainer.test(model, dm) / trainer.validate hand back (eval.py): the epoch's numbers over every batch of `batches`.
+        Each step enqueues forward, loss and one accumulation launch and copies nothing to the host; one all-reduce combines the ranks
+        when a process group is initialised; one readback ends the epoch.  Every value is sum(B x step value) / sum(B) over steps and
+        ranks -- Lightning's on_epoch mean, and for MPJPE, PA-MPJPE, 2D MPJPE and the PCK curve the value on the pooled split
+        (handmvnet_amd/evaluation.py).  Like test_step, converts each batch's joints_cam / root_joint from mm to metres in place."""
+        from .evaluation import EpochEvaluator
+        ev = EpochEvaluator(self, mode)
+        for batch in batches:
+            ev.step(batch)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            ev.reduce(group)
+        return ev.compute()
 
     # ------------------------------------------------------------------ introspection (tests / bench)
     def capture_stages(self, enable: bool = True):

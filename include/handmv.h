@@ -422,6 +422,56 @@ size_t hmv_pose_losses_scratch_bytes(int32_t B, int32_t V);
  * alignment, nor the target form. */
 int hmv_pose_losses(int32_t device, const hmv_loss_args *args, float *result, void *stream);
 
+/* ---- evaluation epoch (what trainer.validate / trainer.test hand back: one set of numbers for the whole split) ----
+ * hmv_eval_add adds one evaluation step -- everything HandMvNet._calculate_mpjpe (handmvnet.py:370-427) computes for it, and the loss
+ * vector the loss entry above wrote -- into a caller-owned fp64 state vector in device memory.  Nothing is copied to the host: the
+ * caller reads the state back once per epoch and divides.  The epoch value of every quantity is
+ *     sum over steps (and ranks) of B x the step's value  /  sum of B,
+ * the batch-size-weighted mean that Lightning's on_epoch logging produces; MPJPE, PA-MPJPE, 2D MPJPE and the PCK curve are linear in
+ * the rows, so for them it is the value on the pooled split, whatever the cut into batches and ranks.
+ *
+ * State layout: a contiguous array of 15 + steps doubles (hmv_eval_state_doubles(steps)):
+ *   [0]   samples, sum of B                          [1]   steps added
+ *   [2]   3D rows, sum of B * 21                     [3]   sum of the 3D joint distances (the units of joints_cam: metres)
+ *   [4]   sum of the distances after the per-pose similarity alignment
+ *   [5]   2D rows, sum of B * V * 21                 [6]   sum of the 2D joint distances (crop-image pixels)
+ *   [7]   sum of B over the steps that carried a loss
+ *   [8 .. 13]   sum of B * term for the six values of the loss vector, in its order
+ *               { heatmap_loss, joints_2d_loss, joints_3d_loss, g2d_loss, p2d_loss, loss }
+ *   [14 .. 14 + steps]   PCK histogram of the 3D distances, steps + 1 bins: bin i counts the rows whose first threshold with
+ *               dist <= thr is thr[i], thr = torch.linspace(thr_min, thr_max, steps) in fp32; the last bin the rows beyond thr_max.
+ *               The PCK curve is the cumulative histogram over [2].
+ * Counts are integers held in doubles (exact below 2^53).  A masked joint (joints_mask non-zero) is zeroed on both sides, as
+ * models/utils.py:123-131 does: it adds the distance 0 and still counts in [5].  A zero-filled buffer is an empty epoch, so there is
+ * no reset entry; summing the states of several ranks element by element gives the state of their union.
+ * The state belongs to one stream at a time: stream order is what orders successive steps (the kernel's final read-modify-write of the
+ * state is done by one thread, without atomics).
+ *
+ * One single-workgroup launch with the per-row arithmetic of the metrics entry above (same device functions): fp32 for the distance
+ * versus threshold comparison, fp64 sums in a fixed order and the 3x3 Procrustes problem in fp64, no floating-point atomics -- two
+ * identical epochs give identical bits. */
+typedef struct hmv_eval_args {
+    int32_t struct_size;            /* sizeof(hmv_eval_args), ABI guard */
+    int32_t B, V;                   /* samples, views */
+    int32_t steps;                  /* PCK thresholds, 1 .. 256 (the reference uses 20) */
+    float thr_min, thr_max;         /* thr_min <= thr_max, the units of joints_cam */
+    const float *pred_joints_cam;   /* out["joints_cam"]         [B][21][3] metres */
+    const float *gt_joints_cam;     /* inputs["joints_cam"]      [B][21][3] metres */
+    const float *pred_joints_2d;    /* out["joints_crop_img"]    [B][V][21][2] */
+    const float *gt_joints_2d;      /* inputs["joints_crop_img"] [B][V][21][2] */
+    const uint8_t *joints_mask;     /* inputs["joints_img_mask"] [B][V][21], non-zero = invisible; may be NULL */
+    const float *loss_result;       /* the device float[6] the loss entry wrote for this step; NULL: a step without loss labels */
+    double *state;                  /* device, 8-byte aligned */
+    size_t state_doubles;           /* >= hmv_eval_state_doubles(steps) */
+} hmv_eval_args;
+
+/* Doubles in the state of an epoch with `steps` thresholds: 15 + steps; 0 when steps is outside 1 .. 256. */
+size_t hmv_eval_state_doubles(int32_t steps);
+
+/* Adds one step to args->state, asynchronously on `stream`.  Every argument is checked before any HIP call: a bad one returns
+ * HMV_ERR_ARG and the text behind a NULL handle's last error names it. */
+int hmv_eval_add(int32_t device, const hmv_eval_args *args, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

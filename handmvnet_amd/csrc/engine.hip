@@ -1138,6 +1138,14 @@ namespace {
 // second A source of a conv (Bottleneck conv3 + downsample as one GEMM over [t2 | x(strided)])
 struct Dual { const float *in2 = nullptr; int ksplit = 0, H2 = 0, W2 = 0, lda2 = 0, stride2 = 1; };
 
+// An activation map in the workspace, channels-last: [N][H][W][ld] with C real channels, ld the row stride in elements
+struct Map { float *p = nullptr; int N = 0, H = 0, W = 0, C = 0, ld = 0; };
+inline int conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }   // output size of a conv along one axis
+
+// What a backbone hands on: the n sampled feature levels in the reference's feats[] order (handmvnet.py:165-177) and the heat-map logits
+// (fp32, row stride 32)
+struct Features { Map lv[4]; int n = 0; Map hm; };
+
 // One conv / GEMM launch of a packed Layer, said whole: what is not named at the call site has its default here
 struct ConvCall {
     const Layer *L;
@@ -1155,9 +1163,15 @@ struct ConvCall {
     Dual dual;
     const Layer *next = nullptr; float *next_out = nullptr;   // chained 1x1 conv + ReLU (conv_stream.hip)
     int pool_h = 0, pool_w = 0;               // MaxPool2d(3, 2, 1) fused behind it (conv_hs.hip, the fp16 stem): `out` is then the pooled map
+    bool mapped = false, maps_ok = true;      // built from two Maps: Runner::conv holds the output map to the conv's own output grid
 
+    // a launch whose output buffer is not the conv's own output grid: GEMM rows (N = rows, H = W = 1), transposed-conv phases, the pooled
+    // stem, an up-sampling fuse term, the op-level entries
     ConvCall(const Layer &L_, const float *in_, int N_, int H_, int W_, float *out_, int ldc_, int Ho_, int Wo_)
         : L(&L_), in(in_), N(N_), H(H_), W(W_), out(out_), ldc(ldc_), Ho(Ho_), Wo(Wo_) {}
+    ConvCall(const Layer &L_, const Map &x, const Map &y)
+        : L(&L_), in(x.p), N(x.N), H(x.H), W(x.W), out(y.p), ldc(y.ld), Ho(y.H), Wo(y.W), mapped(true),
+          maps_ok(x.N == y.N && x.ld >= x.C && y.ld >= y.C) {}
     ConvCall &s(int v) { stride = v; return *this; }
     ConvCall &pad(int ph, int pw) { pad_h = ph; pad_w = pw; return *this; }
     ConvCall &pad(int v) { return pad(v, v); }   // both ways
@@ -1165,7 +1179,7 @@ struct ConvCall {
     ConvCall &res_rows(int out_group, int in_group) { rg_out = out_group; rg_in = in_group; return *this; }
     ConvCall &act(int a) { activation = a; return *this; }
     ConvCall &f16(bool v) { out_f16 = v; return *this; }
-    ConvCall &filled() { fill = true; return *this; }
+    ConvCall &filled(bool v = true) { fill = v; return *this; }
     ConvCall &upsample(int shift) { up = shift; return *this; }
     ConvCall &phase(int oy, int ox) { scatter = 1; ooy = oy; oox = ox; return *this; }
     ConvCall &all_phases(int n, size_t wstride) { scatter = 1; phases = n; phase_stride = wstride; return *this; }
@@ -1175,6 +1189,8 @@ struct ConvCall {
     ConvCall &pooled(int ph, int pw) { pool_h = ph; pool_w = pw; return *this; }
 };
 
+// One forward in progress: workspace, stream and launch helpers, the two residual blocks, then the stages of HandMvNet.forward
+#define LAUNCH(expr) launch(#expr, [&] { return (expr); })   // (inside Runner: see launch())
 struct Runner {
     hmv_engine *h;
     hipStream_t s;
@@ -1197,6 +1213,19 @@ struct Runner {
         if (defer && p) deferred.push_back(p);
         else A.release(p);
     }
+    // fp16 path: the conv stack (stem .. pose_net / sample convs) stores activations as fp16; heat-map logits,
+    // coordinates, tokens, fusion and decoder stay fp32.  ACT(n) = arena floats for n activation elements.
+    const bool h16 = h->cfg.dtype != HMV_F32;      // the conv stack runs on the fp16 kernels ...
+    const bool split = h->cfg.dtype == HMV_F32X3;  // ... on (hi, lo) pairs: 4 bytes per element like fp32
+    size_t ACT(size_t n) const { return (h16 && !split) ? (n + 1) / 2 : n; }
+    // A map's allocation is sized by its own dims: a conv-stack activation (ld = 0: the NHWC channel stride cpad(C)), or fp32 whatever the mode
+    Map act(int N, int H, int W, int C, int ld = 0) {
+        Map m{nullptr, N, H, W, C, ld ? ld : cpad(C)};
+        m.p = alloc(ACT((size_t)N * H * W * m.ld));
+        return m;
+    }
+    Map f32map(int N, int H, int W, int C, int ld) { return Map{alloc((size_t)N * H * W * ld), N, H, W, C, ld}; }
+    void release(const Map &m) { release(m.p); }
     void fork() {   // the second stream starts behind everything enqueued so far
         defer = true;
         if (dry || rc != HMV_OK) return;
@@ -1329,6 +1358,12 @@ struct Runner {
     void conv(const ConvCall &c) {
         if (dry || rc != HMV_OK) return;
         const Layer &L = *c.L;
+        // two Maps: the output map is the grid the input map, R x S, stride and pad imply (a row-decomposed 3x3 is packed as 3x1), no row
+        // stride cuts its channels -- else stop, like alloc(), before anything is launched
+        if (c.mapped && !(c.maps_ok && c.Ho == conv_out(c.H, L.R, c.stride, c.pad_h) && c.Wo == conv_out(c.W, L.rd_cout ? L.R : L.S, c.stride, c.pad_w))) {
+            rc = h->fail(HMV_ERR_STATE, "%s: output map %d x %d does not fit its input %d x %d", L.label.c_str(), c.Ho, c.Wo, c.H, c.W);
+            return;
+        }
         const ConvParams p = params(c);
         // split layers walk 3x the reduction on fp16 MFMAs: the tile rules see the real reduction length
         const ConvTile tile = conv_pick_tile(p.M, p.Cout, L.plane ? p.K / (L.x3n ? 2 : 3) : p.K, L.f16, c.res != nullptr);
@@ -1407,25 +1442,29 @@ struct Runner {
     // Everything of a fusion block behind the attention in two launches: the split-K to_out GEMM, then ONE kernel for
     // (slice sum + bias + residual) -> [LayerNorm1] -> FeedForward (LayerNorm, Linear, GELU, Linear, + residual) -> [LayerNorm2]
     // (fusion_kernels.hip).  Same alloc / release sequence in the dry (planning) run.
-    bool ff_fusable(const Layer &out, const Layer &ff1, const Layer &ff2, int rows, int ldt, bool have_x3 = false) const {
-        return h->ff_fuse && (have_x3 || splitk_slices(out, rows) > 1) && !ff1.f16 && !ff2.f16 && !ff1.plane && !ff2.plane &&
+    bool ff_fusable(const AttnLayer &a, int rows, bool have_x3 = false) const {
+        const Layer &ff1 = a.ff1, &ff2 = a.ff2;
+        const int ldt = h->ldt;
+        return h->ff_fuse && (have_x3 || splitk_slices(a.out, rows) > 1) && !ff1.f16 && !ff2.f16 && !ff1.plane && !ff2.plane &&
                ff1.Kpad == ldt && ldt % 16 == 0 && (ff1.Cout == 128 || ff1.Cout == 256) && ff2.Kpad == ff1.Cout && ff2.Cout_pad >= ldt &&
                ldt <= 576;
     }
-    void ff_block(const Layer &out, const Layer &ff1, const Layer &ff2, const float *att, int rows, const float *res, int ldr, int rg_out,
-                  int rg_in, const float *n1g, const float *n1b, const float *fg, const float *fb, const float *n2g, const float *n2b,
-                  float *y, int ldt, int d, float *y_pairs = nullptr, const Layer *out_x3 = nullptr) {
-        // out_x3: `att` holds (hi, lo) pairs and to_out runs as ONE split-pair GEMM (gemm_x3.hip) instead of four fp32 split-K slices
-        const int S = out_x3 ? 1 : splitk_slices(out, rows), lds_ = (out.Cout + 3) / 4 * 4;
+    // The layers, the LayerNorm vectors (null where the block has none) and the split-pair to_out are `a`'s; rows of `att` in, token rows
+    // `y` (and their (hi, lo) pair copy `y_pairs`, if not null) out, both with row stride ldt like the residual rows `res`
+    void ff_block(const AttnLayer &a, const float *att, int rows, const float *res, int rg_out, int rg_in, float *y, float *y_pairs, bool x3) {
+        const Layer &out = a.out, &ff1 = a.ff1, &ff2 = a.ff2;
+        const int ldt = h->ldt;
+        // x3: `att` holds (hi, lo) pairs and to_out runs as ONE split-pair GEMM (gemm_x3.hip) instead of four fp32 split-K slices
+        const int S = x3 ? 1 : splitk_slices(out, rows), lds_ = (out.Cout + 3) / 4 * 4;
         float *slab = alloc((size_t)S * rows * lds_);
-        if (out_x3) conv(ConvCall(*out_x3, att, rows, 1, 1, slab, lds_, 1, 1));   // (its own bias is zero)
+        if (x3) conv(ConvCall(a.out_x3, att, rows, 1, 1, slab, lds_, 1, 1));   // (its own bias is zero)
         else conv_slices(out, att, rows, S, slab, lds_);
         launch("ff_block", [&] {
             FfBlockParams p{};
             p.slab = slab; p.S = S; p.slice = (size_t)rows * lds_; p.lds = lds_; p.bias0 = out.bias;
-            p.res = res; p.ldr = ldr; p.rg_out = rg_out; p.rg_in = rg_in;
-            p.rows = rows; p.d = d; p.ld = ldt;
-            p.n1g = n1g; p.n1b = n1b; p.fg = fg; p.fb = fb; p.n2g = n2g; p.n2b = n2b;
+            p.res = res; p.ldr = ldt; p.rg_out = rg_out; p.rg_in = rg_in;
+            p.rows = rows; p.d = h->d; p.ld = ldt;
+            p.n1g = a.n1g; p.n1b = a.n1b; p.fg = a.fg; p.fb = a.fb; p.n2g = a.n2g; p.n2b = a.n2b;
             p.w1 = ff1.w; p.b1 = ff1.bias; p.ldw1 = ff1.Kpad; p.w2 = ff2.w; p.b2 = ff2.bias; p.ldw2 = ff2.Kpad;
             p.out = y; p.ldo = ldt; p.hid = ff1.Cout; p.out_pairs = y_pairs; p.sat = h->sat;
 #ifdef HMV_DEV_KNOBS
@@ -1463,8 +1502,491 @@ struct Runner {
         launch("layernorm", [&] { return launch_layernorm(o, ldy, rows, L.Cout, g1, b1, y, ldy, g2, b2, y2, s); });
         release(o);
     }
-};
 
+    // q/k/v projection of fp32 token rows; in the fp16 / f32x3 modes on the fused split kernels (Loader::linear_x3)
+    // pairs_out: the result rows as (hi, lo) fp16 pairs [hi ldc | lo ldc] (the GEMM's pair epilogue; same bytes as fp32 rows) for a consumer
+    // that multiplies on the fp16 matrix cores (attention_x3_kernel)
+    void project(const Layer &L, const float *a, int rows, float *out, int ldc, float *ready_pairs = nullptr, bool pairs_out = false) {
+        if (!L.plane) { gemm(L, a, rows, out, ldc, nullptr, 0, ACT_NONE); return; }
+        float *pairs = ready_pairs;
+        if (!pairs) {
+            pairs = alloc((size_t)rows * h->ldt);                           // [hi ldt | lo ldt] halfs per row
+            launch("rows_f32_to_half", [&] { return launch_rows_f32_to_half(a, pairs, (size_t)rows, h->ldt, 2, s, h->sat); });
+        }
+        conv(ConvCall(L, pairs, rows, 1, 1, out, ldc, 1, 1).f16(pairs_out));
+        release(pairs);
+    }
+
+    // Bottleneck (resnet.py:124-144; HRNet's layer1): -> its output map; the caller releases `x`.  `t1`: conv1 + BN + ReLU of this block
+    // where the previous block's chained conv3 launch computed it (conv_stream.hip chain), else no map; on return the same for the block
+    // behind this one, `nb`, whose conv1 may ride on this block's conv3 launch
+    Map bottleneck(const Block &b, const Map &x, const Block *nb, Map &t1_chained) {
+        const int planes = b.c1.Cout, outc = b.c3.Cout;
+        const int ho = conv_out(x.H, 3, b.stride, 1), wo = conv_out(x.W, 3, b.stride, 1);
+        Map t1 = t1_chained;
+        if (!t1.p) {
+            t1 = act(x.N, x.H, x.W, planes);
+            conv(ConvCall(b.c1, x, t1).act(ACT_RELU).f16(h16));
+        }
+        Map t2 = act(x.N, ho, wo, planes);
+        conv(ConvCall(b.c2, t1, t2).s(b.stride).pad(1).act(ACT_RELU).f16(h16));
+        release(t1);
+        Map dsb;
+        if (b.has_ds && !b.fused_ds) {
+            dsb = act(x.N, ho, wo, outc);
+            conv(ConvCall(b.ds, x, dsb).s(b.stride).f16(h16));
+        }
+        Map y = act(x.N, ho, wo, outc);
+        // fused_ds: conv3 and the downsample branch as one GEMM over [t2 | x]
+        // out = relu([t2 | x(strided)] . Wcat + b): BN3 and the downsample's BN are in Wcat and b
+        ConvCall c3 = b.fused_ds ? ConvCall(b.c3ds, t2, y).second(x.p, planes, x.H, x.W, x.ld, b.stride) : ConvCall(b.c3, t2, y).add(b.has_ds ? dsb.p : x.p, outc);
+        c3.act(ACT_RELU).f16(h16);
+        // where chains_into() says so, the conv3 launch also computes conv1 of the block behind it: into a map allocated behind this block's
+        // own output, as the planning run does
+        t1_chained = Map();
+        if (chains_into(c3, nb)) { t1_chained = act(x.N, ho, wo, nb->c1.Cout); c3.chain(nb->c1, t1_chained.p); }
+        conv(c3);
+        release(t2);
+        release(dsb);
+        return y;
+    }
+
+    // BasicBlock (resnet.py:90-106; the branches of an HRNet module): -> its output map; the caller releases `x`.  ds: the downsample
+    // conv, or null.  fill: conv1 and conv2 also write the zero pad channels of their maps (channel counts that are no multiple of 4)
+    Map basic_block(const Layer &c1, const Layer &c2, const Layer *ds, int stride, const Map &x, bool fill) {
+        const int outc = c1.rd_cout ? c1.rd_cout : c1.Cout;
+        Map t1 = act(x.N, conv_out(x.H, 3, stride, 1), conv_out(x.W, 3, stride, 1), outc);
+        conv(ConvCall(c1, x, t1).s(stride).pad(1).act(ACT_RELU).f16(h16).filled(fill));
+        Map dsb;
+        if (ds) {
+            dsb = act(x.N, t1.H, t1.W, outc);
+            conv(ConvCall(*ds, x, dsb).s(stride).f16(h16));
+        }
+        Map y = act(x.N, t1.H, t1.W, outc);
+        conv(ConvCall(c2, t1, y).pad(1).add(ds ? dsb.p : x.p, y.ld).act(ACT_RELU).f16(h16).filled(fill));
+        release(t1);
+        release(dsb);
+        return y;
+    }
+
+    // The first n of a chain of stride-2 3x3 convs (+ BN + ReLU) from `src` on, each into a map of its own: -> the last one (n = 0: no map)
+    Map down_chain(const std::vector<Layer> &ls, size_t n, Map src) {
+        Map tmp;
+        for (size_t q = 0; q < n; ++q) {
+            Map o = act(src.N, conv_out(src.H, 3, 2, 1), conv_out(src.W, 3, 2, 1), ls[q].Cout);
+            conv(ConvCall(ls[q], src, o).s(2).pad(1).act(ACT_RELU).f16(h16).filled());
+            release(tmp);
+            tmp = src = o;
+        }
+        return tmp;
+    }
+
+    // feats[0] as fp32 NCHW into the capture buffer
+    void capture_feat0(const Map &f) {
+        if (!h->capture || dry || !h->cap_feat0) return;
+        if (split) LAUNCH(launch_nhwc_split_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
+        else if (h16) LAUNCH(launch_nhwc_f16_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
+        else LAUNCH(launch_nhwc_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s, f.ld));
+    }
+
+    // HighResolutionNet.forward (hrnet.py:357-393) and pose_net on its highest-resolution branch
+    Features hrnet_backbone(int N, const float *x) {
+        const HrNet &hr = h->hr;
+        const int H = h->cfg.height, W = h->cfg.width;
+        Map in4 = act(N, H, W, 3, h16 ? 8 : 4);   // 4 fp32 / 8 fp16 / [hi8 | lo8] per pixel
+        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4.p, s));
+        else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4.p, N, H, W, s, h->sat));
+        else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4.p, N, H, W, s));
+        else LAUNCH(launch_nchw_to_nhwc4(x, in4.p, N, H, W, s));
+        Map c1 = act(N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), 64);
+        conv(ConvCall(hr.conv1, in4, c1).s(2).pad(1).act(ACT_RELU).f16(h16));
+        release(in4);
+        Map cur = act(N, conv_out(c1.H, 3, 2, 1), conv_out(c1.W, 3, 2, 1), 64);
+        conv(ConvCall(hr.conv2, c1, cur).s(2).pad(1).act(ACT_RELU).f16(h16));
+        release(c1);
+        Map t1_chained;
+        for (size_t bi = 0; bi < hr.layer1.size(); ++bi) {   // 4 Bottlenecks, planes 64 -> 256 channels
+            Map y = bottleneck(hr.layer1[bi], cur, bi + 1 < hr.layer1.size() ? &hr.layer1[bi + 1] : nullptr, t1_chained);
+            release(cur);
+            cur = y;
+        }
+        Map xs[4], pre[4] = {cur};
+        int npre = 1;
+        for (int st = 0; st < 3; ++st) {
+            const int nbr = st + 2;
+            for (int i = 0; i < nbr; ++i) {   // transition layers (hrnet.py:287-311, 368-390)
+                if (i >= npre) {   // a new, lower-resolution branch from the LAST previous branch
+                    xs[i] = down_chain(hr.trans[st][i], hr.trans[st][i].size(), pre[npre - 1]);
+                } else if (!hr.trans[st][i].empty()) {
+                    xs[i] = act(N, pre[i].H, pre[i].W, hr.ch[i]);
+                    conv(ConvCall(hr.trans[st][i][0], pre[i], xs[i]).pad(1).act(ACT_RELU).f16(h16).filled());
+                } else {
+                    xs[i] = pre[i];   // x_list.append(y_list[i]): the same tensor
+                }
+            }
+            for (int i = 0; i < npre; ++i)
+                if (xs[i].p != pre[i].p) release(pre[i]);
+            for (const HrModule &M : hr.stage[st]) {   // HighResolutionModule.forward (hrnet.py:194-212)
+                // Four branches: the lowest-resolution one (320 / 512 channels on 1/32-size maps: a few hundred small tiles per conv, bound
+                // by request latency) runs on the second stream BESIDE the branch above it (one round of 256 x 192 tiles, latency-bound too):
+                // their workgroups share the CUs.  The two highest-resolution branches own the chip with persistent kernels and stay alone.
+                const bool overlap = h->hr_overlap && h16 && nbr == 4 && (dry || h->aux != nullptr);
+                for (int b = 0; b < nbr; ++b) {
+                    if (overlap && b == 2) fork();
+                    const hipStream_t main_s = s;
+                    if (overlap && b == 3) s = h->aux;
+                    for (int blk = 0; blk < 4; ++blk) {
+                        Map y = basic_block(M.br[b][blk][0], M.br[b][blk][1], nullptr, 1, xs[b], /*fill=*/true);
+                        release(xs[b]);
+                        xs[b] = y;
+                    }
+                    s = main_s;
+                    if (overlap && b == 3) join();
+                }
+                // fuse: y_i = relu(sum_j f_ij(x_j)).  Every non-identity term is a conv at branch i's resolution whose
+                // epilogue adds the running sum (the identity term x_i rides along as the first residual); the
+                // "1x1 conv + BN + nearest upsample" terms run the 1x1 conv on the up-sampled index map instead.
+                Map outs[4];
+                for (int i = 0; i < nbr; ++i) {
+                    const Map &xi = xs[i];
+                    Map running;
+                    int nterm = 0;
+                    // two or more up-sampling terms (always the last of the sum): one launch for all of them (hr_fuse.hip)
+                    HrFuseParams fp{};
+                    bool fused = false;
+                    if (h->hr_fuse && !split && nbr - 1 - i >= 2) {
+                        fp.N = N; fp.H = xi.H; fp.W = xi.W; fp.C = xi.C; fp.ldc = xi.ld; fp.relu = 1; fp.f16 = h16 ? 1 : 0;
+                        for (int j = i + 1; j < nbr; ++j) {
+                            const Layer &l = h16 ? M.fup[i][j] : M.fuse[i][j][0];
+                            HrFuseSrc &S = fp.src[fp.nsrc++];
+                            S.w = l.w; S.bias = l.bias; S.C = xs[j].C; S.ld = xs[j].ld; S.ldw = l.Kpad; S.shift = j - i; S.H = xs[j].H; S.W = xs[j].W;
+                        }
+                        fused = fp.src[0].w != nullptr && hr_fuse_up_plan(fp);
+                    }
+                    for (int j = 0; j < nbr; ++j) {
+                        if (j == i) continue;
+                        if (fused && j > i) continue;
+                        const bool first = nterm == 0, last = nterm == nbr - 2;
+                        const float *res = first ? xi.p : running.p;
+                        const int term_act = last ? ACT_RELU : ACT_NONE;
+                        Map o = act(N, xi.H, xi.W, xi.C);
+                        if (j > i) {
+                            conv(ConvCall(M.fuse[i][j][0], xs[j].p, N, xs[j].H, xs[j].W, o.p, o.ld, o.H, o.W).add(res, o.ld).act(term_act).f16(h16).upsample(j - i).filled());
+                        } else {   // i - j stride-2 convs; the last one writes the term
+                            const std::vector<Layer> &ls = M.fuse[i][j];
+                            const Map tmp = down_chain(ls, ls.size() - 1, xs[j]);
+                            conv(ConvCall(ls.back(), tmp.p ? tmp : xs[j], o).s(2).pad(1).add(res, o.ld).act(term_act).f16(h16).filled());
+                            release(tmp);
+                        }
+                        if (!first) release(running);
+                        running = o;
+                        ++nterm;
+                    }
+                    if (fused) {
+                        Map o = act(N, xi.H, xi.W, xi.C);
+                        fp.base = running.p ? running.p : xi.p;
+                        fp.out = o.p;
+                        for (int q = 0; q < fp.nsrc; ++q) fp.src[q].x = xs[i + 1 + q].p;
+                        hr_fuse_up(fp, M.fuse[i][i + 1][0].label + "+up");
+                        release(running);
+                        running = o;
+                    }
+                    outs[i] = running;
+                }
+                for (int b = 0; b < nbr; ++b) { release(xs[b]); xs[b] = outs[b]; }
+            }
+            npre = nbr;
+            for (int i = 0; i < nbr; ++i) { pre[i] = xs[i]; xs[i] = Map(); }
+        }
+        Features f;
+        f.n = 4;
+        for (int i = 0; i < 4; ++i) f.lv[i] = pre[i];
+        capture_feat0(f.lv[0]);
+        // pose_net = Conv2d(C0, 21, 3, stride 2, padding 1) on the highest-resolution branch (handmvnet.py:51-57, 180)
+        f.hm = f32map(N, conv_out(f.lv[0].H, 3, 2, 1), conv_out(f.lv[0].W, 3, 2, 1), NJ, 32);
+        conv(ConvCall(h->pose0, f.lv[0], f.hm).s(2).pad(1));
+        return f;
+    }
+
+    // ResNet-18 / 34 / 50-paper (resnet.py:216-254) and their pose_net (handmvnet.py:70-86)
+    Features resnet_backbone(int N, const float *x) {
+        const int H = h->cfg.height, W = h->cfg.width;
+        // ---- stem: conv1 7x7 s2 + BN + ReLU, maxpool 3x3 s2 (resnet.py:218-221)
+        // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
+        const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
+        Map in4 = act(N, Hs, Ws, 12, h16 ? 16 : 12);
+        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4.p, s, /*s2d=*/true));
+        else LAUNCH(launch_nchw_to_s2d(x, in4.p, N, H, W, smode, s, h->sat));
+        const int H1 = conv_out(H, 7, 2, 3), W1 = conv_out(W, 7, 2, 3);   // == Hs, Ws
+        const int hp = conv_out(H1, 3, 2, 1), wp = conv_out(W1, 3, 2, 1);
+        // fp16, many frames: conv1 + BN + ReLU + maxpool as ONE launch (conv_hs.hip's pooled epilogue: the 64-channel conv map, 8x the
+        // pooled map's bytes, never reaches HBM).  Bit-identical to the two launches, so the choice may depend on the launch size
+        auto stem = [&](float *out) { return ConvCall(h->stem, in4.p, N, Hs, Ws, out, 64, H1, W1).pad(2).act(ACT_RELU).f16(h16); };
+        const bool stem_pool = h16 && !split && h->chain_fuse && conv_hs_supported(params(stem(nullptr).pooled(hp, wp)), route);
+        Map cur;
+        if (stem_pool) {
+            cur = act(N, hp, wp, 64);
+            conv(stem(cur.p).pooled(hp, wp));
+            release(in4);
+        } else {
+            Map c1 = act(N, H1, W1, 64);
+            conv(stem(c1.p));
+            release(in4);
+            cur = act(N, hp, wp, 64);
+            if (split) LAUNCH(launch_maxpool3s2_split(c1.p, cur.p, N, H1, W1, 64, hp, wp, s));
+            else if (h16) LAUNCH(launch_maxpool3s2_f16(c1.p, cur.p, N, H1, W1, 64, hp, wp, s));
+            else LAUNCH(launch_maxpool3s2(c1.p, cur.p, N, H1, W1, 64, hp, wp, s));
+            release(c1);
+        }
+
+        // ---- residual layers (resnet.py:223-239)
+        Map level[3], t1_chained;
+        for (int li = 0; li < 3; ++li) {
+            for (size_t bi = 0; bi < h->blocks[li].size(); ++bi) {
+                const Block &b = h->blocks[li][bi];
+                // the block behind this one (of this layer or the first of the next): its conv1 may ride on this block's conv3 launch
+                const Block *nb = bi + 1 < h->blocks[li].size() ? &h->blocks[li][bi + 1] : (li + 1 < 3 && !h->blocks[li + 1].empty() ? &h->blocks[li + 1][0] : nullptr);
+                Map y = h->paper ? bottleneck(b, cur, nb, t1_chained) : basic_block(b.c1, b.c2, b.has_ds ? &b.ds : nullptr, b.stride, cur, /*fill=*/false);
+                bool keep = false;
+                for (int q = 0; q < 3; ++q) keep |= (level[q].p == cur.p);
+                if (!keep) release(cur);
+                cur = y;
+            }
+            // handmvnet.py:165-177: feats = [layer3, layer2, layer1][:n_levels]; keep only what is sampled
+            const bool needed = (li == 2) || (2 - li) < h->cfg.n_levels;
+            if (needed) level[li] = cur;
+        }
+        Features f;
+        for (int li = 2; li >= 0; --li)   // feats = [layer3, layer2, layer1]; only the kept levels are non-null
+            if (level[li].p) f.lv[f.n++] = level[li];
+        const Map &feat0 = f.lv[0];
+        capture_feat0(feat0);
+
+        // ---- pose_net (handmvnet.py:70-86, 180) -> channels-last heat map with row stride 32
+        if (h->paper) {
+            Map ph = act(N, feat0.H, feat0.W, 512);
+            conv(ConvCall(h->pose0, feat0, ph).act(ACT_RELU).f16(h16));
+            f.hm = f32map(N, feat0.H, feat0.W, NJ, 32);   // heat-map logits are ALWAYS fp32 (x1000 temperature)
+            conv(ConvCall(h->pose1, ph, f.hm));
+            release(ph);
+        } else {
+            const int fh = feat0.H, fw = feat0.W;
+            Map p0 = act(N, 2 * fh, 2 * fw, 128);
+            if (h->deconv_all.w)
+                conv(ConvCall(h->deconv_all, feat0.p, N, fh, fw, p0.p, 128, fh, fw).pad(1).act(ACT_RELU).f16(h16).all_phases(4, h->deconv_stride));
+            else
+                for (int a = 0; a < 2; ++a)
+                    for (int b = 0; b < 2; ++b)
+                        conv(ConvCall(h->deconv[a * 2 + b], feat0.p, N, fh, fw, p0.p, 128, fh, fw).pad(1 - a, 1 - b).act(ACT_RELU).f16(h16).phase(a, b));
+            Map p1 = act(N, p0.H, p0.W, 64);
+            conv(ConvCall(h->pose1, p0, p1).pad(1).act(ACT_RELU).f16(h16));
+            release(p0);
+            f.hm = f32map(N, p0.H, p0.W, NJ, 32);
+            conv(ConvCall(h->pose2, p1, f.hm).pad(1));
+            release(p1);
+        }
+        return f;
+    }
+
+    // soft-argmax, SampleNet and the token rows (handmvnet.py:182-225): releases the backbone's maps, returns the tokens [N * 21][ldt].
+    // Xpairs: those rows once more as [hi ldt | lo ldt] halfs where the first fusion block's projection reads pairs, else left as it is (null)
+    float *tokens_stage(const Features &f, const float *bbox, const float *intr, float *crop_img, float *heatmap, float *&Xpairs) {
+        const hmv_config &c = h->cfg;
+        const int N = f.hm.N, V = c.num_views, d = h->d, ldt = h->ldt;
+        // ---- soft-argmax (handmvnet.py:182, 252)
+        float *coords = alloc((size_t)N * NJ * 2);
+        LAUNCH(launch_soft_argmax(f.hm.p, f.hm.ld, N, f.hm.H, f.hm.W, coords, crop_img, (float)c.image_size, (float)c.heatmap_size, heatmap, s));
+        release(f.hm);
+        if (h->capture && !dry && h->cap_coords)
+            LAUNCH(hipMemcpyAsync(h->cap_coords, coords, (size_t)N * NJ * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+
+        // ---- sample nets as gather -> conv1x1+BN+ReLU -> bilinear blend (nets.py:46-63; handmvnet.py:185-187)
+        float *tokens = alloc((size_t)N * NJ * ldt);
+        int col0 = 0;
+        for (int i = 0; i < c.n_levels; ++i) {
+            const Map &lv = f.lv[i];
+            const int Ci = lv.ld, co = lv.C / 2;   // gather the (padded) channel rows; the conv's pad weights are zero
+            float *g = alloc(ACT((size_t)N * NJ * 4 * Ci));
+            // a split row is Ci (hi, lo) pairs = Ci 4-byte elements, like fp32
+            LAUNCH(launch_sample_gather(lv.p, N, lv.H, lv.W, Ci, coords, g, s, (h16 && !split) ? 2 : 4));
+            float *s4 = alloc((size_t)N * NJ * 4 * co);
+            gemm(h->sample[i], g, N * NJ * 4, s4, co, nullptr, 0, ACT_RELU);
+            release(g);
+            LAUNCH(launch_sample_blend(s4, co, co, N, lv.H, lv.W, coords, tokens, ldt, col0, s));
+            release(s4);
+            col0 += co;
+        }
+        for (int i = 0; i < f.n; ++i) release(f.lv[i]);
+        // pos2d / FoV / zero pad / PE (handmvnet.py:189-225; fusion.py:27-28).  In the fp16-kernel modes the q/k/v projections of
+        // CrossAttentionFusion read their token rows as (hi, lo) fp16 pairs: the kernel that produces a block's input rows -- this one for
+        // block 0, ff_block_kernel for the others -- writes that copy itself (rows_f32_to_half's arithmetic, one launch less per block)
+        if (!h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = alloc((size_t)N * NJ * ldt);
+        LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc,
+                                      (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe,   // the learnable-query blocks add their own PE
+                                      (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
+        release(coords);
+        return tokens;
+    }
+
+    // CrossAttentionFusionLearnableQuery (fusion.py:33-49; MultiHeadAttentionLearnableQuery layers.py:273-301): token rows X [B * Tcur][ldt]
+    // in (released), the fused rows out; Tcur follows
+    float *fusion_learnable_query(int B, float *X, int &Tcur) {
+        const int d = h->d, ldt = h->ldt;
+        for (int l = 0; l < 5; ++l) {
+            const AttnLayer &a = h->attn[l];
+            const bool cross = l == 2;
+            const int rows = B * Tcur, Tq = cross ? NJ : Tcur, qrows = B * Tq;
+            float *xp = alloc((size_t)rows * ldt);                       // x = self.pos_embed(x)
+            LAUNCH(launch_add_pe(X, ldt, rows, Tcur, d, h->pe, xp, ldt, s));
+            release(X);
+            float *att = alloc((size_t)qrows * INNER_LQ);
+            const bool tx3 = a.out_x3.plane != 0 && ff_fusable(a, qrows, true);   // attention rows as (hi, lo) pairs
+            if (cross) {
+                float *kv = alloc((size_t)rows * 2 * INNER_LQ);
+                project(a.kv, xp, rows, kv, 2 * INNER_LQ);
+                LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                release(kv);
+            } else {
+                float *qkv = alloc((size_t)rows * 3 * INNER_LQ);
+                project(a.qkv, xp, rows, qkv, 3 * INNER_LQ);
+                LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                release(qkv);
+            }
+            if (ff_fusable(a, qrows, tx3)) {
+                // out = to_out(att) (+ x, not in the probe block); out = ff(out) + out: no LayerNorm around the attention, the
+                // FeedForward keeps its own; pad columns come out as zeros
+                float *Xf = alloc((size_t)qrows * ldt);
+                ff_block(a, att, qrows, cross ? nullptr : xp, 0, 0, Xf, nullptr, tx3);
+                release(att);
+                release(xp);
+                X = Xf;
+                Tcur = Tq;
+                continue;
+            }
+            float *o = alloc((size_t)qrows * ldt);
+            if (cross) gemm(a.out, att, qrows, o, ldt, nullptr, 0, ACT_NONE);   // out = to_out(att); no residual from the tokens
+            else gemm(a.out, att, qrows, o, ldt, xp, ldt, ACT_NONE);            // out = to_out(att) + x
+            release(att);
+            release(xp);
+            float *f0 = alloc((size_t)qrows * ldt);
+            LAUNCH(launch_layernorm(o, ldt, qrows, d, a.fg, a.fb, f0, ldt, nullptr, nullptr, nullptr, s));
+            float *f1 = alloc((size_t)qrows * DHEAD_LQ);
+            gemm(a.ff1, f0, qrows, f1, DHEAD_LQ, nullptr, 0, ACT_GELU);
+            release(f0);
+            float *Xn = alloc((size_t)qrows * ldt);
+            gemm(a.ff2, f1, qrows, Xn, ldt, o, ldt, ACT_NONE);          // out = ff(out) + out
+            release(f1);
+            release(o);
+            // The decoder's GEMM reads all ldt columns of the last block's output (its weights are zero there, but 0 * NaN is NaN)
+            // and no epilogue writes them: a GEMM epilogue stops at round4(d), the split-K reduction at d.  Inner blocks go
+            // through add_pe, which writes the pad itself.
+            if (l == 4 && ldt > d) LAUNCH(hipMemset2DAsync(Xn + d, (size_t)ldt * sizeof(float), 0, (size_t)(ldt - d) * sizeof(float), (size_t)qrows, s));
+            X = Xn;
+            Tcur = Tq;
+        }
+        return X;
+    }
+
+    // CrossAttentionFusion (fusion.py:7-30; layers.py:202-237): as above; Xpairs: the (hi, lo) pair copy of X where tokens_stage wrote one
+    float *fusion_cross_attn(int B, float *X, float *Xpairs, int &Tcur) {
+        const hmv_config &c = h->cfg;
+        const int d = h->d, ldt = h->ldt;
+        const int half = (c.fusion_layers - 1) / 2;
+        for (int l = 0; l < c.fusion_layers; ++l) {
+            const AttnLayer &a = h->attn[l];
+            const bool cross = (l == half);
+            const int Tq = cross ? NJ : Tcur, koff = cross ? NJ : 0, Tk = cross ? Tcur - NJ : Tcur;
+            const int rows = B * Tcur, qrows = B * Tq;
+#ifdef HMV_NO_ATT_X3   // A/B builds only (python -m handmvnet_amd.build --variant noax HMV_NO_ATT_X3): the exact-fp32 attention in every mode
+            const int att_x3 = 0;
+#else
+            // fp16-kernel modes: the projection writes q, k, v as (hi, lo) pairs and the attention multiplies on the fp16 matrix cores (by the
+            // arithmetic mode alone: a sample's result never depends on the batch)
+            const int att_x3 = (h16 && a.qkv.plane) ? 1 : 0;
+#endif
+            float *qkv = alloc((size_t)rows * 3 * INNER);
+            project(a.qkv, X, rows, qkv, 3 * INNER, Xpairs, att_x3 != 0);
+            Xpairs = nullptr;
+            float *att = alloc((size_t)qrows * INNER);
+            // fp16-kernel modes, fused tail: the attention rows leave the kernel as (hi, lo) pairs and to_out is a split-pair GEMM
+            const bool tx3 = a.out_x3.plane != 0 && ff_fusable(a, qrows, true);
+            if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
+            else LAUNCH(hipMemsetAsync(att, 0, (size_t)qrows * INNER * sizeof(float), s));   // (zero rows are zero pairs)
+            release(qkv);
+            if (ff_fusable(a, qrows, tx3)) {   // norm1(to_out + _q) -> FeedForward -> norm2 in one launch behind the GEMM
+                float *Xf = alloc((size_t)qrows * ldt);
+                if (l + 1 < c.fusion_layers && h->attn[l + 1].qkv.plane) Xpairs = alloc((size_t)qrows * ldt);   // the next block's projection input
+                ff_block(a, att, qrows, X, cross ? Tq : 0, cross ? Tcur : 0, Xf, Xpairs, tx3);
+                release(att);
+                release(X);
+                X = Xf;
+                Tcur = Tq;
+                continue;
+            }
+            float *n1 = alloc((size_t)qrows * ldt), *f0 = alloc((size_t)qrows * ldt);
+            gemm_ln(a.out, att, qrows, X, ldt, cross ? Tq : 0, cross ? Tcur : 0, a.n1g, a.n1b, n1, ldt, a.fg, a.fb, f0);  // norm1(to_out + _q), ff LN
+            release(att);
+            float *f1 = alloc((size_t)qrows * DHEAD);
+            gemm(a.ff1, f0, qrows, f1, DHEAD, nullptr, 0, ACT_GELU);
+            release(f0);
+            float *f2 = alloc((size_t)qrows * ldt);
+            gemm(a.ff2, f1, qrows, f2, ldt, n1, ldt, ACT_NONE);
+            release(f1);
+            float *Xn = alloc((size_t)qrows * ldt);
+            LAUNCH(launch_layernorm(f2, ldt, qrows, d, a.n2g, a.n2b, Xn, ldt, nullptr, nullptr, nullptr, s));
+            release(f2);
+            release(n1);
+            release(X);
+            X = Xn;
+            Tcur = Tq;
+        }
+        return X;
+    }
+
+    // decoder (nets.py:133-139 / 150-154): the fused rows X [B * 21][ldt] (released) -> joints_cam [B * 21][3]
+    void decoder(int B, float *X, float *joints_cam) {
+        const hmv_config &c = h->cfg;
+        const int d = h->d, ldt = h->ldt, jr = B * NJ;
+        if (c.decoder == HMV_DECODER_GCN && h->cheb_fuse && h->gcn[0].Kpad == ldt &&
+            cheb_fusable(ldt, ldt, h->gcn[0].Kpad, 256, h->gcn[1].Kpad, 64, h->gcn[2].Kpad, 3)) {
+            // the three ChebConv layers in two launches (fusion_kernels.hip): layer 1 per (sample, 16 channels), layers 2 + 3 per sample
+            float *scr = alloc((size_t)jr * 256);
+            launch("cheb_fused", [&] {
+                ChebFusedParams p{};
+                p.x = X; p.ldx = ldt; p.B = B; p.K = ldt;
+                p.w1 = h->gcn[0].w; p.ldw1 = h->gcn[0].Kpad; p.c1 = 256; p.bias1 = h->gcn_bias[0];
+                p.w2 = h->gcn[1].w; p.ldw2 = h->gcn[1].Kpad; p.c2 = 64; p.bias2 = h->gcn_bias[1];
+                p.w3 = h->gcn[2].w; p.ldw3 = h->gcn[2].Kpad; p.c3 = 3; p.bias3 = h->gcn_bias[2];
+                p.tk = h->cheb_t; p.scratch = scr; p.out = joints_cam; p.ldo = 3;
+                return launch_cheb_fused(p, s);
+            }, 2);
+            release(X);
+            release(scr);
+        } else if (c.decoder == HMV_DECODER_GCN) {
+            const int dims[4] = {d, 256, 64, 3};
+            float *xin = X;
+            for (int i = 0; i < 3; ++i) {
+                const int co = dims[i + 1];
+                float *y = alloc((size_t)jr * 3 * co);
+                gemm(h->gcn[i], xin, jr, y, 3 * co, nullptr, 0, ACT_NONE);
+                release(xin);
+                float *out = i == 2 ? joints_cam : alloc((size_t)jr * co);
+                LAUNCH(launch_cheb_mix(y, 3 * co, B, co, h->cheb_t, h->gcn_bias[i], i < 2, out, i == 2 ? 3 : co, s));
+                release(y);
+                xin = i == 2 ? nullptr : out;
+            }
+        } else {
+            float *g1 = alloc((size_t)jr * 64);
+            gemm(h->fc1, X, jr, g1, 64, nullptr, 0, ACT_LEAKY);
+            release(X);
+            gemm(h->fc2, g1, jr, joints_cam, 3, nullptr, 0, ACT_NONE);
+            release(g1);
+        }
+    }
+};
+#undef LAUNCH
+
+// HandMvNet.forward (handmvnet.py:158-266), stage by stage; a planning run (dry) issues the same alloc / release sequence and launches nothing
 int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const float *intr, float *crop_img, float *joints_cam,
                 float *heatmap, hipStream_t s, bool dry, Arena &A) {
     Runner R{h, s, dry, HMV_OK, A};
@@ -1474,539 +1996,14 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
             hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
             return h->fail(HMV_ERR_HIP, "second stream for the HRNet branches");
     }
-    const int V = c.num_views, N = B * V, H = c.height, W = c.width;
-    const int d = h->d, ldt = h->ldt;
-    // fp16 path: the conv stack (stem .. pose_net / sample convs) stores activations as fp16; heat-map logits,
-    // coordinates, tokens, fusion and decoder stay fp32.  ACT(n) = arena floats for n activation elements.
-    const bool h16 = c.dtype != HMV_F32;      // the conv stack runs on the fp16 kernels ...
-    const bool split = c.dtype == HMV_F32X3;  // ... on (hi, lo) pairs: 4 bytes per element like fp32
-#define ACT(n) ((h16 && !split) ? ((size_t)(n) + 1) / 2 : (size_t)(n))
-#define LAUNCH(expr) R.launch(#expr, [&] { return (expr); })
-    // conv3 of a Bottleneck (+ residual or second source, + ReLU); where chains_into() says so, the same launch also computes conv1 of the
-    // block behind it, `nb`: returns that conv1's output (allocated behind the block's own output, as the planning run does), else null
-    auto conv3 = [&](ConvCall c3, const Block *nb) -> float * {
-        float *t1 = nullptr;
-        if (R.chains_into(c3, nb)) { t1 = R.alloc(ACT((size_t)c3.N * c3.Ho * c3.Wo * nb->c1.Cout)); c3.chain(nb->c1, t1); }
-        R.conv(c3);
-        return t1;
-    };
-
-    // sampled feature levels in the reference's feats[] order (handmvnet.py:165-177), channels-last with row stride ld
-    float *lvl[4] = {nullptr, nullptr, nullptr, nullptr};
-    int lvc[4] = {0, 0, 0, 0}, lvld[4] = {0, 0, 0, 0}, lvh[4] = {0, 0, 0, 0}, lvw[4] = {0, 0, 0, 0}, nkeep = 0;
-    int hmh = 0, hmw = 0;
-    float *hm = nullptr;
-    if (h->hrnet) {
-        // ================= HighResolutionNet.forward (hrnet.py:357-393) =================
-        const HrNet &hr = h->hr;
-        float *in4 = R.alloc((size_t)N * H * W * (split ? 8 : 4));
-        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4, s));
-        else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4, N, H, W, s, h->sat));
-        else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4, N, H, W, s));
-        else LAUNCH(launch_nchw_to_nhwc4(x, in4, N, H, W, s));
-        const int H1 = (H + 2 - 3) / 2 + 1, W1 = (W + 2 - 3) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
-        float *c1 = R.alloc(ACT((size_t)N * H1 * W1 * 64));
-        R.conv(ConvCall(hr.conv1, in4, N, H, W, c1, 64, H1, W1).s(2).pad(1).act(ACT_RELU).f16(h16));
-        R.release(in4);
-        float *cur = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-        R.conv(ConvCall(hr.conv2, c1, N, H1, W1, cur, 64, H2, W2).s(2).pad(1).act(ACT_RELU).f16(h16));
-        R.release(c1);
-        float *t1_chained = nullptr;
-        for (size_t bi = 0; bi < hr.layer1.size(); ++bi) {   // 4 Bottlenecks, planes 64 -> 256 channels
-            const Block &b = hr.layer1[bi];
-            float *t1 = t1_chained;   // (conv_stream.hip chain, as in the ResNet loop below: the previous block's conv3 launch computed it)
-            t1_chained = nullptr;
-            if (!t1) {
-                t1 = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-                R.conv(ConvCall(b.c1, cur, N, H2, W2, t1, 64, H2, W2).act(ACT_RELU).f16(h16));
-            }
-            float *t2 = R.alloc(ACT((size_t)N * H2 * W2 * 64));
-            R.conv(ConvCall(b.c2, t1, N, H2, W2, t2, 64, H2, W2).pad(1).act(ACT_RELU).f16(h16));
-            R.release(t1);
-            const float *res = cur;
-            float *dsb = nullptr;
-            if (b.has_ds) {
-                dsb = R.alloc(ACT((size_t)N * H2 * W2 * 256));
-                R.conv(ConvCall(b.ds, cur, N, H2, W2, dsb, 256, H2, W2).f16(h16));
-                res = dsb;
-            }
-            float *y = R.alloc(ACT((size_t)N * H2 * W2 * 256));
-            const Block *nb = bi + 1 < hr.layer1.size() ? &hr.layer1[bi + 1] : nullptr;
-            t1_chained = conv3(ConvCall(b.c3, t2, N, H2, W2, y, 256, H2, W2).add(res, 256).act(ACT_RELU).f16(h16), nb);
-            R.release(t2);
-            R.release(dsb);
-            R.release(cur);
-            cur = y;
-        }
-        float *xs[4] = {nullptr, nullptr, nullptr, nullptr}, *pre[4] = {cur, nullptr, nullptr, nullptr};
-        int hs[4] = {0, 0, 0, 0}, ws[4] = {0, 0, 0, 0}, prec[4] = {256, 0, 0, 0}, preh[4] = {H2, 0, 0, 0}, prew[4] = {W2, 0, 0, 0};
-        int npre = 1;
-        for (int st = 0; st < 3; ++st) {
-            const int nbr = st + 2;
-            bool moved[4] = {false, false, false, false};
-            for (int i = 0; i < nbr; ++i) {   // transition layers (hrnet.py:287-311, 368-390)
-                const int cp = cpad(hr.ch[i]);
-                if (i < npre) {
-                    hs[i] = preh[i]; ws[i] = prew[i];
-                    if (!hr.trans[st][i].empty()) {
-                        xs[i] = R.alloc(ACT((size_t)N * hs[i] * ws[i] * cp));
-                        R.conv(ConvCall(hr.trans[st][i][0], pre[i], N, preh[i], prew[i], xs[i], cp, hs[i], ws[i]).pad(1).act(ACT_RELU).f16(h16).filled());
-                    } else {
-                        xs[i] = pre[i];   // x_list.append(y_list[i]): the same tensor
-                        moved[i] = true;
-                    }
-                } else {   // a new, lower-resolution branch from the LAST previous branch
-                    const float *src = pre[npre - 1];
-                    float *tmp = nullptr;
-                    int hh_ = preh[npre - 1], ww_ = prew[npre - 1];
-                    for (const Layer &l : hr.trans[st][i]) {
-                        const int ho = (hh_ + 2 - 3) / 2 + 1, wo = (ww_ + 2 - 3) / 2 + 1, cpo = cpad(l.Cout);
-                        float *o = R.alloc(ACT((size_t)N * ho * wo * cpo));
-                        R.conv(ConvCall(l, src, N, hh_, ww_, o, cpo, ho, wo).s(2).pad(1).act(ACT_RELU).f16(h16).filled());
-                        R.release(tmp);
-                        tmp = o; src = o; hh_ = ho; ww_ = wo;
-                    }
-                    xs[i] = tmp; hs[i] = hh_; ws[i] = ww_;
-                }
-            }
-            for (int i = 0; i < npre; ++i)
-                if (!moved[i]) R.release(pre[i]);
-            for (const HrModule &M : hr.stage[st]) {   // HighResolutionModule.forward (hrnet.py:194-212)
-                // Four branches: the lowest-resolution one (320 / 512 channels on 1/32-size maps: a few hundred small tiles per conv, bound
-                // by request latency) runs on the second stream BESIDE the branch above it (one round of 256 x 192 tiles, latency-bound too):
-                // their workgroups share the CUs.  The two highest-resolution branches own the chip with persistent kernels and stay alone.
-                const bool overlap = h->hr_overlap && h16 && nbr == 4 && (dry || h->aux != nullptr);
-                for (int b = 0; b < nbr; ++b) {
-                    const int cp = cpad(hr.ch[b]);
-                    if (overlap && b == 2) R.fork();
-                    const hipStream_t main_s = R.s;
-                    if (overlap && b == 3) R.s = h->aux;
-                    for (int blk = 0; blk < 4; ++blk) {
-                        float *t = R.alloc(ACT((size_t)N * hs[b] * ws[b] * cp));
-                        R.conv(ConvCall(M.br[b][blk][0], xs[b], N, hs[b], ws[b], t, cp, hs[b], ws[b]).pad(1).act(ACT_RELU).f16(h16).filled());
-                        float *y = R.alloc(ACT((size_t)N * hs[b] * ws[b] * cp));
-                        R.conv(ConvCall(M.br[b][blk][1], t, N, hs[b], ws[b], y, cp, hs[b], ws[b]).pad(1).add(xs[b], cp).act(ACT_RELU).f16(h16).filled());
-                        R.release(t);
-                        R.release(xs[b]);
-                        xs[b] = y;
-                    }
-                    R.s = main_s;
-                    if (overlap && b == 3) R.join();
-                }
-                // fuse: y_i = relu(sum_j f_ij(x_j)).  Every non-identity term is a conv at branch i's resolution whose
-                // epilogue adds the running sum (the identity term x_i rides along as the first residual); the
-                // "1x1 conv + BN + nearest upsample" terms run the 1x1 conv on the up-sampled index map instead.
-                float *outs[4] = {nullptr, nullptr, nullptr, nullptr};
-                for (int i = 0; i < nbr; ++i) {
-                    const int cpi = cpad(hr.ch[i]);
-                    float *running = nullptr;
-                    int nterm = 0;
-                    // two or more up-sampling terms (always the last of the sum): one launch for all of them (hr_fuse.hip)
-                    HrFuseParams fp{};
-                    bool fused = false;
-                    if (h->hr_fuse && !split && nbr - 1 - i >= 2) {
-                        fp.N = N; fp.H = hs[i]; fp.W = ws[i]; fp.C = hr.ch[i]; fp.ldc = cpi; fp.relu = 1; fp.f16 = h16 ? 1 : 0;
-                        for (int j = i + 1; j < nbr; ++j) {
-                            const Layer &l = h16 ? M.fup[i][j] : M.fuse[i][j][0];
-                            HrFuseSrc &S = fp.src[fp.nsrc++];
-                            S.w = l.w; S.bias = l.bias; S.C = hr.ch[j]; S.ld = cpad(hr.ch[j]); S.ldw = l.Kpad; S.shift = j - i; S.H = hs[j]; S.W = ws[j];
-                        }
-                        fused = fp.src[0].w != nullptr && hr_fuse_up_plan(fp);
-                    }
-                    for (int j = 0; j < nbr; ++j) {
-                        if (j == i) continue;
-                        if (fused && j > i) continue;
-                        const bool first = nterm == 0, last = nterm == nbr - 2;
-                        const float *res = first ? xs[i] : running;
-                        const int act = last ? ACT_RELU : ACT_NONE;
-                        float *o = R.alloc(ACT((size_t)N * hs[i] * ws[i] * cpi));
-                        if (j > i) {
-                            R.conv(ConvCall(M.fuse[i][j][0], xs[j], N, hs[j], ws[j], o, cpi, hs[i], ws[i]).add(res, cpi).act(act).f16(h16).upsample(j - i).filled());
-                        } else {
-                            const float *src = xs[j];
-                            float *tmp = nullptr;
-                            int hh_ = hs[j], ww_ = ws[j];
-                            const int nq = i - j;
-                            for (int q = 0; q < nq; ++q) {
-                                const Layer &l = M.fuse[i][j][q];
-                                const int ho = (hh_ + 2 - 3) / 2 + 1, wo = (ww_ + 2 - 3) / 2 + 1;
-                                if (q == nq - 1) {
-                                    R.conv(ConvCall(l, src, N, hh_, ww_, o, cpi, ho, wo).s(2).pad(1).add(res, cpi).act(act).f16(h16).filled());
-                                } else {
-                                    const int cpo = cpad(l.Cout);
-                                    float *t = R.alloc(ACT((size_t)N * ho * wo * cpo));
-                                    R.conv(ConvCall(l, src, N, hh_, ww_, t, cpo, ho, wo).s(2).pad(1).act(ACT_RELU).f16(h16).filled());
-                                    R.release(tmp);
-                                    tmp = t; src = t;
-                                }
-                                hh_ = ho; ww_ = wo;
-                            }
-                            R.release(tmp);
-                        }
-                        if (!first) R.release(running);
-                        running = o;
-                        ++nterm;
-                    }
-                    if (fused) {
-                        float *o = R.alloc(ACT((size_t)N * hs[i] * ws[i] * cpi));
-                        fp.base = running ? running : xs[i];
-                        fp.out = o;
-                        for (int q = 0; q < fp.nsrc; ++q) fp.src[q].x = xs[i + 1 + q];
-                        R.hr_fuse_up(fp, M.fuse[i][i + 1][0].label + "+up");
-                        if (running) R.release(running);
-                        running = o;
-                    }
-                    outs[i] = running;
-                }
-                for (int b = 0; b < nbr; ++b) { R.release(xs[b]); xs[b] = outs[b]; }
-            }
-            npre = nbr;
-            for (int i = 0; i < nbr; ++i) { pre[i] = xs[i]; prec[i] = hr.ch[i]; preh[i] = hs[i]; prew[i] = ws[i]; xs[i] = nullptr; }
-        }
-        (void)prec;
-        nkeep = 4;
-        for (int i = 0; i < 4; ++i) { lvl[i] = pre[i]; lvc[i] = hr.ch[i]; lvld[i] = cpad(hr.ch[i]); lvh[i] = preh[i]; lvw[i] = prew[i]; }
-        if (h->capture && !dry && h->cap_feat0) {
-            if (split) LAUNCH(launch_nhwc_split_to_nchw(lvl[0], h->cap_feat0, N, lvh[0], lvw[0], lvc[0], s));
-            else if (h16) LAUNCH(launch_nhwc_f16_to_nchw(lvl[0], h->cap_feat0, N, lvh[0], lvw[0], lvc[0], s));
-            else LAUNCH(launch_nhwc_to_nchw(lvl[0], h->cap_feat0, N, lvh[0], lvw[0], lvc[0], s, lvld[0]));
-        }
-        // pose_net = Conv2d(C0, 21, 3, stride 2, padding 1) on the highest-resolution branch (handmvnet.py:51-57, 180)
-        hmh = (lvh[0] + 2 - 3) / 2 + 1; hmw = (lvw[0] + 2 - 3) / 2 + 1;
-        hm = R.alloc((size_t)N * hmh * hmw * 32);
-        R.conv(ConvCall(h->pose0, lvl[0], N, lvh[0], lvw[0], hm, 32, hmh, hmw).s(2).pad(1));
-    } else {
-    // ---- stem: conv1 7x7 s2 + BN + ReLU, maxpool 3x3 s2 (resnet.py:218-221)
-    // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
-    const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
-    float *in4 = R.alloc((size_t)N * Hs * Ws * (split ? 16 : (h16 ? 8 : 12)));
-    if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4, s, /*s2d=*/true));
-    else LAUNCH(launch_nchw_to_s2d(x, in4, N, H, W, smode, s, h->sat));
-    const int H1 = (H + 6 - 7) / 2 + 1, W1 = (W + 6 - 7) / 2 + 1;   // == Hs, Ws
-    int hh = (H1 + 2 - 3) / 2 + 1, ww = (W1 + 2 - 3) / 2 + 1, C = 64;
-    // fp16, many frames: conv1 + BN + ReLU + maxpool as ONE launch (conv_hs.hip's pooled epilogue: the 64-channel conv map, 8x the
-    // pooled map's bytes, never reaches HBM).  Bit-identical to the two launches, so the choice may depend on the launch size
-    auto stem = [&](float *out) { return ConvCall(h->stem, in4, N, Hs, Ws, out, 64, H1, W1).pad(2).act(ACT_RELU).f16(h16); };
-    const bool stem_pool = h16 && !split && h->chain_fuse && conv_hs_supported(R.params(stem(nullptr).pooled(hh, ww)), R.route);
-    float *cur;
-    if (stem_pool) {
-        cur = R.alloc(ACT((size_t)N * hh * ww * 64));
-        R.conv(stem(cur).pooled(hh, ww));
-        R.release(in4);
-    } else {
-        float *c1 = R.alloc(ACT((size_t)N * H1 * W1 * 64));
-        R.conv(stem(c1));
-        R.release(in4);
-        cur = R.alloc(ACT((size_t)N * hh * ww * 64));
-        if (split) LAUNCH(launch_maxpool3s2_split(c1, cur, N, H1, W1, 64, hh, ww, s));
-        else if (h16) LAUNCH(launch_maxpool3s2_f16(c1, cur, N, H1, W1, 64, hh, ww, s));
-        else LAUNCH(launch_maxpool3s2(c1, cur, N, H1, W1, 64, hh, ww, s));
-        R.release(c1);
-    }
-
-    // ---- residual layers (resnet.py:223-239; Bottleneck 124-144; BasicBlock 90-106)
-    float *level[3] = {nullptr, nullptr, nullptr};
-    int lc[3], lh[3], lw[3];
-    float *t1_chained = nullptr;
-    for (int li = 0; li < 3; ++li) {
-        for (size_t bi = 0; bi < h->blocks[li].size(); ++bi) {
-            const Block &b = h->blocks[li][bi];
-            const int ho = (hh + 2 - 3) / b.stride + 1, wo = (ww + 2 - 3) / b.stride + 1;
-            float *y;
-            int outc;
-            if (h->paper) {
-                const int planes = b.c1.Cout;
-                outc = b.c3.Cout;
-                float *t1 = t1_chained;   // conv1 + BN + ReLU of this block came out of the previous block's chained conv3 launch
-                t1_chained = nullptr;
-                if (!t1) {
-                    t1 = R.alloc(ACT((size_t)N * hh * ww * planes));
-                    R.conv(ConvCall(b.c1, cur, N, hh, ww, t1, planes, hh, ww).act(ACT_RELU).f16(h16));
-                }
-                float *t2 = R.alloc(ACT((size_t)N * ho * wo * planes));
-                R.conv(ConvCall(b.c2, t1, N, hh, ww, t2, planes, ho, wo).s(b.stride).pad(1).act(ACT_RELU).f16(h16));
-                R.release(t1);
-                // the block behind this one (of this layer or the first of the next): its conv1 may ride on this block's conv3 launch
-                const Block *nb = bi + 1 < h->blocks[li].size() ? &h->blocks[li][bi + 1] : (li + 1 < 3 && !h->blocks[li + 1].empty() ? &h->blocks[li + 1][0] : nullptr);
-                const float *res = cur;
-                float *dsb = nullptr;
-                if (b.fused_ds) {   // conv3 and the downsample branch as one GEMM over [t2 | x]
-                    // out = relu([t2 | x(strided)] . Wcat + b): BN3 and the downsample's BN are in Wcat and b
-                    y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    t1_chained = conv3(ConvCall(b.c3ds, t2, N, ho, wo, y, outc, ho, wo).second(cur, planes, hh, ww, C, b.stride).act(ACT_RELU).f16(h16), nb);
-                } else {
-                    if (b.has_ds) {
-                        dsb = R.alloc(ACT((size_t)N * ho * wo * outc));
-                        R.conv(ConvCall(b.ds, cur, N, hh, ww, dsb, outc, ho, wo).s(b.stride).f16(h16));
-                        res = dsb;
-                    }
-                    y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    t1_chained = conv3(ConvCall(b.c3, t2, N, ho, wo, y, outc, ho, wo).add(res, outc).act(ACT_RELU).f16(h16), nb);
-                }
-                R.release(t2);
-                R.release(dsb);
-            } else {
-                const int planes = b.c1.Cout;
-                outc = planes;
-                float *t1 = R.alloc(ACT((size_t)N * ho * wo * planes));
-                R.conv(ConvCall(b.c1, cur, N, hh, ww, t1, planes, ho, wo).s(b.stride).pad(1).act(ACT_RELU).f16(h16));
-                const float *res = cur;
-                float *dsb = nullptr;
-                if (b.has_ds) {
-                    dsb = R.alloc(ACT((size_t)N * ho * wo * outc));
-                    R.conv(ConvCall(b.ds, cur, N, hh, ww, dsb, outc, ho, wo).s(b.stride).f16(h16));
-                    res = dsb;
-                }
-                y = R.alloc(ACT((size_t)N * ho * wo * outc));
-                R.conv(ConvCall(b.c2, t1, N, ho, wo, y, outc, ho, wo).pad(1).add(res, outc).act(ACT_RELU).f16(h16));
-                R.release(t1);
-                R.release(dsb);
-            }
-            bool keep = false;
-            for (int q = 0; q < 3; ++q) keep |= (level[q] == cur);
-            if (!keep) R.release(cur);
-            cur = y; C = outc; hh = ho; ww = wo;
-        }
-        // handmvnet.py:165-177: feats = [layer3, layer2, layer1][:n_levels]; keep only what is sampled
-        const bool needed = (li == 2) || (2 - li) < c.n_levels;
-        lc[li] = C; lh[li] = hh; lw[li] = ww;
-        if (needed) level[li] = cur;
-    }
-    float *feat0 = level[2];
-    const int fh = lh[2], fw = lw[2];
-    if (h->capture && !dry && h->cap_feat0) {
-        if (split) LAUNCH(launch_nhwc_split_to_nchw(feat0, h->cap_feat0, N, fh, fw, lc[2], s));
-        else if (h16) LAUNCH(launch_nhwc_f16_to_nchw(feat0, h->cap_feat0, N, fh, fw, lc[2], s));
-        else LAUNCH(launch_nhwc_to_nchw(feat0, h->cap_feat0, N, fh, fw, lc[2], s));
-    }
-
-    // ---- pose_net (handmvnet.py:70-86, 180) -> channels-last heat map with row stride 32
-    if (h->paper) {
-        hmh = fh; hmw = fw;
-        float *ph = R.alloc(ACT((size_t)N * fh * fw * 512));
-        R.conv(ConvCall(h->pose0, feat0, N, fh, fw, ph, 512, fh, fw).act(ACT_RELU).f16(h16));
-        hm = R.alloc((size_t)N * hmh * hmw * 32);   // heat-map logits are ALWAYS fp32 (x1000 temperature)
-        R.conv(ConvCall(h->pose1, ph, N, fh, fw, hm, 32, fh, fw));
-        R.release(ph);
-    } else {
-        hmh = 2 * fh; hmw = 2 * fw;
-        float *p0 = R.alloc(ACT((size_t)N * hmh * hmw * 128));
-        if (h->deconv_all.w)
-            R.conv(ConvCall(h->deconv_all, feat0, N, fh, fw, p0, 128, fh, fw).pad(1).act(ACT_RELU).f16(h16).all_phases(4, h->deconv_stride));
-        else
-            for (int a = 0; a < 2; ++a)
-                for (int b = 0; b < 2; ++b)
-                    R.conv(ConvCall(h->deconv[a * 2 + b], feat0, N, fh, fw, p0, 128, fh, fw).pad(1 - a, 1 - b).act(ACT_RELU).f16(h16).phase(a, b));
-        float *p1 = R.alloc(ACT((size_t)N * hmh * hmw * 64));
-        R.conv(ConvCall(h->pose1, p0, N, hmh, hmw, p1, 64, hmh, hmw).pad(1).act(ACT_RELU).f16(h16));
-        R.release(p0);
-        hm = R.alloc((size_t)N * hmh * hmw * 32);
-        R.conv(ConvCall(h->pose2, p1, N, hmh, hmw, hm, 32, hmh, hmw).pad(1));
-        R.release(p1);
-    }
-    for (int i = 0; i < 3; ++i) {   // feats = [layer3, layer2, layer1]; only the kept levels are non-null
-        const int li = 2 - i;
-        if (!level[li]) continue;
-        lvl[nkeep] = level[li]; lvc[nkeep] = lc[li]; lvld[nkeep] = lc[li]; lvh[nkeep] = lh[li]; lvw[nkeep] = lw[li];
-        ++nkeep;
-    }
-    }   // resnet backbones
-    // ---- soft-argmax (handmvnet.py:182, 252)
-    float *coords = R.alloc((size_t)N * NJ * 2);
-    LAUNCH(launch_soft_argmax(hm, 32, N, hmh, hmw, coords, crop_img, (float)c.image_size, (float)c.heatmap_size, heatmap, s));
-    R.release(hm);
-    if (h->capture && !dry && h->cap_coords)
-        LAUNCH(hipMemcpyAsync(h->cap_coords, coords, (size_t)N * NJ * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-
-    // ---- sample nets as gather -> conv1x1+BN+ReLU -> bilinear blend (nets.py:46-63; handmvnet.py:185-187)
-    float *tokens = R.alloc((size_t)N * NJ * ldt);
-    int col0 = 0;
-    for (int i = 0; i < c.n_levels; ++i) {
-        const int Ci = lvld[i], co = lvc[i] / 2;   // gather the (padded) channel rows; the conv's pad weights are zero
-        float *g = R.alloc(ACT((size_t)N * NJ * 4 * Ci));
-        // a split row is Ci (hi, lo) pairs = Ci 4-byte elements, like fp32
-        LAUNCH(launch_sample_gather(lvl[i], N, lvh[i], lvw[i], Ci, coords, g, s, (h16 && !split) ? 2 : 4));
-        float *s4 = R.alloc((size_t)N * NJ * 4 * co);
-        R.gemm(h->sample[i], g, N * NJ * 4, s4, co, nullptr, 0, ACT_RELU);
-        R.release(g);
-        LAUNCH(launch_sample_blend(s4, co, co, N, lvh[i], lvw[i], coords, tokens, ldt, col0, s));
-        R.release(s4);
-        col0 += co;
-    }
-    for (int i = 0; i < nkeep; ++i) R.release(lvl[i]);
-    // pos2d / FoV / zero pad / PE (handmvnet.py:189-225; fusion.py:27-28).  In the fp16-kernel modes the q/k/v projections of
-    // CrossAttentionFusion read their token rows as (hi, lo) fp16 pairs: the kernel that produces a block's input rows -- this one for
-    // block 0, ff_block_kernel for the others -- writes that copy itself (rows_f32_to_half's arithmetic, one launch less per block)
-    float *Xpairs = nullptr;   // [hi ldt | lo ldt] halfs per row of X, when its producer wrote them
-    if (!h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = R.alloc((size_t)N * NJ * ldt);
-    LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc,
-                                  (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe,   // the learnable-query blocks add their own PE
-                                  (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
-    R.release(coords);
-
-    float *X = tokens;
-    int Tcur = V * NJ;
-    // q/k/v projection of fp32 token rows; in the fp16 / f32x3 modes on the fused split kernels (Loader::linear_x3)
-    // pairs_out: the result rows as (hi, lo) fp16 pairs [hi ldc | lo ldc] (the GEMM's pair epilogue; same bytes as fp32 rows) for a consumer
-    // that multiplies on the fp16 matrix cores (attention_x3_kernel)
-    auto project = [&](const Layer &L, const float *a, int rows, float *out, int ldc, float *ready_pairs = nullptr, bool pairs_out = false) {
-        if (!L.plane) { R.gemm(L, a, rows, out, ldc, nullptr, 0, ACT_NONE); return; }
-        float *pairs = ready_pairs;
-        if (!pairs) {
-            pairs = R.alloc((size_t)rows * ldt);                           // [hi ldt | lo ldt] halfs per row
-            LAUNCH(launch_rows_f32_to_half(a, pairs, (size_t)rows, ldt, 2, s, h->sat));
-        }
-        R.conv(ConvCall(L, pairs, rows, 1, 1, out, ldc, 1, 1).f16(pairs_out));
-        R.release(pairs);
-    };
-    if (h->lq) {
-        // ---- CrossAttentionFusionLearnableQuery (fusion.py:33-49; MultiHeadAttentionLearnableQuery layers.py:273-301)
-        for (int l = 0; l < 5; ++l) {
-            const AttnLayer &a = h->attn[l];
-            const bool cross = l == 2;
-            const int rows = B * Tcur, Tq = cross ? NJ : Tcur, qrows = B * Tq;
-            float *xp = R.alloc((size_t)rows * ldt);                       // x = self.pos_embed(x)
-            LAUNCH(launch_add_pe(X, ldt, rows, Tcur, d, h->pe, xp, ldt, s));
-            R.release(X);
-            float *att = R.alloc((size_t)qrows * INNER_LQ);
-            const bool tx3 = a.out_x3.plane != 0 && R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, true);   // attention rows as (hi, lo) pairs
-            if (cross) {
-                float *kv = R.alloc((size_t)rows * 2 * INNER_LQ);
-                project(a.kv, xp, rows, kv, 2 * INNER_LQ);
-                LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
-                R.release(kv);
-            } else {
-                float *qkv = R.alloc((size_t)rows * 3 * INNER_LQ);
-                project(a.qkv, xp, rows, qkv, 3 * INNER_LQ);
-                LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
-                R.release(qkv);
-            }
-            if (R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, tx3)) {
-                // out = to_out(att) (+ x, not in the probe block); out = ff(out) + out: no LayerNorm around the attention, the
-                // FeedForward keeps its own; pad columns come out as zeros
-                float *Xf = R.alloc((size_t)qrows * ldt);
-                R.ff_block(a.out, a.ff1, a.ff2, att, qrows, cross ? nullptr : xp, ldt, 0, 0, nullptr, nullptr, a.fg, a.fb, nullptr, nullptr,
-                           Xf, ldt, d, nullptr, tx3 ? &a.out_x3 : nullptr);
-                R.release(att);
-                R.release(xp);
-                X = Xf;
-                Tcur = Tq;
-                continue;
-            }
-            float *o = R.alloc((size_t)qrows * ldt);
-            if (cross) R.gemm(a.out, att, qrows, o, ldt, nullptr, 0, ACT_NONE);   // out = to_out(att); no residual from the tokens
-            else R.gemm(a.out, att, qrows, o, ldt, xp, ldt, ACT_NONE);            // out = to_out(att) + x
-            R.release(att);
-            R.release(xp);
-            float *f0 = R.alloc((size_t)qrows * ldt);
-            LAUNCH(launch_layernorm(o, ldt, qrows, d, a.fg, a.fb, f0, ldt, nullptr, nullptr, nullptr, s));
-            float *f1 = R.alloc((size_t)qrows * DHEAD_LQ);
-            R.gemm(a.ff1, f0, qrows, f1, DHEAD_LQ, nullptr, 0, ACT_GELU);
-            R.release(f0);
-            float *Xn = R.alloc((size_t)qrows * ldt);
-            R.gemm(a.ff2, f1, qrows, Xn, ldt, o, ldt, ACT_NONE);          // out = ff(out) + out
-            R.release(f1);
-            R.release(o);
-            // The decoder's GEMM reads all ldt columns of the last block's output (its weights are zero there, but 0 * NaN is NaN)
-            // and no epilogue writes them: a GEMM epilogue stops at round4(d), the split-K reduction at d.  Inner blocks go
-            // through add_pe, which writes the pad itself.
-            if (l == 4 && ldt > d) LAUNCH(hipMemset2DAsync(Xn + d, (size_t)ldt * sizeof(float), 0, (size_t)(ldt - d) * sizeof(float), (size_t)qrows, s));
-            X = Xn;
-            Tcur = Tq;
-        }
-    }
-    // ---- CrossAttentionFusion (fusion.py:7-30; layers.py:202-237)
-    const int half = (c.fusion_layers - 1) / 2;
-    for (int l = 0; l < (h->lq ? 0 : c.fusion_layers); ++l) {
-        const AttnLayer &a = h->attn[l];
-        const bool cross = (l == half);
-        const int Tq = cross ? NJ : Tcur, koff = cross ? NJ : 0, Tk = cross ? Tcur - NJ : Tcur;
-        const int rows = B * Tcur, qrows = B * Tq;
-#ifdef HMV_NO_ATT_X3   // A/B builds only (python -m handmvnet_amd.build --variant noax HMV_NO_ATT_X3): the exact-fp32 attention in every mode
-        const int att_x3 = 0;
-#else
-        // fp16-kernel modes: the projection writes q, k, v as (hi, lo) pairs and the attention multiplies on the fp16 matrix cores (by the
-        // arithmetic mode alone: a sample's result never depends on the batch)
-        const int att_x3 = (h16 && a.qkv.plane) ? 1 : 0;
-#endif
-        float *qkv = R.alloc((size_t)rows * 3 * INNER);
-        project(a.qkv, X, rows, qkv, 3 * INNER, Xpairs, att_x3 != 0);
-        Xpairs = nullptr;
-        float *att = R.alloc((size_t)qrows * INNER);
-        // fp16-kernel modes, fused tail: the attention rows leave the kernel as (hi, lo) pairs and to_out is a split-pair GEMM
-        const bool tx3 = a.out_x3.plane != 0 && R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, true);
-        if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
-        else LAUNCH(hipMemsetAsync(att, 0, (size_t)qrows * INNER * sizeof(float), s));   // (zero rows are zero pairs)
-        R.release(qkv);
-        if (R.ff_fusable(a.out, a.ff1, a.ff2, qrows, ldt, tx3)) {   // norm1(to_out + _q) -> FeedForward -> norm2 in one launch behind the GEMM
-            float *Xf = R.alloc((size_t)qrows * ldt);
-            if (l + 1 < c.fusion_layers && h->attn[l + 1].qkv.plane) Xpairs = R.alloc((size_t)qrows * ldt);   // the next block's projection input
-            R.ff_block(a.out, a.ff1, a.ff2, att, qrows, X, ldt, cross ? Tq : 0, cross ? Tcur : 0, a.n1g, a.n1b, a.fg, a.fb, a.n2g, a.n2b, Xf,
-                       ldt, d, Xpairs, tx3 ? &a.out_x3 : nullptr);
-            R.release(att);
-            R.release(X);
-            X = Xf;
-            Tcur = Tq;
-            continue;
-        }
-        float *n1 = R.alloc((size_t)qrows * ldt), *f0 = R.alloc((size_t)qrows * ldt);
-        R.gemm_ln(a.out, att, qrows, X, ldt, cross ? Tq : 0, cross ? Tcur : 0, a.n1g, a.n1b, n1, ldt, a.fg, a.fb, f0);  // norm1(to_out + _q), ff LN
-        R.release(att);
-        float *f1 = R.alloc((size_t)qrows * DHEAD);
-        R.gemm(a.ff1, f0, qrows, f1, DHEAD, nullptr, 0, ACT_GELU);
-        R.release(f0);
-        float *f2 = R.alloc((size_t)qrows * ldt);
-        R.gemm(a.ff2, f1, qrows, f2, ldt, n1, ldt, ACT_NONE);
-        R.release(f1);
-        float *Xn = R.alloc((size_t)qrows * ldt);
-        LAUNCH(launch_layernorm(f2, ldt, qrows, d, a.n2g, a.n2b, Xn, ldt, nullptr, nullptr, nullptr, s));
-        R.release(f2);
-        R.release(n1);
-        R.release(X);
-        X = Xn;
-        Tcur = Tq;
-    }
-    if (h->capture && !dry && h->cap_fused) LAUNCH(launch_copy_rows(X, ldt, h->cap_fused, d, B * Tcur, d, s));
-
-    // ---- decoder (nets.py:133-139 / 150-154)
-    const int jr = B * NJ;
-    if (c.decoder == HMV_DECODER_GCN && h->cheb_fuse && h->gcn[0].Kpad == ldt &&
-        cheb_fusable(ldt, ldt, h->gcn[0].Kpad, 256, h->gcn[1].Kpad, 64, h->gcn[2].Kpad, 3)) {
-        // the three ChebConv layers in two launches (fusion_kernels.hip): layer 1 per (sample, 16 channels), layers 2 + 3 per sample
-        float *scr = R.alloc((size_t)jr * 256);
-        R.launch("cheb_fused", [&] {
-            ChebFusedParams p{};
-            p.x = X; p.ldx = ldt; p.B = B; p.K = ldt;
-            p.w1 = h->gcn[0].w; p.ldw1 = h->gcn[0].Kpad; p.c1 = 256; p.bias1 = h->gcn_bias[0];
-            p.w2 = h->gcn[1].w; p.ldw2 = h->gcn[1].Kpad; p.c2 = 64; p.bias2 = h->gcn_bias[1];
-            p.w3 = h->gcn[2].w; p.ldw3 = h->gcn[2].Kpad; p.c3 = 3; p.bias3 = h->gcn_bias[2];
-            p.tk = h->cheb_t; p.scratch = scr; p.out = joints_cam; p.ldo = 3;
-            return launch_cheb_fused(p, s);
-        }, 2);
-        R.release(X);
-        R.release(scr);
-    } else if (c.decoder == HMV_DECODER_GCN) {
-        const int dims[4] = {d, 256, 64, 3};
-        float *xin = X;
-        for (int i = 0; i < 3; ++i) {
-            const int co = dims[i + 1];
-            float *y = R.alloc((size_t)jr * 3 * co);
-            R.gemm(h->gcn[i], xin, jr, y, 3 * co, nullptr, 0, ACT_NONE);
-            R.release(xin);
-            float *out = i == 2 ? joints_cam : R.alloc((size_t)jr * co);
-            LAUNCH(launch_cheb_mix(y, 3 * co, B, co, h->cheb_t, h->gcn_bias[i], i < 2, out, i == 2 ? 3 : co, s));
-            R.release(y);
-            xin = i == 2 ? nullptr : out;
-        }
-    } else {
-        float *g1 = R.alloc((size_t)jr * 64);
-        R.gemm(h->fc1, X, jr, g1, 64, nullptr, 0, ACT_LEAKY);
-        R.release(X);
-        R.gemm(h->fc2, g1, jr, joints_cam, 3, nullptr, 0, ACT_NONE);
-        R.release(g1);
-    }
-#undef LAUNCH
-#undef ACT
+    const int N = B * c.num_views;
+    const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
+    float *Xpairs = nullptr;
+    float *X = R.tokens_stage(f, bbox, intr, crop_img, heatmap, Xpairs);
+    int Tcur = c.num_views * NJ;
+    X = h->lq ? R.fusion_learnable_query(B, X, Tcur) : R.fusion_cross_attn(B, X, Xpairs, Tcur);
+    if (h->capture && !dry && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, s); });
+    R.decoder(B, X, joints_cam);
     return R.rc;
 }
 

@@ -5,9 +5,11 @@ bytes that launch reports about itself (needs an MI355X; reads the engine's own 
 For every workload bench.py publishes numbers for -- cfg1, cfg2, cfg3, hr40 at their B, V and frame size, restated below as data
 so that no test depends on bench.py internals -- plus the batch-1, 8-view r50 shape of profiles/r04_bench_b1.json, and for each
 arithmetic mode (f32, f16, f32x3), it builds the model on synthetic weights, runs ONE eager profiled forward and records the
-ordered list of {layer, kernel, flops, bytes} (HandMvNet.profile_records()).
+ordered list of {layer, kernel, flops, bytes} (HandMvNet.profile_records()), and under "plans" the workspace plan of that
+forward: the bytes reserve() sizes for its batch and the device operations the forward enqueued (launch_count()).
 
-tests/test_gpu_launch_ledger.py holds every later build to this list: a forward whose (layer, kernel) sequence differs fails.  A
+tests/test_gpu_launch_ledger.py holds every later build to this list: a forward whose (layer, kernel) sequence, workspace bytes or launch count differs
+fails.  A
 DELIBERATE routing change regenerates the ledger with this script and comes with a measurement that justifies it; the ledger is
 always generated from the library of the commit BEFORE the change under test, never from the tree a test is about to judge.
 
@@ -49,7 +51,8 @@ def workload_params(w):
 
 
 def profiled_forward(w, mode):
-    """-> (model, cfg, state_dict, records of ONE eager profiled forward of workload row `w` in `mode`)."""
+    """-> (model, cfg, state_dict, records, plan) of ONE eager profiled forward of workload row `w` in `mode`; plan =
+    {"workspace_bytes": what reserve() sizes for the batch, "launches": device operations the forward enqueued}."""
     import torch
     from handmvnet_amd import HandMvNet
     from handmvnet_amd.spec import config_from_params
@@ -72,9 +75,11 @@ def profiled_forward(w, mode):
     out = m(xt, bt, {"intrinsic": it})
     torch.cuda.synchronize()
     recs = m.profile_records()
+    plan = {"launches": m.launch_count()}
     m.set_profiling(False)
+    plan["workspace_bytes"] = m.reserve(w["B"], w["size"], w["size"])
     assert torch.isfinite(out["joints_cam"]).all()
-    return m, cfg, sd, recs
+    return m, cfg, sd, recs, {k: plan[k] for k in ("workspace_bytes", "launches")}
 
 
 def main():
@@ -82,16 +87,18 @@ def main():
     from handmvnet_amd import _lib
     only = set(sys.argv[1:])
     led = {"what": "per workload and arithmetic mode: the ordered conv / GEMM launches of one eager forward "
-                   "(tests/golden/make_launch_ledger.py)", "workloads": WORKLOADS, "forwards": {}}
+                   "(tests/golden/make_launch_ledger.py)", "workloads": WORKLOADS, "forwards": {}, "plans": {}}
     if only:
         with open(LEDGER) as f:
-            led["forwards"] = json.load(f)["forwards"]
+            old = json.load(f)
+        led["forwards"], led["plans"] = old["forwards"], old.get("plans", {})
     led["library"] = _lib.load().hmv_version().decode()
     for name, w in WORKLOADS.items():
         if only and name not in only:
             continue
         for mode in MODES:
-            m, _, _, recs = profiled_forward(w, mode)
+            m, _, _, recs, plan = profiled_forward(w, mode)
+            led["plans"].setdefault(name, {})[mode] = plan
             led["forwards"].setdefault(name, {})[mode] = [{"layer": r["layer"], "kernel": r["kernel"], "flops": r["flops"],
                                                             "bytes": r["bytes"]} for r in recs]
             print(name, mode, len(recs), "launches", flush=True)
@@ -109,7 +116,7 @@ def main():
                 rows = ",\n".join("    " + json.dumps(r) for r in led["forwards"][name][mode])
                 f.write('   %s: [\n%s\n   ]%s\n' % (json.dumps(mode), rows, "," if j + 1 < len(modes) else ""))
             f.write("  }%s\n" % ("," if i + 1 < len(names) else ""))
-        f.write(" }\n}\n")
+        f.write(' },\n "plans": {\n%s\n }\n}\n' % ",\n".join("  %s: %s" % (json.dumps(n), json.dumps(p)) for n, p in led["plans"].items()))
 
 
 if __name__ == "__main__":

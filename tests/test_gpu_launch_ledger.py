@@ -1,7 +1,8 @@
 """What every engine launch runs and reports at the benchmarked shapes (run with -m gpu on an MI355X).
 
 tests/golden/launch_ledger.json (make_launch_ledger.py) records, for every workload bench.py publishes numbers for and every
-arithmetic mode, the ordered conv / GEMM launches of one eager forward: layer label, kernel family, FLOPs, bytes.  This file
+arithmetic mode, the ordered conv / GEMM launches of one eager forward: layer label, kernel family, FLOPs, bytes, and the forward's
+workspace bytes and launch count.  This file
 holds a build to it three ways:
 
   1. routing      -- the forward runs the ledger's kernel for every layer, covers every conv / linear layer exactly once, and
@@ -46,11 +47,11 @@ _FWD = {}
 def _forward(workload, mode):
     key = (workload, mode)
     if key not in _FWD:
-        m, cfg, sd, recs = profiled_forward(WORKLOADS[workload], mode)
+        m, cfg, sd, recs, plan = profiled_forward(WORKLOADS[workload], mode)
         shapes = {k: tuple(np.shape(v)) for k, v in sd.items()}
         del m
         torch.cuda.empty_cache()
-        _FWD[key] = (cfg, shapes, recs)
+        _FWD[key] = (cfg, shapes, recs, plan)
     return _FWD[key]
 
 
@@ -385,8 +386,9 @@ def test_routing_matches_the_ledger(workload, mode):
     """The (layer, kernel) sequence of a forward is the ledger's.  The rule (as for tests/test_tile_rules.py): the ledger is not
     edited to make this pass.  A DELIBERATE routing change regenerates it (tests/golden/make_launch_ledger.py, run on the
     commit before the change is judged) and comes with a measurement of the layers that moved; anything else that lands here is
-    a refactor that changed what the benchmarked forwards run."""
-    _, _, recs = _forward(workload, mode)
+    a refactor that changed what the benchmarked forwards run.  The same holds for the ledger's "plans": the workspace bytes and the
+    launch count of that forward, compared as integers."""
+    _, _, recs, plan = _forward(workload, mode)
     got = [(r["layer"], r["kernel"]) for r in recs]
     want = [(r["layer"], r["kernel"]) for r in _LEDGER["forwards"][workload][mode]]
     if got != want:
@@ -398,6 +400,8 @@ def test_routing_matches_the_ledger(workload, mode):
                 rows.append(f"  #{i:<3d} ledger {w[0]:<44s} {w[1]:<52s} | forward {g[0]:<44s} {g[1]}")
         pytest.fail(f"{workload} {mode}: {len(rows)} launches differ from tests/golden/launch_ledger.json "
                     f"({len(want)} in the ledger, {len(got)} in the forward)\n" + "\n".join(rows))
+    # ... and its workspace plan: the bytes reserve() sizes for the batch and the device operations the forward enqueued
+    assert plan == _LEDGER["plans"][workload][mode], (workload, mode, plan, _LEDGER["plans"][workload][mode])
 
 
 @pytest.mark.parametrize("workload,mode", CASES)
@@ -405,7 +409,7 @@ def test_every_conv_and_linear_layer_has_exactly_one_record(workload, mode):
     """Every weight of ndim 4 / 2 that spec.executed_keys() lists and the conv / GEMM family executes appears in exactly one record
     (alone or inside an a+b / +downsample / +maxpool / +up label; the four phases of a transposed conv count as its one
     record), no label appears twice, and the only layers without a record are the skip-listed ones of the fusion tail / decoder."""
-    cfg, _, recs = _forward(workload, mode)
+    cfg, _, recs, _ = _forward(workload, mode)
     want, skipped = expected_layers(cfg)
     labels = [r["layer"] for r in recs]
     assert len(set(labels)) == len(labels), sorted(l for l in set(labels) if labels.count(l) > 1)
@@ -429,7 +433,7 @@ def test_every_conv_and_linear_layer_has_exactly_one_record(workload, mode):
 def test_reported_flops_and_bytes_of_every_launch(workload, mode):
     """hmv_profile_get / hmv_profile_get_bytes of every launch against the count made here: FLOPs to 1 ulp of the double, bytes
     exactly.  (These are the numerators bench.py's per-kernel and dominant-kernel roofline fractions divide by.)"""
-    cfg, shapes, recs = _forward(workload, mode)
+    cfg, shapes, recs, _ = _forward(workload, mode)
     w = WORKLOADS[workload]
     layers = reference_layers(cfg, shapes, w["B"], w["size"])
     bad = []
@@ -450,7 +454,7 @@ def test_record_flops_against_the_published_forward_flops(workload, mode):
     engine on the 4 * 21 gathered ones, so record * (h * w) == dense * 84 exactly, level by level; nothing else may differ.
     (At cfg3 the conv-stack records give 5 226.7 GFLOP against 5 479.0 dense; the gap is SampleNet's 274.9 - 22.5.)"""
     from handmvnet_amd.spec import conv_flops_per_image, level_sizes
-    cfg, shapes, recs = _forward(workload, mode)
+    cfg, shapes, recs, _ = _forward(workload, mode)
     w = WORKLOADS[workload]
     layers = reference_layers(cfg, shapes, w["B"], w["size"])
     per_image = conv_flops_per_image(cfg, w["size"])
@@ -496,8 +500,8 @@ def test_solo_dual_launches_are_other_kernels_than_the_batch_s(mode):
     tests/test_gpu_parity.py::test_full_size_properties: every sample's feat0 inside the batch is bit-equal to its solo run, and the solo
     run is held to the f64 oracle.  That is evidence only while the solo forward runs those layers on OTHER kernels than the batch does:
     asserted here on the two forwards themselves (cfg3 at B = 32 and at B = 1), for every layer with a dual launch in either."""
-    _, _, big = _forward("cfg3", mode)
-    _, _, solo = _forward("cfg3_b1", mode)
+    _, _, big, _ = _forward("cfg3", mode)
+    _, _, solo, _ = _forward("cfg3_b1", mode)
 
     def kernel_of(recs, base):   # the kernel that computes `base` (alone or inside a dual / chained launch)
         return next(r["kernel"] for r in recs if base in record_layers(r["layer"], None))

@@ -14,7 +14,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_profile_get", "hmv_op_conv2d", "hmv_op_conv2d_ex", "hmv_op_conv2d_f16", "hmv_op_conv2d_sel", "hmv_op_conv2d_rd", "hmv_op_conv2d_as", "hmv_op_attention", "hmv_op_attention_lq", "hmv_bench_conv", "hmv_pose_metrics", "hmv_forward_frames",
            "hmv_op_prepare_frames", "hmv_set_graphs", "hmv_graph_stats", "hmv_version", "hmv_tile_rule", "hmv_profile_get_bytes", "hmv_poison_workspace", "hmv_launch_count", "hmv_set_tail_fusion", "hmv_set_chain_fusion", "hmv_set_hr_fusion", "hmv_op_conv2d_x3", "hmv_op_hr_fuse_up", "hmv_op_attention_x3",
            "hmv_range_status", "hmv_op_target_heatmaps", "hmv_project_joints", "hmv_pose_losses", "hmv_pose_losses_scratch_bytes",
-           "hmv_eval_state_doubles", "hmv_eval_add"]
+           "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -82,6 +82,10 @@ def load() -> ctypes.CDLL:
     lib.hmv_set_chain_fusion.argtypes = [vp, ci]
     lib.hmv_set_hr_fusion.argtypes = [vp, ci]
     lib.hmv_forward.argtypes = [vp, ci, fp, fp, fp, fp, fp, fp, vp]
+    lib.hmv_forward_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, fp, fp, fp, fp, fp, vp]
+    lib.hmv_forward_views.restype = ctypes.c_int
+    lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
+    lib.hmv_op_attention_views.restype = ctypes.c_int
     lib.hmv_last_error.argtypes = [vp]
     lib.hmv_last_error.restype = ctypes.c_char_p
     lib.hmv_destroy.argtypes = [vp]

@@ -206,6 +206,17 @@ struct hmv_engine {
     int reserved_batch = 0;
     Arena plan;
 
+    // ragged view sets (hmv_forward_views): the call's tables [seg: B + 1 first token rows | fpos: per frame, 21 x its rank among its
+    // sample's present views] -- the host copy, and the device copy it is uploaded to on the caller's stream.  The host copies are
+    // pinned (the upload is then asynchronous for the host as well) and form a small ring: a slot is rewritten only after the upload
+    // that last read it has run (`done`), which a caller notices only when it is four ragged calls ahead of the device.
+    struct ViewsSlot { int32_t *host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
+    ViewsSlot views_host[4];
+    unsigned views_next = 0;
+    int32_t *views_dev = nullptr;
+    size_t views_cap = 0;
+    bool last_ragged = false;   // the last forward was a ragged one: it captured no stages (hmv_read_stage)
+
     bool capture = false;
     int cap_batch = 0;
     float *cap_feat0 = nullptr, *cap_coords = nullptr, *cap_tokens = nullptr, *cap_fused = nullptr;
@@ -1190,6 +1201,10 @@ struct ConvCall {
 };
 
 // One forward in progress: workspace, stream and launch helpers, the two residual blocks, then the stages of HandMvNet.forward
+// A ragged call's view sets: N frames in all, sample b's token rows are seg[b] .. seg[b + 1] (device, B + 1 entries), frame n sits at
+// positions fpos[n] .. fpos[n] + 20 of its sample (device, N entries); Tmax = the longest sample's token count.  A planning run has no tables.
+struct ViewSet { int N; const int32_t *seg, *fpos; int Tmax; };
+
 #define LAUNCH(expr) launch(#expr, [&] { return (expr); })   // (inside Runner: see launch())
 struct Runner {
     hmv_engine *h;
@@ -1197,6 +1212,7 @@ struct Runner {
     bool dry;
     int rc = HMV_OK;
     Arena &A;
+    const ViewSet *vs = nullptr;   // not null: a ragged forward (hmv_forward_views); stages are not captured then
 
     float *alloc(size_t n) {
         float *ptr = A.alloc(n);
@@ -1583,7 +1599,7 @@ struct Runner {
 
     // feats[0] as fp32 NCHW into the capture buffer
     void capture_feat0(const Map &f) {
-        if (!h->capture || dry || !h->cap_feat0) return;
+        if (!h->capture || dry || vs || !h->cap_feat0) return;
         if (split) LAUNCH(launch_nhwc_split_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
         else if (h16) LAUNCH(launch_nhwc_f16_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
         else LAUNCH(launch_nhwc_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s, f.ld));
@@ -1797,7 +1813,7 @@ struct Runner {
         float *coords = alloc((size_t)N * NJ * 2);
         LAUNCH(launch_soft_argmax(f.hm.p, f.hm.ld, N, f.hm.H, f.hm.W, coords, crop_img, (float)c.image_size, (float)c.heatmap_size, heatmap, s));
         release(f.hm);
-        if (h->capture && !dry && h->cap_coords)
+        if (h->capture && !dry && !vs && h->cap_coords)
             LAUNCH(hipMemcpyAsync(h->cap_coords, coords, (size_t)N * NJ * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
 
         // ---- sample nets as gather -> conv1x1+BN+ReLU -> bilinear blend (nets.py:46-63; handmvnet.py:185-187)
@@ -1821,35 +1837,41 @@ struct Runner {
         // CrossAttentionFusion read their token rows as (hi, lo) fp16 pairs: the kernel that produces a block's input rows -- this one for
         // block 0, ff_block_kernel for the others -- writes that copy itself (rows_f32_to_half's arithmetic, one launch less per block)
         if (!h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = alloc((size_t)N * NJ * ldt);
-        LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc,
-                                      (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe,   // the learnable-query blocks add their own PE
-                                      (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
+        const float *pe = (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe;   // the learnable-query blocks add their own PE
+        if (vs) LAUNCH(launch_tokens_finalize_views(tokens, ldt, d, h->fdim, N, vs->fpos, coords, bbox, intr, c.pos_enc, pe, s, Xpairs, h->sat));
+        else LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc, pe,
+                                           (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
         release(coords);
         return tokens;
     }
 
     // CrossAttentionFusionLearnableQuery (fusion.py:33-49; MultiHeadAttentionLearnableQuery layers.py:273-301): token rows X [B * Tcur][ldt]
     // in (released), the fused rows out; Tcur follows
+    // A ragged forward (vs): up to and including the probe block a sample owns T_b = 21 v_b rows, the segment seg[b] .. seg[b + 1] of the
+    // vs->N * 21 packed rows; Tcur is then the longest sample's count.  Behind the probe block every sample has 21 rows, as ever.
     float *fusion_learnable_query(int B, float *X, int &Tcur) {
         const int d = h->d, ldt = h->ldt;
         for (int l = 0; l < 5; ++l) {
             const AttnLayer &a = h->attn[l];
-            const bool cross = l == 2;
-            const int rows = B * Tcur, Tq = cross ? NJ : Tcur, qrows = B * Tq;
+            const bool cross = l == 2, ragged = vs && l <= 2;
+            const int rows = ragged ? vs->N * NJ : B * Tcur, Tq = cross ? NJ : Tcur, qrows = (ragged && !cross) ? rows : B * Tq;
             float *xp = alloc((size_t)rows * ldt);                       // x = self.pos_embed(x)
-            LAUNCH(launch_add_pe(X, ldt, rows, Tcur, d, h->pe, xp, ldt, s));
+            if (ragged) LAUNCH(launch_add_pe_views(X, ldt, rows, vs->fpos, d, h->pe, xp, ldt, s));
+            else LAUNCH(launch_add_pe(X, ldt, rows, Tcur, d, h->pe, xp, ldt, s));
             release(X);
             float *att = alloc((size_t)qrows * INNER_LQ);
             const bool tx3 = a.out_x3.plane != 0 && ff_fusable(a, qrows, true);   // attention rows as (hi, lo) pairs
             if (cross) {
                 float *kv = alloc((size_t)rows * 2 * INNER_LQ);
                 project(a.kv, xp, rows, kv, 2 * INNER_LQ);
-                LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                if (ragged) LAUNCH(launch_attention_d256_views(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, vs->seg, Tcur, att, s, tx3 ? 1 : 0, h->sat));
+                else LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
                 release(kv);
             } else {
                 float *qkv = alloc((size_t)rows * 3 * INNER_LQ);
                 project(a.qkv, xp, rows, qkv, 3 * INNER_LQ);
-                LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                if (ragged) LAUNCH(launch_attention_d256_views(qkv, 3 * INNER_LQ, 1, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, vs->seg, Tcur, att, s, tx3 ? 1 : 0, h->sat));
+                else LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
                 release(qkv);
             }
             if (ff_fusable(a, qrows, tx3)) {
@@ -1894,9 +1916,9 @@ struct Runner {
         const int half = (c.fusion_layers - 1) / 2;
         for (int l = 0; l < c.fusion_layers; ++l) {
             const AttnLayer &a = h->attn[l];
-            const bool cross = (l == half);
+            const bool cross = (l == half), ragged = vs && l <= half;   // (as in fusion_learnable_query)
             const int Tq = cross ? NJ : Tcur, koff = cross ? NJ : 0, Tk = cross ? Tcur - NJ : Tcur;
-            const int rows = B * Tcur, qrows = B * Tq;
+            const int rows = ragged ? vs->N * NJ : B * Tcur, qrows = (ragged && !cross) ? rows : B * Tq;
 #ifdef HMV_NO_ATT_X3   // A/B builds only (python -m handmvnet_amd.build --variant noax HMV_NO_ATT_X3): the exact-fp32 attention in every mode
             const int att_x3 = 0;
 #else
@@ -1910,13 +1932,25 @@ struct Runner {
             float *att = alloc((size_t)qrows * INNER);
             // fp16-kernel modes, fused tail: the attention rows leave the kernel as (hi, lo) pairs and to_out is a split-pair GEMM
             const bool tx3 = a.out_x3.plane != 0 && ff_fusable(a, qrows, true);
-            if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
+            // (ragged: a sample with one view has no keys in the cross block; the kernel writes its rows as zeros)
+            if (ragged) LAUNCH(launch_attention_views(qkv, B, vs->seg, Tcur, cross ? 1 : 0, att, s, tx3 ? 1 : 0, att_x3, h->sat));
+            else if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
             else LAUNCH(hipMemsetAsync(att, 0, (size_t)qrows * INNER * sizeof(float), s));   // (zero rows are zero pairs)
             release(qkv);
+            // ragged cross block: the residual `_q` = each sample's first 21 rows, gathered into contiguous rows, so that everything
+            // behind the attention addresses its residual row by row (rg_out = 0) as in the self blocks
+            int rgo = cross ? Tq : 0, rgi = cross ? Tcur : 0;
+            if (ragged && cross) {
+                float *Xq = alloc((size_t)qrows * ldt);
+                LAUNCH(launch_gather_query_rows(X, ldt, vs->seg, B, Xq, s));
+                release(X);
+                X = Xq;
+                rgo = rgi = 0;
+            }
             if (ff_fusable(a, qrows, tx3)) {   // norm1(to_out + _q) -> FeedForward -> norm2 in one launch behind the GEMM
                 float *Xf = alloc((size_t)qrows * ldt);
                 if (l + 1 < c.fusion_layers && h->attn[l + 1].qkv.plane) Xpairs = alloc((size_t)qrows * ldt);   // the next block's projection input
-                ff_block(a, att, qrows, X, cross ? Tq : 0, cross ? Tcur : 0, Xf, Xpairs, tx3);
+                ff_block(a, att, qrows, X, rgo, rgi, Xf, Xpairs, tx3);
                 release(att);
                 release(X);
                 X = Xf;
@@ -1924,7 +1958,7 @@ struct Runner {
                 continue;
             }
             float *n1 = alloc((size_t)qrows * ldt), *f0 = alloc((size_t)qrows * ldt);
-            gemm_ln(a.out, att, qrows, X, ldt, cross ? Tq : 0, cross ? Tcur : 0, a.n1g, a.n1b, n1, ldt, a.fg, a.fb, f0);  // norm1(to_out + _q), ff LN
+            gemm_ln(a.out, att, qrows, X, ldt, rgo, rgi, a.n1g, a.n1b, n1, ldt, a.fg, a.fb, f0);  // norm1(to_out + _q), ff LN
             release(att);
             float *f1 = alloc((size_t)qrows * DHEAD);
             gemm(a.ff1, f0, qrows, f1, DHEAD, nullptr, 0, ACT_GELU);
@@ -1987,22 +2021,23 @@ struct Runner {
 #undef LAUNCH
 
 // HandMvNet.forward (handmvnet.py:158-266), stage by stage; a planning run (dry) issues the same alloc / release sequence and launches nothing
+// vs (ragged view sets, hmv_forward_views): the backbone and the token stage run on vs->N frames, the fusion over each sample's own rows
 int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const float *intr, float *crop_img, float *joints_cam,
-                float *heatmap, hipStream_t s, bool dry, Arena &A) {
-    Runner R{h, s, dry, HMV_OK, A};
+                float *heatmap, hipStream_t s, bool dry, Arena &A, const ViewSet *vs = nullptr) {
+    Runner R{h, s, dry, HMV_OK, A, vs};
     const hmv_config &c = h->cfg;
     if (!dry && h->hrnet && h->hr_overlap && c.dtype != HMV_F32 && !h->aux) {   // (the first forward of a handle is never a captured one)
         if (hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
             return h->fail(HMV_ERR_HIP, "second stream for the HRNet branches");
     }
-    const int N = B * c.num_views;
+    const int N = vs ? vs->N : B * c.num_views;
     const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
     float *Xpairs = nullptr;
     float *X = R.tokens_stage(f, bbox, intr, crop_img, heatmap, Xpairs);
-    int Tcur = c.num_views * NJ;
+    int Tcur = vs ? vs->Tmax : c.num_views * NJ;
     X = h->lq ? R.fusion_learnable_query(B, X, Tcur) : R.fusion_cross_attn(B, X, Xpairs, Tcur);
-    if (h->capture && !dry && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, s); });
+    if (h->capture && !dry && !vs && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, s); });
     R.decoder(B, X, joints_cam);
     return R.rc;
 }
@@ -2083,6 +2118,7 @@ static int forward_common(hmv_handle h, int32_t batch, const float *x, const flo
         const int rc = hmv_reserve(h, batch);
         if (rc != HMV_OK) return rc;
     }
+    h->last_ragged = false;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // stage capture copies into side buffers and profiling brackets launches with events: both stay eager
     if (!h->graphs || h->capture || h->profiling)
@@ -2164,6 +2200,96 @@ int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, 
     return forward_common(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
 }
 
+/* hmv_forward for a batch whose samples have different cameras (include/handmv.h).  Everything that can be refused is refused before the
+ * first launch.  Always eager: the tables differ from call to call, so a ragged call never enters the graph replay cache. */
+int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
+                      float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (batch <= 0) return h->fail(HMV_ERR_ARG, "hmv_forward_views: batch must be positive (got %d)", (int)batch);
+    if (!view_counts) return h->fail(HMV_ERR_ARG, "hmv_forward_views: view_counts is null (one host entry per sample)");
+    if (!x || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "null or empty input/output");
+    const int V = h->cfg.num_views;
+    size_t N = 0;
+    int vmax = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int v = view_counts[b];
+        if (v < 1 || v > V)
+            return h->fail(HMV_ERR_ARG, "hmv_forward_views: view_counts[%d] = %d, every sample needs between 1 and num_views = %d present views", b, v, V);
+        N += (size_t)v;
+        vmax = v > vmax ? v : vmax;
+    }
+    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
+        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (batch > h->reserved_batch) {
+        const int rc = hmv_reserve(h, batch);
+        if (rc != HMV_OK) return rc;
+    }
+    // the tables: [seg: B + 1 | fpos: N]
+    const size_t tab_n = (size_t)batch + 1 + N;
+    hmv_engine::ViewsSlot &slot = h->views_host[h->views_next++ % 4];
+    if (slot.done) HIPCHK(h, hipEventSynchronize(slot.done));
+    else HIPCHK(h, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (tab_n > slot.cap) {
+        if (slot.host) HIPCHK(h, hipHostFree(slot.host));
+        slot.host = nullptr;
+        slot.cap = 0;
+        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (V + 1) + 1);
+        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&slot.host), cap * sizeof(int32_t), hipHostMallocDefault));
+        slot.cap = cap;
+    }
+    int32_t *seg = slot.host, *fpos = seg + batch + 1;
+    seg[0] = 0;
+    for (int b = 0, n = 0; b < batch; ++b) {
+        seg[b + 1] = seg[b] + NJ * view_counts[b];
+        for (int r = 0; r < view_counts[b]; ++r) fpos[n++] = NJ * r;
+    }
+    ViewSet vs{(int)N, nullptr, nullptr, NJ * vmax};
+    // The workspace: reserved for `batch` uniform samples, which asks for more of every buffer than any ragged batch of as many samples.
+    // The planner is first-fit, though, and the ragged cross block holds one more small buffer, so this call's own plan is
+    // checked BEFORE anything is launched, and the workspace grows in the (unobserved) case that it does not fit.
+    {
+        Arena dry;
+        dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));
+        const bool saved = h->profiling;
+        h->profiling = false;
+        run_forward(h, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry, &vs);
+        h->profiling = saved;
+        if (dry.high > h->arena_bytes) {
+            HIPCHK(h, hipDeviceSynchronize());
+            h->drop_graphs();   // captured launches point into the old workspace
+            if (h->arena) HIPCHK(h, hipFree(h->arena));
+            h->arena = nullptr;
+            h->arena_bytes = 0;
+            const int served = h->reserved_batch;   // the larger workspace still serves as many uniform samples
+            h->reserved_batch = 0;
+            HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->arena), dry.high));
+            h->arena_bytes = dry.high;
+            h->reserved_batch = served;
+        }
+    }
+    if (tab_n > h->views_cap) {   // (hipFree waits for the launches that still read the old table)
+        if (h->views_dev) HIPCHK(h, hipFree(h->views_dev));
+        h->views_dev = nullptr;
+        h->views_cap = 0;
+        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (V + 1) + 1);
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->views_dev), cap * sizeof(int32_t)));
+        h->views_cap = cap;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(h, hipMemcpyAsync(h->views_dev, slot.host, tab_n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipEventRecord(slot.done, s));
+    vs.seg = h->views_dev;
+    vs.fpos = h->views_dev + batch + 1;
+    h->last_ragged = true;
+    h->plan.reset(h->arena);
+    h->launches = 1;
+    const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan, &vs);
+    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    return rc;
+}
+
 int hmv_forward_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, const int32_t *crop_boxes,
                        const float *mean, const float *std, const float *bbox, const float *intrinsic, float *joints_crop_img,
                        float *joints_cam, float *heatmap, void *stream) {
@@ -2206,6 +2332,11 @@ void hmv_destroy(hmv_handle h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (void *p : h->dev_allocs) (void)hipFree(p);
     if (h->sat) (void)hipFree(h->sat);
+    if (h->views_dev) (void)hipFree(h->views_dev);
+    for (auto &sl : h->views_host) {
+        if (sl.host) (void)hipHostFree(sl.host);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+    }
     if (h->arena) (void)hipFree(h->arena);
     for (float *p : {h->cap_feat0, h->cap_coords, h->cap_tokens, h->cap_fused})
         if (p) (void)hipFree(p);
@@ -2274,6 +2405,8 @@ int hmv_read_stage(hmv_handle h, const char *stage, float *dst, size_t capacity,
     else if (st == "tokens") { src = h->cap_tokens; n = h->cap_tokens_n; }
     else if (st == "fused") { src = h->cap_fused; n = h->cap_fused_n; }
     else return h->fail(HMV_ERR_ARG, "unknown stage %s", stage);
+    if (h->last_ragged)
+        return h->fail(HMV_ERR_STATE, "the last forward was a ragged one (hmv_forward_views): stages are captured by hmv_forward only");
     if (!src) return h->fail(HMV_ERR_STATE, "stage capture was not enabled before the forward");
     if (capacity < n) n = capacity;
     HIPCHK(h, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
@@ -2371,6 +2504,46 @@ int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_
     if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
     const hipError_t e = launch_attention_d256(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, out, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
+    return HMV_OK;
+}
+
+/* Test hook: the ragged attention kernels on their own (include/handmv.h). */
+int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, const int32_t *seg_host, int32_t cross,
+                           float *out, void *stream) {
+    auto bad = [](const char *why) { g_create_err = std::string("hmv_op_attention_views: ") + why; return (int)HMV_ERR_ARG; };
+    if (!qkv || !out || !seg_host || B <= 0 || kind < 0 || kind > 2) return bad("bad argument");
+    if (kind == 2 && cross && !probe) return bad("the cross block of the 256-wide heads needs the probe queries");
+    if (seg_host[0] != 0) return bad("seg[0] must be 0");
+    int Tmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int T = seg_host[b + 1] - seg_host[b];
+        if (T < 1 || (cross && kind != 2 && T < 21)) return bad("every sample needs at least one row, and 21 query rows in the cross block");
+        Tmax = T > Tmax ? T : Tmax;
+    }
+    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t rows = (size_t)seg_host[B];
+    int32_t *seg = nullptr;
+    void *pairs = nullptr;
+    RangeWord rw;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&seg), (size_t)(B + 1) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(seg, seg_host, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && kind == 1) {   // the kernel takes rows of (hi, lo) fp16 pairs: split the fp32 rows first (hmv_op_attention_x3)
+        e = rw.alloc();
+        if (e == hipSuccess) e = hipMalloc(&pairs, rows * 3072 * 4);
+        if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, rows, 3072, 2, s, rw.p);
+        if (e == hipSuccess) e = launch_attention_views(static_cast<const float *>(pairs), B, seg, Tmax, cross, out, s, 0, 1, rw.p);
+    } else if (e == hipSuccess && kind == 0) {
+        e = launch_attention_views(qkv, B, seg, Tmax, cross, out, s);
+    } else if (e == hipSuccess) {
+        if (cross) e = launch_attention_d256_views(probe, 2048, 0, qkv, qkv + 2048, 4096, B, seg, Tmax, out, s);
+        else e = launch_attention_d256_views(qkv, 6144, 1, qkv + 2048, qkv + 4096, 6144, B, seg, Tmax, out, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (pairs) (void)hipFree(pairs);
+    if (seg) (void)hipFree(seg);
+    if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
+    if (kind == 1 && rw.saturated()) { g_create_err = "hmv_op_attention_views: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
     return HMV_OK;
 }
 

@@ -232,6 +232,23 @@ hipError_t launch_attention_d256(const float *q, int q_ld, int q_bstride, const 
                                  int Tq, float *out, hipStream_t s, int pairs = 0, int *sat = nullptr);
 // y[r][c] = x[r][c] + pe[r % T][c] for c < d, 0 for d <= c < ldy (PositionalEncoding inside every learnable-query block)
 hipError_t launch_add_pe(const float *x, int ldx, int rows, int T, int d, const float *pe, float *y, int ldy, hipStream_t s);
+// ---- ragged view sets (hmv_forward_views): sample b's tokens are rows seg[b] .. seg[b + 1] of the packed token matrix (seg: device
+// table of B + 1 first rows), frame n is the (fpos[n] / 21)-th present view of its sample (fpos: device table, one entry per frame).
+// Compile-time variants of the kernels above -- the uniform instantiations are untouched -- with the same arithmetic per sample: the
+// split of a sample's key range depends on its own token count alone.
+hipError_t launch_tokens_finalize_views(float *tokens, int ldt, int d, int fdim, int N, const int *fpos, const float *coords,
+                                        const float *bbox, const float *intr, int pos_mask, const float *pe, hipStream_t s,
+                                        void *pairs = nullptr, int *sat = nullptr);
+// Tmax: the longest sample's token count (sizes the grid).  cross = 0: a self block, out rows seg[b] + i;  cross = 1: the cross block,
+// queries = a sample's first 21 rows, keys = the rest, out rows b * 21 + i -- exact zeros for a sample with one view (no keys)
+hipError_t launch_attention_views(const float *qkv, int B, const int *seg, int Tmax, int cross, float *out, hipStream_t s, int pairs = 0,
+                                  int x3 = 0, int *sat = nullptr);
+// q_seg = 1: query rows seg[b] + i of q, out rows seg[b] + i (self block);  0: the 21 rows of q for every sample, out rows b * 21 + i
+hipError_t launch_attention_d256_views(const float *q, int q_ld, int q_seg, const float *k, const float *v, int kv_ld, int B,
+                                       const int *seg, int Tmax, float *out, hipStream_t s, int pairs = 0, int *sat = nullptr);
+hipError_t launch_add_pe_views(const float *x, int ldx, int rows, const int *fpos, int d, const float *pe, float *y, int ldy, hipStream_t s);
+// out[b * 21 + j][0, ld) = x[seg[b] + j][0, ld): the cross block's residual rows `_q`, contiguous (ld % 4 == 0)
+hipError_t launch_gather_query_rows(const float *x, int ld, const int *seg, int B, float *out, hipStream_t s);
 // split-K GEMM tail: out[r][c] = act(sum_s slab[s][r][c] + bias[c] + res[r'][c]) for c < N (slices summed in index order)
 hipError_t launch_splitk_layernorm(const float *slab, int S, int rows, int lds, int d, const float *bias, const float *res, int ldr,
                                    int rg_out, int rg_in, const float *g1, const float *b1, float *y, int ldy, const float *g2,

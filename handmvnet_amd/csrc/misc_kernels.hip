@@ -538,41 +538,25 @@ hipError_t launch_sample_blend(const float *s4, int lds4, int C, int N, int H, i
 __global__ void tokens_finalize_kernel(float *tokens, int ldt, int d, int fdim, int V, const float *coords,
                                        const float *bbox, const float *intr, int pos_mask, const float *pe,
                                        float *raw_copy, _Float16 *pairs, int *sat) {
-    const int row = blockIdx.x;           // n*21 + j, n = b*V + v
-    const int n = row / 21, j = row - n * 21;
-    float *t = tokens + (size_t)row * ldt;
-    int col = fdim;
-    if (threadIdx.x == 0) {
-        if (pos_mask & 1) { t[col] = coords[2 * row]; t[col + 1] = coords[2 * row + 1]; }
-    }
-    if (pos_mask & 1) col += 2;
-    if ((pos_mask & 2) && threadIdx.x < 10) {
-        const float *bb = bbox + 4 * n, *in = intr + 4 * n;
-        const int pt = threadIdx.x >> 1, isy = threadIdx.x & 1;
-        float px, py;
-        if (pt == 0) { px = bb[0]; py = bb[1]; }
-        else if (pt == 1) { px = bb[0]; py = bb[3]; }
-        else if (pt == 2) { px = bb[2]; py = bb[1]; }
-        else if (pt == 3) { px = bb[2]; py = bb[3]; }
-        else { px = (bb[0] + bb[2]) / 2.f; py = (bb[1] + bb[3]) / 2.f; }
-        t[col + threadIdx.x] = isy ? atanf((py - in[3]) / in[1]) : atanf((px - in[2]) / in[0]);
-    }
-    for (int c = d + threadIdx.x; c < ldt; c += blockDim.x) t[c] = 0.f;
-    __syncthreads();
-    const int pos = (n % V) * 21 + j;  // token index inside its sample, view-major
-    for (int c = threadIdx.x; c < d; c += blockDim.x) {
-        float v = t[c];
-        if (raw_copy) raw_copy[(size_t)row * d + c] = v;
-        if (pe) { v = v + pe[(size_t)pos * d + c]; t[c] = v; }
-        if (pairs) {
-            _Float16 a, b;
-            note_range(sat, split_f16(v, a, b));
-            pairs[(size_t)row * 2 * ldt + c] = a;
-            pairs[(size_t)row * 2 * ldt + ldt + c] = b;
-        }
-    }
-    if (pairs)
-        for (int c = d + threadIdx.x; c < ldt; c += blockDim.x) { pairs[(size_t)row * 2 * ldt + c] = (_Float16)0.f; pairs[(size_t)row * 2 * ldt + ldt + c] = (_Float16)0.f; }
+#define TOK_POS (n % V) * 21 + j
+#include "tokens_finalize_body.inc"
+#undef TOK_POS
+}
+// Ragged view sets: frame n is the (fpos[n] / 21)-th PRESENT view of its sample, whatever camera it came from
+__global__ void tokens_finalize_views_kernel(float *tokens, int ldt, int d, int fdim, const int *__restrict__ fpos, const float *coords,
+                                             const float *bbox, const float *intr, int pos_mask, const float *pe,
+                                             float *raw_copy, _Float16 *pairs, int *sat) {
+#define TOK_POS fpos[n] + j
+#include "tokens_finalize_body.inc"
+#undef TOK_POS
+}
+hipError_t launch_tokens_finalize_views(float *tokens, int ldt, int d, int fdim, int N, const int *fpos, const float *coords,
+                                        const float *bbox, const float *intr, int pos_mask, const float *pe, hipStream_t s, void *pairs,
+                                        int *sat) {
+    if (N <= 0 || !fpos) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tokens_finalize_views_kernel, dim3(N * 21), dim3(128), 0, s, tokens, ldt, d, fdim, fpos, coords, bbox, intr,
+                       pos_mask, pe, nullptr, reinterpret_cast<_Float16 *>(pairs), sat);
+    return hipGetLastError();
 }
 hipError_t launch_tokens_finalize(float *tokens, int ldt, int d, int fdim, int N, int V, const float *coords,
                                   const float *bbox, const float *intr, int pos_mask, const float *pe, float *raw_copy,
@@ -712,202 +696,61 @@ template <int D, int ATT_WAVES>
 __global__ __launch_bounds__(64 * ATT_WAVES, D == 128 ? HMV_ATT_OCC : 1) void attention_mfma_kernel(const float *__restrict__ q, int q_ld, int q_bstride,
         const float *__restrict__ k, const float *__restrict__ v, int kv_ld, int T, int Tq, int Tk, int nqb, float *__restrict__ out, int pairs,
         int *sat) {
-    using SH = AttShape<D, ATT_WAVES>;
-    constexpr int NC = SH::NC, NU = D / 8, NV = D / 32;   // K vectors per lane, V vectors per lane and quarter chunk
-    extern __shared__ __attribute__((aligned(16))) float att_smem[];
-    const int qblk = blockIdx.x % nqb, bh = blockIdx.x / nqb;
-    const int b = bh >> 3, h = bh & 7;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, kh = lane >> 5;
-    const size_t ld = (size_t)kv_ld;
-    const float *qb = q + (size_t)b * q_bstride * q_ld + h * D;
+#define ATT_ROWS \
+    const float *qb = q + (size_t)b * q_bstride * q_ld + h * D; \
     const float *kb = k + (size_t)b * T * ld + h * D, *vb = v + (size_t)b * T * ld + h * D;
-    const int nkc = (Tk + 31) >> 5;
-    const float scale = D == 128 ? 0.08838834764831845f : 0.0625f;  // D ** -0.5
-    float *sQ = att_smem;                                                   // [32][LDK]
-    float *sVw = att_smem + SH::Q_FLOATS + wave * SH::V_FLOATS;             // [8][D], this wave's
+#define ATT_OROW (size_t)b * Tq + row
+#include "attention_mfma_body.inc"
+#undef ATT_ROWS
+#undef ATT_OROW
+}
 
-    // every global load of a wave's first chunk is issued before anything waits
-    constexpr bool PREFETCH = D == 128;
-    f32x4 kf[NU], va[NV], vb_[NV];
-    int kc = wave;
-#define ATT_LOAD_K(KC)                                                                                  \
-    do {                                                                                                \
-        const int key_ = (KC) * 32 + l31;                                                               \
-        const bool kv_ = key_ < Tk;                                                                     \
-        const float *krow_ = kb + (size_t)(kv_ ? key_ : 0) * ld + 4 * kh;                               \
-        _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                \
-            kf[u] = *reinterpret_cast<const f32x4 *>(krow_ + 8 * u);                                    \
-            if (!kv_) kf[u] = f32x4{0.f, 0.f, 0.f, 0.f};                                                \
-        }                                                                                               \
-    } while (0)
-    // 8 keys x D channels: NV coalesced 16-byte vectors per lane (keys >= Tk are zeros)
-#define ATT_LOAD_V(KEY0, VR)                                                                            \
-    do {                                                                                                \
-        _Pragma("unroll") for (int it = 0; it < NV; ++it) {                                             \
-            const int idx_ = it * 64 + lane, k2_ = (KEY0) + idx_ / (D / 4);                             \
-            VR[it] = f32x4{0.f, 0.f, 0.f, 0.f};                                                         \
-            if (k2_ < Tk) VR[it] = *reinterpret_cast<const f32x4 *>(vb + (size_t)k2_ * ld + 4 * (idx_ % (D / 4))); \
-        }                                                                                               \
-    } while (0)
-#define ATT_STORE_V(VR)                                                                                 \
-    do {                                                                                                \
-        __builtin_amdgcn_wave_barrier();                                                                \
-        _Pragma("unroll") for (int it = 0; it < NV; ++it) {                                             \
-            const int idx_ = it * 64 + lane;                                                            \
-            *reinterpret_cast<f32x4 *>(&sVw[(idx_ / (D / 4)) * D + 4 * (idx_ % (D / 4))]) = VR[it];     \
-        }                                                                                               \
-        __builtin_amdgcn_wave_barrier();                                                                \
-    } while (0)
-    // O^T += V^T P^T over the 8 keys of quarter G: the k-pair of step e2 is (key 8G + e2, key 8G + e2 + 4) = P register 4G + e2
-#define ATT_PV(G)                                                                                       \
-    do {                                                                                                \
-        _Pragma("unroll") for (int e2 = 0; e2 < 4; ++e2) {                                              \
-            const float *vrow = &sVw[(4 * kh + e2) * D + l31];                                          \
-            _Pragma("unroll") for (int c = 0; c < NC; ++c)                                              \
-                o[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32 * c], sacc[4 * (G) + e2], o[c], 0, 0, 0); \
-        }                                                                                               \
-    } while (0)
-    if (kc < nkc) {
-        ATT_LOAD_K(kc);
-        ATT_LOAD_V(kc * 32, va);
-    }
-    // Q block (rows >= Tq are zeros), shared by the waves
-#pragma unroll
-    for (int it = 0; it < (8 * D) / (64 * ATT_WAVES); ++it) {
-        const int idx = it * (64 * ATT_WAVES) + tid, r = idx / (D / 4), c4 = idx % (D / 4), row = qblk * 32 + r;
-        f32x4 qv = {0.f, 0.f, 0.f, 0.f};
-        if (row < Tq) qv = *reinterpret_cast<const f32x4 *>(qb + (size_t)row * q_ld + 4 * c4);
-        *reinterpret_cast<f32x4 *>(&sQ[r * SH::LDK + 4 * c4]) = qv;
-    }
-    __syncthreads();
-
-    f32x16 o[NC];   // o[c][e] on lane (q, half): O[q][32c + (e&3) + 8(e>>2) + 4 half]
-    float m_run = -INFINITY, l_run = 0.f;   // of query l31, over the keys this lane has seen (its half of every chunk)
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[c][e] = 0.f;
-
-#define ATT_CHUNK(KC)                                                                                   \
-    do {                                                                                                \
-        f32x16 sacc;                                                                                    \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) sacc[e] = 0.f;                                   \
-        _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                \
-            const f32x4 qf = *reinterpret_cast<const f32x4 *>(&sQ[l31 * SH::LDK + 8 * u + 4 * kh]);     \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                               \
-                sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[u][e], qf[e], sacc, 0, 0, 0);            \
-        }                                                                                               \
-        /* the key rows of this wave's NEXT chunk fly during the softmax and the P V products of this one (their registers are free) */ \
-        if (PREFETCH && (KC) + ATT_WAVES < nkc) ATT_LOAD_K((KC) + ATT_WAVES);                           \
-        ATT_LOAD_V((KC) * 32 + 8, vb_);   /* the next 8 keys fly during the softmax */                  \
-        /* register e = key (e&3) + 8(e>>2) + 4 half of the chunk, for query l31 */                     \
-        float mx = -INFINITY;                                                                           \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                \
-            const bool kv_ = (KC) * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh < Tk;                          \
-            sacc[e] = kv_ ? sacc[e] * scale : -INFINITY;                                                \
-            mx = fmaxf(mx, sacc[e]);                                                                    \
-        }                                                                                               \
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));          /* finite: the chunk has >= 1 valid key */     \
-        const float m_new = fmaxf(m_run, mx);                                                           \
-        const float alpha = expf(m_run - m_new);         /* exp(-inf) = 0 on the first chunk */         \
-        float psum = 0.f;                                                                               \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                \
-            sacc[e] = expf(sacc[e] - m_new);             /* exp(-inf) = 0 for keys >= Tk */             \
-            psum += sacc[e];                                                                            \
-        }                                                                                               \
-        l_run = l_run * alpha + psum;                                                                   \
-        m_run = m_new;                                                                                  \
-        _Pragma("unroll") for (int c = 0; c < NC; ++c)                                                  \
-            _Pragma("unroll") for (int e = 0; e < 16; ++e) o[c][e] *= alpha;                            \
-        /* 8 keys at a time through the wave's LDS buffer; the loads run two quarters ahead */          \
-        ATT_STORE_V(va);                                                                                \
-        ATT_LOAD_V((KC) * 32 + 16, va);                                                                 \
-        ATT_PV(0);                                                                                      \
-        ATT_STORE_V(vb_);                                                                               \
-        ATT_LOAD_V((KC) * 32 + 24, vb_);                                                                \
-        ATT_PV(1);                                                                                      \
-        ATT_STORE_V(va);                                                                                \
-        if (PREFETCH && (KC) + ATT_WAVES < nkc) ATT_LOAD_V(((KC) + ATT_WAVES) * 32, va);   /* ... and its first 8 value rows */ \
-        ATT_PV(2);                                                                                      \
-        ATT_STORE_V(vb_);                                                                               \
-        ATT_PV(3);                                                                                      \
-        __builtin_amdgcn_wave_barrier();                                                                \
-    } while (0)
-    if (kc < nkc) {
-        // 128-wide heads: a chunk requests the operands of this wave's next one (round 4); the 256-wide ones have no registers for that
-        if constexpr (PREFETCH) {
-            for (; kc < nkc; kc += ATT_WAVES) ATT_CHUNK(kc);
-        } else {
-            ATT_CHUNK(kc);
-            for (kc += ATT_WAVES; kc < nkc; kc += ATT_WAVES) {
-                ATT_LOAD_K(kc);
-                ATT_LOAD_V(kc * 32, va);
-                ATT_CHUNK(kc);
-            }
+// ---- ragged view sets: sample b's tokens are rows seg[b] .. seg[b + 1] of the packed token matrix, T_b = seg[b + 1] - seg[b] of them
+// Where a workgroup's rows are, for the ragged forms of the three attention kernels.  The grid is sized for the longest sample.
+//   queries  q_seg: rows seg[b] + i of q;  otherwise rows i of q, shared by every sample (the learnable probe queries)
+//   keys     rows seg[b] + koff + j of k / v, j < T_b - koff
+//   tq_fixed 0: every token queries (self blocks), output row seg[b] + i;  > 0: the first tq_fixed rows do (cross block), output row
+//            b * tq_fixed + i
+// rows() == false: nothing (more) to do for this workgroup -- its query block lies beyond the sample's queries, or the sample has NO keys
+// (one view in the cross block: the reference's attention rows are zeros) and its rows were written as zeros here.  The answer depends
+// on (b, qblk) alone, so the whole workgroup takes it, and the callers ask ahead of any LDS access or barrier.
+struct AttSeg {
+    const int *seg;
+    int q_seg, koff, tq_fixed;
+    template <int D>
+    __device__ __forceinline__ bool rows(int b, int h, int qblk, int nthreads, int pairs, float *out, size_t &q0, size_t &k0, int &Tq, int &Tk,
+                                         size_t &orow0) const {
+        const int r0 = seg[b], Tb = seg[b + 1] - r0;
+        Tq = tq_fixed ? tq_fixed : Tb;
+        Tk = Tb - koff;
+        if (qblk * 32 >= Tq) return false;
+        q0 = q_seg ? (size_t)r0 : 0;
+        k0 = (size_t)(r0 + koff);
+        orow0 = tq_fixed ? (size_t)b * tq_fixed : (size_t)r0;
+        if (Tk > 0) return true;
+        // a row is 32 D bytes in either output form -- 8 D floats, or [hi 8 D | lo 8 D] halfs, and zero pairs are zero bytes.  Head h owns floats
+        // [h D, + D), or halfs [h D, + D) of each plane = floats [h D / 2, + D / 2) and [4 D + h D / 2, + D / 2)
+        for (int i = threadIdx.x; i < 32 * (D / 4); i += nthreads) {
+            const int r = i / (D / 4), c = 4 * (i % (D / 4)), row = qblk * 32 + r;
+            const int col = pairs ? (c < D / 2 ? h * (D / 2) + c : 4 * D + h * (D / 2) + c - D / 2) : h * D + c;
+            if (row < Tq) *reinterpret_cast<f32x4 *>(out + (orow0 + row) * (8 * D) + col) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+        return false;
     }
-#undef ATT_CHUNK
-#undef ATT_LOAD_K
-#undef ATT_LOAD_V
-#undef ATT_STORE_V
-#undef ATT_PV
-
-    // ---- merge the 4 waves' partials in wave order: out = sum_w O_w e^(m_w - M) / sum_w l_w e^(m_w - M)
-    __syncthreads();   // the merge area aliases the loop's buffers
-    float *sO = att_smem, *sM = att_smem + ATT_WAVES * NC * 16 * 64, *sL = sM + ATT_WAVES * 32;
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (kh == 0) { sM[wave * 32 + l31] = m_run; sL[wave * 32 + l31] = l_run; }
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sO[((wave * NC + c) * 16 + e) * 64 + lane] = o[c][e];
-    __syncthreads();
-    {
-        float M = sM[l31];
-#pragma unroll
-        for (int w = 1; w < ATT_WAVES; ++w) M = fmaxf(M, sM[w * 32 + l31]);
-        float a[ATT_WAVES], den = 0.f;
-#pragma unroll
-        for (int w = 0; w < ATT_WAVES; ++w) {
-            a[w] = expf(sM[w * 32 + l31] - M);   // exp(-inf) = 0 for a wave that had no chunk
-            den += sL[w * 32 + l31] * a[w];
-        }
-        const float inv = 1.f / den;
-        const int row = qblk * 32 + l31;
-#pragma unroll
-        for (int c = wave; c < NC; c += ATT_WAVES) {   // this wave finishes channel blocks wave, wave + 4, ..
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 r4;
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    float num = 0.f;
-#pragma unroll
-                    for (int w = 0; w < ATT_WAVES; ++w) num += sO[((w * NC + c) * 16 + 4 * g + e2) * 64 + lane] * a[w];
-                    r4[e2] = num * inv;
-                }
-                if (row < Tq) {
-                    if (pairs) {   // the rows as (hi, lo) fp16 pairs [hi 8 D | lo 8 D] for a split-pair to_out GEMM (gemm_x3.hip): split_f16's arithmetic
-                        f16x4 hi4, lo4;
-                        bool ov = false;
-#pragma unroll
-                        for (int e2 = 0; e2 < 4; ++e2) {
-                            _Float16 a_, b_;
-                            ov |= split_f16(r4[e2], a_, b_);
-                            hi4[e2] = a_; lo4[e2] = b_;
-                        }
-                        note_range(sat, ov);
-                        _Float16 *pr = reinterpret_cast<_Float16 *>(out) + ((size_t)b * Tq + row) * (16 * D) + h * D + 32 * c + 8 * g + 4 * kh;
-                        *reinterpret_cast<f16x4 *>(pr) = hi4;
-                        *reinterpret_cast<f16x4 *>(pr + 8 * D) = lo4;
-                    } else {
-                        *reinterpret_cast<f32x4 *>(out + ((size_t)b * Tq + row) * (8 * D) + h * D + 32 * c + 8 * g + 4 * kh) = r4;
-                    }
-                }
-            }
-        }
-    }
+};
+template <int D, int ATT_WAVES>
+__global__ __launch_bounds__(64 * ATT_WAVES, D == 128 ? HMV_ATT_OCC : 1) void attention_mfma_views_kernel(const float *__restrict__ q, int q_ld,
+        const float *__restrict__ k, const float *__restrict__ v, int kv_ld, const AttSeg sg, int nqb, float *__restrict__ out, int pairs, int *sat) {
+#define ATT_ROWS \
+    size_t q0_, k0_, orow0_; \
+    int Tq, Tk; \
+    if (!sg.rows<D>(b, h, qblk, 64 * ATT_WAVES, pairs, out, q0_, k0_, Tq, Tk, orow0_)) return; \
+    const float *qb = q + q0_ * q_ld + h * D; \
+    const float *kb = k + k0_ * ld + h * D, *vb = v + k0_ * ld + h * D;
+#define ATT_OROW orow0_ + row
+#include "attention_mfma_body.inc"
+#undef ATT_ROWS
+#undef ATT_OROW
 }
 // ------------------------------------------------------------------ attention on the fp16 matrix cores over (hi, lo) pairs (round 4)
 // The fp16-kernel modes' form of attention_mfma_kernel<128>: same decomposition (one workgroup per (sample, head, 32-query block), the
@@ -947,195 +790,26 @@ __device__ __forceinline__ f16x8 ax_cat(const f16x4 a, const f16x4 b) { return f
 // slots of step u are the eight consecutive channels 16 u + 8 kh + j for both operands.
 __global__ __launch_bounds__(64 * AX_WAVES, 2) void attention_x3_kernel(const _Float16 *__restrict__ q, int q_ld, int q_bstride,
         const _Float16 *__restrict__ k, const _Float16 *__restrict__ v, int kv_ld, int lo_off, int T, int Tq, int Tk, int nqb, float *__restrict__ out, int pairs) {
-    constexpr int D = 128, NC = 4;
-    extern __shared__ __attribute__((aligned(16))) char ax_smem[];
-    const int qblk = blockIdx.x % nqb, bh = blockIdx.x / nqb;
-    const int b = bh >> 3, h = bh & 7;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, kh = lane >> 5;
-    const size_t ld = (size_t)kv_ld;
-    const _Float16 *qb = q + (size_t)b * q_bstride * q_ld + h * D;
+#define AX_ROWS \
+    const _Float16 *qb = q + (size_t)b * q_bstride * q_ld + h * D; \
     const _Float16 *kb = k + (size_t)b * T * ld + h * D, *vb = v + (size_t)b * T * ld + h * D;
-    const int nkc = (Tk + 31) >> 5;
-    const float scale = 0.08838834764831845f;   // 128 ** -0.5
-    _Float16 *sQ = reinterpret_cast<_Float16 *>(ax_smem);                                   // [2][32][AX_QLD]
-    _Float16 *sVw = sQ + AX_Q_HALFS + wave * AX_V_HALFS;                                    // [2][16][AX_VLD], this wave's
-
-    f16x8 kh8[8], kl8[8], vh8[4], vl8[4];   // the chunk's key rows (8 steps x (hi, lo)); 16 of its value rows (16 keys x 128 channels = 4 + 4 vectors per lane)
-    int kc = wave;
-    // (keys >= Tk read the last valid row: their logits are set to -inf and their P to exactly 0 below, so only finiteness matters)
-#define AX_LOAD_K(KC)                                                                                   \
-    do {                                                                                                \
-        const _Float16 *krow_ = kb + (size_t)min((KC) * 32 + l31, Tk - 1) * ld + 8 * kh;                \
-        _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                 \
-            kh8[u] = *reinterpret_cast<const f16x8 *>(krow_ + 16 * u);                                  \
-            kl8[u] = *reinterpret_cast<const f16x8 *>(krow_ + lo_off + 16 * u);                         \
-        }                                                                                               \
-    } while (0)
-#define AX_LOAD_V(KEY0)                                                                                 \
-    do {                                                                                                \
-        _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                              \
-            const int k2_ = min((KEY0) + 4 * it + (lane >> 4), Tk - 1);   /* unit it * 64 + lane = key 4 it + (lane >> 4), channels 8 (lane & 15) .. */ \
-            vh8[it] = *reinterpret_cast<const f16x8 *>(vb + (size_t)k2_ * ld + 8 * (lane & 15));       \
-            vl8[it] = *reinterpret_cast<const f16x8 *>(vb + (size_t)k2_ * ld + lo_off + 8 * (lane & 15)); \
-        }                                                                                               \
-    } while (0)
-    // 16 keys -> the wave's LDS buffer, row-major
-#define AX_STORE_V()                                                                                    \
-    do {                                                                                                \
-        __builtin_amdgcn_wave_barrier();                                                                \
-        _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                              \
-            *reinterpret_cast<f16x8 *>(&sVw[(4 * it + (lane >> 4)) * AX_VLD + 8 * (lane & 15)]) = vh8[it]; \
-            *reinterpret_cast<f16x8 *>(&sVw[(16 + 4 * it + (lane >> 4)) * AX_VLD + 8 * (lane & 15)]) = vl8[it]; \
-        }                                                                                               \
-        __builtin_amdgcn_wave_barrier();                                                                \
-    } while (0)
-    // O^T += V^T P^T over the 16 keys of step S_: per 32-channel block two transposed reads per plane, three MFMAs
-#define AX_PV(S_)                                                                                       \
-    do {                                                                                                \
-        _Pragma("unroll") for (int c = 0; c < NC; ++c) {                                                \
-            const _Float16 *t0 = sVw + (4 * kh + ((lane & 15) >> 2)) * AX_VLD + 32 * c + 16 * ((lane >> 4) & 1) + 4 * (lane & 3); \
-            const f16x4 h0 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) atr4 *)(t0))); \
-            const f16x4 h1 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) atr4 *)(t0 + 8 * AX_VLD))); \
-            const f16x4 l0 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) atr4 *)(t0 + 16 * AX_VLD))); \
-            const f16x4 l1 = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) atr4 *)(t0 + 24 * AX_VLD))); \
-            const f16x8 ah_ = ax_cat(h0, h1), al_ = ax_cat(l0, l1);                                     \
-            o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, ph[S_], o[c], 0, 0, 0);                  \
-            o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al_, ph[S_], o[c], 0, 0, 0);                  \
-            o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, pl[S_], o[c], 0, 0, 0);                  \
-            if (c & 1) __builtin_amdgcn_sched_barrier(0);   /* (two blocks' operands in flight at a time: registers) */ \
-        }                                                                                               \
-    } while (0)
-    if (kc < nkc) {
-        AX_LOAD_K(kc);
-        AX_LOAD_V(kc * 32);
-    }
-    // Q block (rows >= Tq are zeros) -> LDS, shared by the waves: the rows as they are (slot j of step u, half kh = channel 16 u + 8 kh + j)
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int idx = it * 256 + tid, r = idx >> 4, c8 = 8 * (idx & 15), row = qblk * 32 + r;
-        f16x8 qh = {0, 0, 0, 0, 0, 0, 0, 0}, ql = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (row < Tq) {
-            qh = *reinterpret_cast<const f16x8 *>(qb + (size_t)row * q_ld + c8);
-            ql = *reinterpret_cast<const f16x8 *>(qb + (size_t)row * q_ld + lo_off + c8);
-        }
-        *reinterpret_cast<f16x8 *>(&sQ[r * AX_QLD + c8]) = qh;
-        *reinterpret_cast<f16x8 *>(&sQ[(32 + r) * AX_QLD + c8]) = ql;
-    }
-    __syncthreads();
-
-    f32x16 o[NC];   // o[c][e] on lane (q, half): O[q][32c + (e&3) + 8(e>>2) + 4 half]
-    float m_run = -INFINITY, l_run = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[c][e] = 0.f;
-
-    for (; kc < nkc; kc += AX_WAVES) {
-        f32x16 sacc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const f16x8 ah = kh8[u], al = kl8[u];
-            const f16x8 bh_ = *reinterpret_cast<const f16x8 *>(&sQ[l31 * AX_QLD + u * 16 + kh * 8]);
-            const f16x8 bl_ = *reinterpret_cast<const f16x8 *>(&sQ[(32 + l31) * AX_QLD + u * 16 + kh * 8]);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh_, sacc, 0, 0, 0);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh_, sacc, 0, 0, 0);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl_, sacc, 0, 0, 0);
-            if (u & 1) __builtin_amdgcn_sched_barrier(0);   // (two steps' operands at a time: the splits of all eight would not fit the registers)
-        }
-        // the key rows of this wave's NEXT chunk fly during the softmax and the P V products of this one (their registers are free)
-        if (kc + AX_WAVES < nkc) AX_LOAD_K(kc + AX_WAVES);
-        // register e = key (e&3) + 8(e>>2) + 4 half of the chunk, for query l31
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const bool kv_ = kc * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh < Tk;
-            sacc[e] = kv_ ? sacc[e] * scale : -INFINITY;
-            mx = fmaxf(mx, sacc[e]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));          // finite: the chunk has >= 1 valid key
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = expf(m_run - m_new);         // exp(-inf) = 0 on the first chunk
-        float psum = 0.f;
-        f16x8 ph[2], pl[2];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float pe = expf(sacc[e] - m_new);      // exp(-inf) = 0 for keys >= Tk
-            psum += pe;
-            const _Float16 a = (_Float16)pe;               // 0 <= pe <= 1: no clamp
-            ph[e >> 3][e & 7] = a;
-            pl[e >> 3][e & 7] = (_Float16)(pe - (float)a);
-        }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[c][e] *= alpha;
-        AX_STORE_V();
-        AX_LOAD_V(kc * 32 + 16);              // the second 16 value rows fly under the first 16 keys' products
-        AX_PV(0);
-        AX_STORE_V();
-        if (kc + AX_WAVES < nkc) AX_LOAD_V((kc + AX_WAVES) * 32);   // ... and the next chunk's first 16 value rows under the second
-        AX_PV(1);
-        __builtin_amdgcn_wave_barrier();
-    }
-#undef AX_LOAD_K
-#undef AX_LOAD_V
-#undef AX_STORE_V
-#undef AX_PV
-
-    // ---- merge the 4 waves' partials in wave order (attention_mfma_kernel's): out = sum_w O_w e^(m_w - M) / sum_w l_w e^(m_w - M)
-    __syncthreads();   // the merge area aliases the loop's buffers
-    float *att_smem = reinterpret_cast<float *>(ax_smem);
-    float *sO = att_smem, *sM = att_smem + AX_WAVES * NC * 16 * 64, *sL = sM + AX_WAVES * 32;
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (kh == 0) { sM[wave * 32 + l31] = m_run; sL[wave * 32 + l31] = l_run; }
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sO[((wave * NC + c) * 16 + e) * 64 + lane] = o[c][e];
-    __syncthreads();
-    {
-        float M = sM[l31];
-#pragma unroll
-        for (int w = 1; w < AX_WAVES; ++w) M = fmaxf(M, sM[w * 32 + l31]);
-        float a[AX_WAVES], den = 0.f;
-#pragma unroll
-        for (int w = 0; w < AX_WAVES; ++w) {
-            a[w] = expf(sM[w * 32 + l31] - M);   // exp(-inf) = 0 for a wave that had no chunk
-            den += sL[w * 32 + l31] * a[w];
-        }
-        const float inv = 1.f / den;
-        const int row = qblk * 32 + l31;
-        const int c = wave;   // this wave finishes channel block `wave`
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 r4;
-#pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) {
-                float num = 0.f;
-#pragma unroll
-                for (int w = 0; w < AX_WAVES; ++w) num += sO[((w * NC + c) * 16 + 4 * g + e2) * 64 + lane] * a[w];
-                r4[e2] = num * inv;
-            }
-            if (row < Tq) {
-                if (pairs) {
-                    f16x4 hi4, lo4;
-                    // (no range report here: a row is a convex combination of value rows that are pairs already, |r4| <= 65504 up to
-                    // rounding -- and a report in this loop changes how the compiler contracts the merge above, i.e. the bits)
-                    ax_split4(r4, hi4, lo4);
-                    _Float16 *pr = reinterpret_cast<_Float16 *>(out) + ((size_t)b * Tq + row) * (16 * D) + h * D + 32 * c + 8 * g + 4 * kh;
-                    *reinterpret_cast<f16x4 *>(pr) = hi4;
-                    *reinterpret_cast<f16x4 *>(pr + 8 * D) = lo4;
-                } else {
-                    *reinterpret_cast<f32x4 *>(out + ((size_t)b * Tq + row) * (8 * D) + h * D + 32 * c + 8 * g + 4 * kh) = r4;
-                }
-            }
-        }
-    }
+#define AX_OROW (size_t)b * Tq + row
+#include "attention_x3_body.inc"
+#undef AX_ROWS
+#undef AX_OROW
+}
+__global__ __launch_bounds__(64 * AX_WAVES, 2) void attention_x3_views_kernel(const _Float16 *__restrict__ q, int q_ld, const _Float16 *__restrict__ k,
+        const _Float16 *__restrict__ v, int kv_ld, int lo_off, const AttSeg sg, int nqb, float *__restrict__ out, int pairs) {
+#define AX_ROWS \
+    size_t q0_, k0_, orow0_; \
+    int Tq, Tk; \
+    if (!sg.rows<128>(b, h, qblk, 64 * AX_WAVES, pairs, out, q0_, k0_, Tq, Tk, orow0_)) return; \
+    const _Float16 *qb = q + q0_ * q_ld + h * D; \
+    const _Float16 *kb = k + k0_ * ld + h * D, *vb = v + k0_ * ld + h * D;
+#define AX_OROW orow0_ + row
+#include "attention_x3_body.inc"
+#undef AX_ROWS
+#undef AX_OROW
 }
 
 template <int D, int W>
@@ -1200,6 +874,77 @@ hipError_t launch_attention_d256(const float *q, int q_ld, int q_bstride, const 
                                  int Tq, float *out, hipStream_t s, int pairs, int *sat) {
     if (T <= 0 || Tq <= 0) return hipErrorInvalidValue;
     return launch_attention_any<256>(q, q_ld, q_bstride, k, v, kv_ld, B, T, Tq, T, out, s, pairs, sat);
+}
+
+// ------------------------------------------------------------------ ragged view sets: the launches around the attention
+// seg: device table [B + 1] of first token rows (AttSeg); Tmax: the longest sample's token count (sizes the grid); cross: the cross block
+// (queries = a sample's first 21 rows, keys = the rest, possibly none) instead of a self block
+template <int D>
+static hipError_t launch_attention_views_any(const float *q, int q_ld, const float *k, const float *v, int kv_ld, int B, const AttSeg &sg, int Tmax,
+                                             float *out, hipStream_t s, int pairs, int *sat) {
+    if (B <= 0 || Tmax <= 0 || !sg.seg) return hipErrorInvalidValue;
+    const int nqb = ((sg.tq_fixed ? sg.tq_fixed : Tmax) + 31) >> 5;
+    const int lds = AttShape<D, 4>::LDS_FLOATS * (int)sizeof(float);
+    static DeviceOnce once;
+    if (const hipError_t e = once.run([&](int) { return set_max_lds(lds, attention_mfma_views_kernel<D, 4>); }); e != hipSuccess) return e;
+    hipLaunchKernelGGL((attention_mfma_views_kernel<D, 4>), dim3((unsigned)B * 8 * nqb), dim3(64 * 4), lds, s, q, q_ld, k, v, kv_ld, sg, nqb, out, pairs, sat);
+    return hipGetLastError();
+}
+hipError_t launch_attention_views(const float *qkv, int B, const int *seg, int Tmax, int cross, float *out, hipStream_t s, int pairs, int x3, int *sat) {
+    const AttSeg sg{seg, 1, cross ? 21 : 0, cross ? 21 : 0};
+    if (x3) {
+        if (B <= 0 || Tmax <= 0 || !seg) return hipErrorInvalidValue;
+        static DeviceOnce once;
+        if (const hipError_t e = once.run([](int) { return set_max_lds(AX_LDS_BYTES, attention_x3_views_kernel); }); e != hipSuccess) return e;
+        const int nqb = ((cross ? 21 : Tmax) + 31) >> 5;
+        const _Float16 *ph = reinterpret_cast<const _Float16 *>(qkv);
+        hipLaunchKernelGGL(attention_x3_views_kernel, dim3((unsigned)B * 8 * nqb), dim3(64 * AX_WAVES), AX_LDS_BYTES, s, ph, 6 * 1024, ph + 1024, ph + 2048,
+                           6 * 1024, 3 * 1024, sg, nqb, out, pairs);
+        return hipGetLastError();
+    }
+    return launch_attention_views_any<128>(qkv, 3 * 1024, qkv + 1024, qkv + 2048, 3 * 1024, B, sg, Tmax, out, s, pairs, sat);
+}
+// 256-wide heads: q_seg = 1: query rows seg[b] + i of q (self block);  0: the 21 probe queries q, shared by every sample (cross block)
+hipError_t launch_attention_d256_views(const float *q, int q_ld, int q_seg, const float *k, const float *v, int kv_ld, int B, const int *seg, int Tmax,
+                                       float *out, hipStream_t s, int pairs, int *sat) {
+    return launch_attention_views_any<256>(q, q_ld, k, v, kv_ld, B, AttSeg{seg, q_seg, 0, q_seg ? 0 : 21}, Tmax, out, s, pairs, sat);
+}
+
+// add_pe_kernel with the position of a row taken from its frame: row r = frame r / 21, joint r % 21, position fpos[frame] + joint
+__global__ void add_pe_views_kernel(const float *__restrict__ x, int ldx, const int *__restrict__ fpos, int d, const float *__restrict__ pe,
+                                    float *__restrict__ y, int ldy, size_t total) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const size_t r = i / ldy;
+        const int c = (int)(i - r * ldy);
+        const size_t pos = (size_t)fpos[r / 21] + r % 21;
+        y[i] = c < d ? x[r * ldx + c] + pe[pos * (size_t)d + c] : 0.f;
+    }
+}
+hipError_t launch_add_pe_views(const float *x, int ldx, int rows, const int *fpos, int d, const float *pe, float *y, int ldy, hipStream_t s) {
+    const size_t total = (size_t)rows * ldy;
+    if (!total) return hipSuccess;
+    if (!fpos || rows % 21) return hipErrorInvalidValue;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(add_pe_views_kernel, dim3(grid), dim3(256), 0, s, x, ldx, fpos, d, pe, y, ldy, total);
+    return hipGetLastError();
+}
+
+// The cross block's residual `_q` = the first 21 rows of every sample: out[b * 21 + j][0, ld) = x[seg[b] + j][0, ld)  (ld % 4 == 0)
+__global__ void gather_query_rows_kernel(const float *__restrict__ x, const int *__restrict__ seg, int ld4, f32x4 *__restrict__ out, size_t total) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const size_t r = i / ld4;
+    const int c = (int)(i - r * ld4), b = (int)(r / 21), j = (int)(r % 21);
+    out[i] = reinterpret_cast<const f32x4 *>(x)[((size_t)seg[b] + j) * ld4 + c];
+}
+hipError_t launch_gather_query_rows(const float *x, int ld, const int *seg, int B, float *out, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (!seg || (ld & 3)) return hipErrorInvalidValue;
+    const size_t total = (size_t)B * 21 * (ld / 4);
+    hipLaunchKernelGGL(gather_query_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, seg, ld / 4, reinterpret_cast<f32x4 *>(out), total);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ split-K reduction

@@ -236,6 +236,62 @@ class HandMvNet(torch.nn.Module):
         self._last_key = (hh, ww, dev.index if dev.index is not None else torch.cuda.current_device(), batch, self._dtype)
         return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
 
+    def forward_views(self, x, view_mask, bbox=None, cam_params=None):
+        """forward() for a batch whose samples have different cameras: `x` is the full [b, v, 3, h, w] batch (v == num_views) and
+        `view_mask` a bool [b, v] tensor, array or nested list, True = the view is present.  Each sample's result is what the model
+        built with num_views = (its number of present views) computes from those views in camera order, from the same weights: the
+        backbone runs on the present frames only and the fusion attends over each sample's own tokens.  Same return dict and shapes
+        as forward(); the `joints_crop_img` and `heatmap` rows of absent views are zeros (as mask_joints zeroes both sides,
+        models/utils.py:123-131).  The mask is read on the host: pass it as a host tensor, array or list -- a device mask costs one
+        synchronising copy.  Present frames and their bbox / intrinsic rows are packed with one device gather each."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 5:
+            raise ValueError("x must be a [b, v, 3, h, w] tensor")
+        b, v, c, hh, ww = x.shape
+        if c != 3:
+            raise ValueError("x must have 3 channels")
+        if v != self.num_views:
+            raise ValueError(f"x must hold all {self.num_views} views per sample (absent ones are named by view_mask), got {v}")
+        mask = view_mask.detach().cpu().numpy() if isinstance(view_mask, torch.Tensor) else np.asarray(view_mask)
+        if mask.shape != (b, v):
+            raise ValueError(f"view_mask must have shape [{b}, {v}], got {list(mask.shape)}")
+        mask = mask.astype(bool)
+        counts = mask.sum(axis=1).astype(np.int32)
+        if b == 0 or (counts == 0).any():
+            raise ValueError("view_mask: every sample needs at least one present view"
+                             + (f" (sample {int(np.argmin(counts))} has none)" if b else ""))
+        if not x.is_cuda:
+            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
+        dev = x.device
+        n = int(counts.sum())
+        idx = torch.from_numpy(np.flatnonzero(mask.reshape(-1))).to(dev)   # present frames, sample-major, camera order
+        xp = x.reshape(b * v, 3, hh, ww).float().index_select(0, idx)
+        bb = it = None
+        if "crop" in self.cfg.pos_enc:
+            if bbox is None or cam_params is None:
+                raise TypeError("pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required")
+            bb = bbox.to(dev).reshape(-1, 4).float()
+            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).float()
+            if bb.shape[0] != b * v or it.shape[0] != b * v:
+                raise RuntimeError("bbox / intrinsic must hold one row per frame")
+            bb, it = bb.index_select(0, idx), it.index_select(0, idx)
+        didx = dev.index if dev.index is not None else torch.cuda.current_device()
+        h = self._engine(hh, ww, didx)
+        hs_h, hs_w = heatmap_size_of(self.cfg, hh, ww)
+        crop_p = torch.empty(n, 21, 2, device=dev, dtype=torch.float32)
+        hm_p = torch.empty(n, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
+        out_cam = torch.empty(b, 21, 3, device=dev, dtype=torch.float32)
+        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().hmv_forward_views(h, b, cnt, xp.data_ptr(), bb.data_ptr() if bb is not None else None,
+                                               it.data_ptr() if it is not None else None, crop_p.data_ptr(), out_cam.data_ptr(),
+                                               hm_p.data_ptr(), ctypes.c_void_p(stream))
+        _lib.check(rc, h)
+        self._last_key = (hh, ww, didx, b, self._dtype)
+        out_crop = torch.zeros(b * v, 21, 2, device=dev, dtype=torch.float32).index_copy_(0, idx, crop_p)
+        out_hm = torch.zeros(b * v, 21, hs_h, hs_w, device=dev, dtype=torch.float32).index_copy_(0, idx, hm_p)
+        return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
+
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                        image_size=None):
         """forward() from raw camera frames: `frames` uint8 [b, v, Hf, Wf, 3] and integer crop windows `crop_boxes`

@@ -154,6 +154,24 @@ int hmv_poison_workspace(hmv_handle h, int32_t value, void *stream);
 int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic,
                 float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
 
+/* hmv_forward for a batch whose samples have DIFFERENT CAMERAS: sample b brings view_counts[b] of the cfg.num_views views (a camera
+ * dropped out, the hand left a view, or an accuracy-against-view-count table is being produced).  Its result is what the model built with
+ * num_views = view_counts[b] computes from those views, fed in camera order, from the same weights: the backbone runs on the present
+ * frames only, and the fusion attends over each sample's own 21 * view_counts[b] tokens, positions counted over its present views.
+ *   view_counts     HOST, `batch` entries, each in [1, cfg.num_views]; read before the call returns
+ *   x               [sum view_counts][3][H][W] fp32, packed sample-major, a sample's present views in camera order
+ *   bbox, intrinsic [sum view_counts][4] each, packed the same way; may be NULL unless HMV_POS_CROP
+ *   joints_crop_img [sum view_counts][21][2]  out
+ *   joints_cam      [batch][21][3]            out
+ *   heatmap         [sum view_counts][21][H/8][W/8] out, may be NULL
+ * Asynchronous on `stream` like the uniform entry and without a device synchronisation: the per-sample row table is derived on the
+ * host and uploaded on `stream`.  One forward is in flight per handle, as ever.  A workspace reserved for `batch` samples serves a
+ * ragged call of up to `batch` samples.  Always runs eagerly (never replayed from the graph cache); records no stages -- reading a
+ * stage afterwards returns HMV_ERR_STATE; the range report covers it like any forward.
+ * HMV_ERR_ARG, before anything is launched, for: batch <= 0, a NULL table, a count of 0 or above cfg.num_views. */
+int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
+                      float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
+
 /* Human-readable description of the last failure on this handle, or with h == NULL of the calling thread's last failed call
  * without a handle (hmv_create, the hmv_op_* entries ...): per thread, like errno. */
 const char *hmv_last_error(hmv_handle h);
@@ -297,6 +315,17 @@ int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, 
  * on the fp32 matrix cores (the kernel template of the 128-wide heads at D = 256). */
 int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_bstride, const float *k, const float *v, int32_t kv_ld,
                         int32_t B, int32_t T, int32_t Tq, float *out, void *stream);
+
+/* The ragged forms of the three attention kernels on their own (what the ragged forward launches; op-level tests).  seg: HOST table of
+ * B + 1 first rows -- sample b owns rows seg[b] .. seg[b + 1] of the packed row matrix; seg[0] = 0.
+ *   kind 0  128-wide heads, fp32 matrix cores;  kind 1  the same over fp16 (hi, lo) pairs (the rows are split first);
+ *           qkv device [rows][3 * 1024] = [q | k | v] per row.  cross = 0: every row queries its sample's rows, out [rows][1024];
+ *           cross = 1: a sample's first 21 rows query the REST of its rows, out [B * 21][1024] -- exact zeros for a sample of 21 rows
+ *   kind 2  256-wide heads.  cross = 0: qkv device [rows][3 * 2048], out [rows][2048];  cross = 1: qkv holds [k | v] rows
+ *           [rows][2 * 2048], the queries are the 21 rows of `probe` [21][2048] for every sample, out [B * 21][2048]
+ * Synchronises the stream. */
+int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, const int32_t *seg, int32_t cross,
+                           float *out, void *stream);
 
 /* Diagnostic micro-benchmark: average milliseconds of `iters` launches of one NHWC conv shape on
  * pseudo-random data.  tile: -1 = the engine's own choice, else 0..7 = 128x32, 128x64, 128x128, 256x128,

@@ -14,7 +14,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_profile_get", "hmv_op_conv2d", "hmv_op_conv2d_ex", "hmv_op_conv2d_f16", "hmv_op_conv2d_sel", "hmv_op_conv2d_rd", "hmv_op_conv2d_as", "hmv_op_attention", "hmv_op_attention_lq", "hmv_bench_conv", "hmv_pose_metrics", "hmv_forward_frames",
            "hmv_op_prepare_frames", "hmv_set_graphs", "hmv_graph_stats", "hmv_version", "hmv_tile_rule", "hmv_profile_get_bytes", "hmv_poison_workspace", "hmv_launch_count", "hmv_set_tail_fusion", "hmv_set_chain_fusion", "hmv_set_hr_fusion", "hmv_op_conv2d_x3", "hmv_op_hr_fuse_up", "hmv_op_attention_x3",
            "hmv_range_status", "hmv_op_target_heatmaps", "hmv_project_joints", "hmv_pose_losses", "hmv_pose_losses_scratch_bytes",
-           "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views"]
+           "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views", "hmv_pose_losses_views",
+           "hmv_eval_add_views", "hmv_forward_frames_views"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -130,12 +131,19 @@ def load() -> ctypes.CDLL:
     lib.hmv_project_joints.restype = ctypes.c_int
     lib.hmv_pose_losses.argtypes = [ci, ctypes.POINTER(HmvLossArgs), fp, vp]
     lib.hmv_pose_losses.restype = ctypes.c_int
+    lib.hmv_pose_losses_views.argtypes = [ci, ctypes.POINTER(HmvLossArgs), fp, fp, vp]
+    lib.hmv_pose_losses_views.restype = ctypes.c_int
     lib.hmv_pose_losses_scratch_bytes.argtypes = [ci, ci]
     lib.hmv_pose_losses_scratch_bytes.restype = ctypes.c_size_t
     lib.hmv_eval_state_doubles.argtypes = [ci]
     lib.hmv_eval_state_doubles.restype = ctypes.c_size_t
     lib.hmv_eval_add.argtypes = [ci, ctypes.POINTER(HmvEvalArgs), vp]
     lib.hmv_eval_add.restype = ctypes.c_int
+    lib.hmv_eval_add_views.argtypes = [ci, ctypes.POINTER(HmvEvalArgs), fp, vp]
+    lib.hmv_eval_add_views.restype = ctypes.c_int
+    lib.hmv_forward_frames_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, ci, ci, fp, fp, ctypes.POINTER(ctypes.c_float),
+                                             ctypes.POINTER(ctypes.c_float), fp, fp, fp, fp, fp, vp]
+    lib.hmv_forward_frames_views.restype = ctypes.c_int
     lib.hmv_forward_frames.argtypes = [vp, ci, fp, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                        fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames.restype = ctypes.c_int

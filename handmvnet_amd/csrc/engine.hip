@@ -222,10 +222,12 @@ struct hmv_engine {
     float *cap_feat0 = nullptr, *cap_coords = nullptr, *cap_tokens = nullptr, *cap_fused = nullptr;
     size_t cap_feat0_n = 0, cap_coords_n = 0, cap_tokens_n = 0, cap_fused_n = 0;
 
-    // set only for the duration of hmv_forward_frames: raw camera frames instead of prepared NCHW input
+    // set only for the duration of hmv_forward_frames / hmv_forward_frames_views: raw camera frames instead of prepared NCHW input
     struct FrameSrc {
         const uint8_t *frames = nullptr;
         const int *boxes = nullptr;
+        const int *index = nullptr;   // hmv_forward_frames_views: packed frame n is frames / boxes [index[n]] of the caller's n_src
+        int n_src = 0;
         int fh = 0, fw = 0;
         float mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
     } fsrc;
@@ -1610,7 +1612,7 @@ struct Runner {
         const HrNet &hr = h->hr;
         const int H = h->cfg.height, W = h->cfg.width;
         Map in4 = act(N, H, W, 3, h16 ? 8 : 4);   // 4 fp32 / 8 fp16 / [hi8 | lo8] per pixel
-        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4.p, s));
+        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4.p, s, /*s2d=*/false, h->fsrc.index, h->fsrc.n_src));
         else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4.p, N, H, W, s, h->sat));
         else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4.p, N, H, W, s));
         else LAUNCH(launch_nchw_to_nhwc4(x, in4.p, N, H, W, s));
@@ -1731,7 +1733,7 @@ struct Runner {
         // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
         const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
         Map in4 = act(N, Hs, Ws, 12, h16 ? 16 : 12);
-        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4.p, s, /*s2d=*/true));
+        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4.p, s, /*s2d=*/true, h->fsrc.index, h->fsrc.n_src));
         else LAUNCH(launch_nchw_to_s2d(x, in4.p, N, H, W, smode, s, h->sat));
         const int H1 = conv_out(H, 7, 2, 3), W1 = conv_out(W, 7, 2, 3);   // == Hs, Ws
         const int hp = conv_out(H1, 3, 2, 1), wp = conv_out(W1, 3, 2, 1);
@@ -2200,27 +2202,30 @@ int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, 
     return forward_common(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
 }
 
-/* hmv_forward for a batch whose samples have different cameras (include/handmv.h).  Everything that can be refused is refused before the
- * first launch.  Always eager: the tables differ from call to call, so a ragged call never enters the graph replay cache. */
-int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
-                      float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
-    if (batch <= 0) return h->fail(HMV_ERR_ARG, "hmv_forward_views: batch must be positive (got %d)", (int)batch);
-    if (!view_counts) return h->fail(HMV_ERR_ARG, "hmv_forward_views: view_counts is null (one host entry per sample)");
-    if (!x || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "null or empty input/output");
+static int check_views(hmv_handle h, const char *who, int32_t batch, const int32_t *view_counts, const float *bbox, const float *intrinsic) {
+    if (batch <= 0) return h->fail(HMV_ERR_ARG, "%s: batch must be positive (got %d)", who, (int)batch);
+    if (!view_counts) return h->fail(HMV_ERR_ARG, "%s: view_counts is null (one host entry per sample)", who);
+    const int V = h->cfg.num_views;
+    for (int b = 0; b < batch; ++b) {
+        const int v = view_counts[b];
+        if (v < 1 || v > V)
+            return h->fail(HMV_ERR_ARG, "%s: view_counts[%d] = %d, every sample needs between 1 and num_views = %d present views", who, b, v, V);
+    }
+    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
+        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
+    return HMV_OK;
+}
+
+// the ragged forward behind hmv_forward_views (x) and hmv_forward_frames_views (h->fsrc set, x null); the arguments have been checked
+static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox,
+                                const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
     const int V = h->cfg.num_views;
     size_t N = 0;
     int vmax = 0;
     for (int b = 0; b < batch; ++b) {
-        const int v = view_counts[b];
-        if (v < 1 || v > V)
-            return h->fail(HMV_ERR_ARG, "hmv_forward_views: view_counts[%d] = %d, every sample needs between 1 and num_views = %d present views", b, v, V);
-        N += (size_t)v;
-        vmax = v > vmax ? v : vmax;
+        N += (size_t)view_counts[b];
+        vmax = view_counts[b] > vmax ? view_counts[b] : vmax;
     }
-    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
-        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (batch > h->reserved_batch) {
         const int rc = hmv_reserve(h, batch);
@@ -2287,6 +2292,43 @@ int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, c
     h->launches = 1;
     const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan, &vs);
     if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    return rc;
+}
+
+/* hmv_forward for a batch whose samples have different cameras (include/handmv.h).  Everything that can be refused is refused before the
+ * first launch.  Always eager: the tables differ from call to call, so a ragged call never enters the graph replay cache. */
+int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
+                      float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (batch > 0 && view_counts && (!x || !joints_crop_img || !joints_cam)) return h->fail(HMV_ERR_ARG, "null or empty input/output");
+    if (const int rc = check_views(h, "hmv_forward_views", batch, view_counts, bbox, intrinsic)) return rc;
+    return forward_views_common(h, batch, view_counts, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
+}
+
+/* hmv_forward_views from raw camera frames (include/handmv.h): the indexed frame preparation in front of the ragged forward. */
+int hmv_forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
+                             const int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std, const float *bbox,
+                             const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (const int rc = check_views(h, "hmv_forward_frames_views", batch, view_counts, bbox, intrinsic)) return rc;
+    if (!frames || !crop_boxes || !mean || !std || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "null or empty input/output");
+    if (frame_h <= 0 || frame_w <= 0) return h->fail(HMV_ERR_ARG, "frame size must be positive");
+    for (int c = 0; c < 3; ++c)
+        if (!(std[c] > 0.f)) return h->fail(HMV_ERR_ARG, "std must be positive");
+    h->fsrc.frames = frames;
+    h->fsrc.boxes = crop_boxes;
+    h->fsrc.index = frame_index;
+    h->fsrc.n_src = batch * h->cfg.num_views;
+    h->fsrc.fh = frame_h;
+    h->fsrc.fw = frame_w;
+    for (int c = 0; c < 3; ++c) { h->fsrc.mean[c] = mean[c]; h->fsrc.std[c] = std[c]; }
+    const int rc = forward_views_common(h, batch, view_counts, nullptr, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
+    h->fsrc.frames = nullptr;
+    h->fsrc.boxes = nullptr;
+    h->fsrc.index = nullptr;
+    h->fsrc.n_src = 0;
     return rc;
 }
 

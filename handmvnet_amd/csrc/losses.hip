@@ -171,56 +171,24 @@ __global__ __launch_bounds__(kThreads) void pose_losses_kernel(const float *__re
     double *prof = lds + kThreads;   // lds[0 .. kThreads): the reduction buffer
     const long f = blockIdx.x;
     const int t = threadIdx.x;
-    if (!target) fill_profiles(labels + f * NJ * 2, S, h, w, sigma, prof);
-    const int len = NJ * h * w;
-    const float *p = pred + f * len;
-    const float *g = target ? target + f * len : nullptr;
-    const bool vec = ((uintptr_t)p & 15) == 0 && (!g || ((uintptr_t)g & 15) == 0);
-    const int groups = (len + 3) / 4;
-    double acc = 0.0;
-    for (int q = t; q < groups; q += kThreads) {
-        const int e0 = q * 4;
-        const int cnt = min(4, len - e0);
-        float pv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (vec && cnt == 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(p + e0);
-            pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w;
-            if (g) {
-                const float4 b = *reinterpret_cast<const float4 *>(g + e0);
-                gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < cnt) {
-                    pv[k] = p[e0 + k];
-                    if (g) gv[k] = g[e0 + k];
-                }
-        }
-        if (!g) {   // target_at(prof, e0 + k, h, w) for the group, with the (joint, row, column) split done once
-            const int hw = h * w;
-            int j = e0 / hw;
-            const int rem = e0 - j * hw;
-            int y = rem / w, x = rem - y * w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < cnt) {
-                    const double *pj = prof + j * (h + w);
-                    gv[k] = (float)(pj[w + y] * pj[x]);
-                    if (++x == w) {
-                        x = 0;
-                        if (++y == h) { y = 0; ++j; }
-                    }
-                }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // lanes past the end hold 0 - 0
-            const double d = (double)pv[k] - (double)gv[k];
-            acc = fma(d, d, acc);
-        }
+#include "pose_losses_body.inc"
+}
+
+// (c) for a ragged view set, first launch: the same per frame slot; the workgroup of an ABSENT slot writes partial 0 and leaves before
+// it touches LDS or a barrier (the test depends on the slot only: the whole workgroup takes it), so nothing of that slot is read and
+// no target map is synthesised for it.
+__global__ __launch_bounds__(kThreads) void pose_losses_views_kernel(const float *__restrict__ pred, const float *__restrict__ target,
+                                                                    const float *__restrict__ labels, int S, int h, int w, int sigma,
+                                                                    const uint8_t *__restrict__ present, double *__restrict__ partial) {
+    extern __shared__ double lds[];
+    const long f = blockIdx.x;
+    const int t = threadIdx.x;
+    if (!present[f]) {
+        if (t == 0) partial[f] = 0.0;
+        return;
     }
-    const double s = block_sum(acc, lds);
-    if (t == 0) partial[f] = s;
+    double *prof = lds + kThreads;
+#include "pose_losses_body.inc"
 }
 
 struct FinishParams {
@@ -290,6 +258,92 @@ __global__ __launch_bounds__(kThreads) void pose_losses_finish_kernel(FinishPara
     }
 }
 
+// Present views of one sample: its row of the view mask, counted.
+__device__ __forceinline__ int count_views(const uint8_t *__restrict__ row, int V) {
+    int n = 0;
+    for (int v = 0; v < V; ++v) n += row[v] != 0;
+    return n;
+}
+
+constexpr int kCountSlots = 1024;   // samples whose count is kept in LDS; a sample beyond them has its mask row counted when asked
+
+// (c) for a ragged view set, second launch (one workgroup).  The value of a view-dependent term is the mean over samples of the
+// sample's own mean over its v_b present views: sum_b sum_{v in P_b} x / (v_b * n) / B.  Written as
+//     sum over ALL slots, in the uniform kernel's order, of (present ? x : 0) * (V / v_b),  divided by the uniform divisor B * V * n,
+// so that a full mask (V / v_b == 1.0 exactly) walks through the uniform kernel's additions and gives its bits.  An absent slot's
+// rows are not read.  A sample WITHOUT a present view (a broken precondition) has V / 0 = inf, its slots add 0 * inf: the
+// view-dependent terms come out NaN, and nothing is indexed by a count.
+__global__ __launch_bounds__(kThreads) void pose_losses_views_finish_kernel(FinishParams a, const uint8_t *__restrict__ present) {
+    __shared__ double red[kThreads];
+    __shared__ int cnt[kCountSlots];
+    const int t = threadIdx.x;
+    for (int b = t; b < a.B && b < kCountSlots; b += kThreads) cnt[b] = count_views(present + (long)b * a.V, a.V);
+    __syncthreads();
+    auto weight = [&](long b) { return (double)a.V / (double)(b < kCountSlots ? cnt[b] : count_views(present + b * a.V, a.V)); };
+
+    const long frames = (long)a.B * a.V;
+    double s = 0.0;
+    for (long i = t; i < frames; i += kThreads) s += a.partial[i] * weight(i / a.V);   // an absent slot's partial is the first launch's 0
+    const double hm = block_sum(s, red);
+
+    const long n2 = frames * NJ * 2;
+    s = 0.0;
+    for (long e = t; e < n2; e += kThreads) {
+        const long bv = e / (NJ * 2);
+        double d = 0.0;
+        if (present[bv]) {
+            const double keep = (a.use_mask && a.mask[e >> 1]) ? 0.0 : 1.0;
+            d = fabs((double)a.pred_2d[e] * keep - (double)a.gt_2d[e] * keep);
+        }
+        s += d * weight(bv / a.V);
+    }
+    const double l2d = block_sum(s, red);
+
+    const long n3 = (long)a.B * NJ * 3;
+    s = 0.0;
+    for (long e = t; e < n3; e += kThreads) s += fabs((double)a.pred_cam[e] - (double)a.gt_cam[e]);
+    const double l3d = block_sum(s, red);
+
+    double g2d = 0.0, p2d = 0.0;
+    if (a.with_projection) {
+        double sg = 0.0, sp = 0.0;
+        for (long i = t; i < frames * NJ; i += kThreads) {
+            const long bv = i / NJ;
+            const int j = (int)(i - bv * NJ);
+            const long b = bv / a.V;
+            double u = 0.0, v = 0.0, dg = 0.0, dp = 0.0;
+            if (present[bv]) {   // the camera tables are full [B][V]: the root camera's row is read whether or not its frame is present
+                project_joint(a.pred_cam + (b * NJ + j) * 3, a.root_joint ? a.root_joint + b * 3 : nullptr,
+                              a.extrinsic + (b * a.V + a.root_idx) * 16, a.extrinsic + bv * 16, a.intrinsic + bv * 4, a.bbox + bv * 4, u, v);
+                dg = fabs(u - (double)a.gt_2d[i * 2]) + fabs(v - (double)a.gt_2d[i * 2 + 1]);
+                dp = fabs(u - (double)a.pred_2d[i * 2]) + fabs(v - (double)a.pred_2d[i * 2 + 1]);
+            }
+            if (a.projected) {   // zeros for an absent slot
+                a.projected[i * 2] = (float)u;
+                a.projected[i * 2 + 1] = (float)v;
+            }
+            const double wgt = weight(b);
+            sg += dg * wgt;
+            sp += dp * wgt;
+        }
+        g2d = block_sum(sg, red);
+        p2d = block_sum(sp, red);
+    }
+    if (t == 0) {
+        const double t_hm = (double)a.w_hm * hm / ((double)frames * NJ * a.hm_h * a.hm_w);
+        const double t_2d = (double)a.w_2d * l2d / (double)n2;
+        const double t_3d = (double)a.w_3d * l3d / (double)n3;
+        const double t_g = a.with_projection ? (double)a.w_g2d * g2d / (double)n2 : 0.0;
+        const double t_p = a.with_projection ? (double)a.w_p2d * p2d / (double)n2 : 0.0;
+        a.result[0] = (float)t_hm;
+        a.result[1] = (float)t_2d;
+        a.result[2] = (float)t_3d;
+        a.result[3] = (float)t_g;
+        a.result[4] = (float)t_p;
+        a.result[5] = (float)(t_hm + t_2d + t_3d + t_g + t_p);
+    }
+}
+
 int bad_arg(const char *entry, const char *what) {
     hmv::set_thread_error(std::string(entry) + ": " + what);
     return HMV_ERR_ARG;
@@ -348,8 +402,10 @@ extern "C" size_t hmv_pose_losses_scratch_bytes(int32_t B, int32_t V) {
     return B > 0 && V > 0 ? sizeof(double) * (size_t)B * (size_t)V : 0;
 }
 
-extern "C" int hmv_pose_losses(int32_t device, const hmv_loss_args *a, float *result, void *stream) {
-    const char *who = "hmv_pose_losses";
+namespace {
+
+// the argument rules of the two loss entries, in front of every HIP call; 0 or the HMV_ERR_ARG of the first broken one
+int check_loss_args(const char *who, const hmv_loss_args *a, const float *result) {
     if (!a) return bad_arg(who, "args is NULL");
     if (a->struct_size != (int32_t)sizeof(hmv_loss_args)) return bad_arg(who, "struct_size does not match this library's hmv_loss_args");
     if (!result) return bad_arg(who, "result is NULL");
@@ -375,16 +431,12 @@ extern "C" int hmv_pose_losses(int32_t device, const hmv_loss_args *a, float *re
     if (!a->scratch || ((uintptr_t)a->scratch & 7)) return bad_arg(who, "scratch is NULL or not 8-byte aligned");
     if (a->scratch_bytes < hmv_pose_losses_scratch_bytes(a->B, a->V))
         return bad_arg(who, "scratch_bytes is smaller than hmv_pose_losses_scratch_bytes gives for B, V");
-    if (hipSetDevice(device) != hipSuccess) return hip_fail(who, hipGetLastError());
-    hipStream_t s = (hipStream_t)stream;
-    double *partial = static_cast<double *>(a->scratch);
-    const size_t lds = sizeof(double) * (kThreads + (a->target_heatmap ? 0 : NJ * (size_t)(a->hm_h + a->hm_w)));
-    hipLaunchKernelGGL(pose_losses_kernel, dim3((unsigned)(a->B * a->V)), dim3(kThreads), lds, s, a->pred_heatmap, a->target_heatmap,
-                       a->gt_joints_2d, a->image_size, a->hm_h, a->hm_w, a->sigma, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(who, e);
+    return HMV_OK;
+}
+
+FinishParams finish_params(const hmv_loss_args *a, float *result) {
     FinishParams f;
-    f.partial = partial;
+    f.partial = static_cast<const double *>(a->scratch);
     f.pred_2d = a->pred_joints_2d; f.gt_2d = a->gt_joints_2d; f.pred_cam = a->pred_joints_cam; f.gt_cam = a->gt_joints_cam;
     f.root_joint = a->root_joint; f.intrinsic = a->intrinsic; f.extrinsic = a->extrinsic; f.bbox = a->bbox;
     f.mask = a->joints_mask;
@@ -393,7 +445,40 @@ extern "C" int hmv_pose_losses(int32_t device, const hmv_loss_args *a, float *re
     f.use_mask = a->joints_mask && a->mask_invisible_joints;
     f.with_projection = a->with_projection != 0;
     f.w_hm = a->w_heatmap; f.w_2d = a->w_joints_2d; f.w_3d = a->w_joints_3d; f.w_g2d = a->w_g2d; f.w_p2d = a->w_p2d;
-    hipLaunchKernelGGL(pose_losses_finish_kernel, dim3(1), dim3(kThreads), 0, s, f);
+    return f;
+}
+
+}  // namespace
+
+extern "C" int hmv_pose_losses(int32_t device, const hmv_loss_args *a, float *result, void *stream) {
+    const char *who = "hmv_pose_losses";
+    if (const int rc = check_loss_args(who, a, result)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return hip_fail(who, hipGetLastError());
+    hipStream_t s = (hipStream_t)stream;
+    double *partial = static_cast<double *>(a->scratch);
+    const size_t lds = sizeof(double) * (kThreads + (a->target_heatmap ? 0 : NJ * (size_t)(a->hm_h + a->hm_w)));
+    hipLaunchKernelGGL(pose_losses_kernel, dim3((unsigned)(a->B * a->V)), dim3(kThreads), lds, s, a->pred_heatmap, a->target_heatmap,
+                       a->gt_joints_2d, a->image_size, a->hm_h, a->hm_w, a->sigma, partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(who, e);
+    hipLaunchKernelGGL(pose_losses_finish_kernel, dim3(1), dim3(kThreads), 0, s, finish_params(a, result));
+    e = hipGetLastError();
+    return e == hipSuccess ? HMV_OK : hip_fail(who, e);
+}
+
+extern "C" int hmv_pose_losses_views(int32_t device, const hmv_loss_args *a, const uint8_t *view_present, float *result, void *stream) {
+    const char *who = "hmv_pose_losses_views";
+    if (const int rc = check_loss_args(who, a, result)) return rc;
+    if (!view_present) return bad_arg(who, "view_present is NULL (hmv_pose_losses is the entry for a batch with every view)");
+    if (hipSetDevice(device) != hipSuccess) return hip_fail(who, hipGetLastError());
+    hipStream_t s = (hipStream_t)stream;
+    double *partial = static_cast<double *>(a->scratch);
+    const size_t lds = sizeof(double) * (kThreads + (a->target_heatmap ? 0 : NJ * (size_t)(a->hm_h + a->hm_w)));
+    hipLaunchKernelGGL(pose_losses_views_kernel, dim3((unsigned)(a->B * a->V)), dim3(kThreads), lds, s, a->pred_heatmap, a->target_heatmap,
+                       a->gt_joints_2d, a->image_size, a->hm_h, a->hm_w, a->sigma, view_present, partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(who, e);
+    hipLaunchKernelGGL(pose_losses_views_finish_kernel, dim3(1), dim3(kThreads), 0, s, finish_params(a, result), view_present);
     e = hipGetLastError();
     return e == hipSuccess ? HMV_OK : hip_fail(who, e);
 }

@@ -1131,67 +1131,55 @@ __device__ __forceinline__ void frame_pixel(const uint8_t *__restrict__ frames, 
         pb = (acc[2] - nm.mean[2]) * nm.inv_std[2];
 }
 
-// OUT: 0 = NHWC4 fp32, 1 = NHWC8 fp16, 2 = split [hi8 | lo8] fp16 pairs (HMV_F32X3)
-template <int OUT>
-__global__ void frames_to_input_kernel(const uint8_t *__restrict__ frames, const int *__restrict__ boxes, int Hf, int Wf, int S_h,
-                                       int S_w, FrameNorm nm, void *__restrict__ out, size_t total) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const int ox = (int)(i % S_w);
-        size_t t = i / S_w;
-        const int oy = (int)(t % S_h);
-        const size_t n = t / S_h;
-        float r, g, b;
-        frame_pixel(frames, boxes, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b);
-        if (OUT == 2) {
-            f16x8 hv = {0, 0, 0, 0, 0, 0, 0, 0}, lv = {0, 0, 0, 0, 0, 0, 0, 0};
-            _Float16 a, c;
-            split_f16(r, a, c); hv[0] = a; lv[0] = c;
-            split_f16(g, a, c); hv[1] = a; lv[1] = c;
-            split_f16(b, a, c); hv[2] = a; lv[2] = c;
-            reinterpret_cast<f16x8 *>(out)[2 * i] = hv;
-            reinterpret_cast<f16x8 *>(out)[2 * i + 1] = lv;
-        } else if (OUT == 1) {
-            f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            v[0] = (_Float16)r; v[1] = (_Float16)g; v[2] = (_Float16)b;
-            reinterpret_cast<f16x8 *>(out)[i] = v;
-        } else {
-            reinterpret_cast<f32x4 *>(out)[i] = f32x4{r, g, b, 0.f};
-        }
+#define FRAMES_TO_INPUT_KERNEL frames_to_input_kernel
+#define FRAMES_TO_S2D_KERNEL frames_to_s2d_kernel
+#define FRAMES_EXTRA_PARAMS
+#define FRAME_PIXEL(n, oy, ox, r, g, b) frame_pixel(frames, boxes, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b)
+#include "frames_to_input_body.inc"
+#undef FRAMES_TO_INPUT_KERNEL
+#undef FRAMES_TO_S2D_KERNEL
+#undef FRAMES_EXTRA_PARAMS
+#undef FRAME_PIXEL
+
+// The same for a ragged view set (hmv_forward_frames_views): output frame n is prepared from frames[index[n]] with the window
+// boxes[index[n]] -- the uint8 frames stay where the caller has them, nothing is gathered.  An index outside [0, n_src) gives the black
+// view of an empty window instead of a read outside the caller's frames.
+__device__ __forceinline__ void frame_pixel_indexed(const uint8_t *__restrict__ frames, const int *__restrict__ boxes,
+                                                    const int *__restrict__ index, int n_src, size_t n, int oy, int ox, int Hf, int Wf,
+                                                    int S_h, int S_w, const FrameNorm &nm, float &pr, float &pg, float &pb) {
+    const int src = index[n];
+    if (src >= 0 && src < n_src) {
+        frame_pixel(frames, boxes, (size_t)src, oy, ox, Hf, Wf, S_h, S_w, nm, pr, pg, pb);
+    } else {
+        pr = -nm.mean[0] * nm.inv_std[0];
+        pg = -nm.mean[1] * nm.inv_std[1];
+        pb = -nm.mean[2] * nm.inv_std[2];
     }
 }
-// the same into the space-to-depth stem layout (nchw_to_s2d_kernel above): one thread per s2d pixel = 2 x 2 output pixels
-template <int MODE>
-__global__ void frames_to_s2d_kernel(const uint8_t *__restrict__ frames, const int *__restrict__ boxes, int Hf, int Wf, int S_h,
-                                     int S_w, int Hs, int Ws, FrameNorm nm, void *__restrict__ out, size_t total) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const int xs = (int)(i % Ws);
-        size_t t = i / Ws;
-        const int ys = (int)(t % Hs);
-        const size_t n = t / Hs;
-        float v[12];
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int oy = 2 * ys + dy, ox = 2 * xs + dx, j = (dy * 2 + dx) * 3;
-                v[j] = v[j + 1] = v[j + 2] = 0.f;
-                if (oy < S_h && ox < S_w) frame_pixel(frames, boxes, n, oy, ox, Hf, Wf, S_h, S_w, nm, v[j], v[j + 1], v[j + 2]);
-            }
-        s2d_store<MODE>(out, i, v);
-    }
-}
+#define FRAMES_TO_INPUT_KERNEL frames_to_input_indexed_kernel
+#define FRAMES_TO_S2D_KERNEL frames_to_s2d_indexed_kernel
+#define FRAMES_EXTRA_PARAMS const int *__restrict__ index, int n_src,
+#define FRAME_PIXEL(n, oy, ox, r, g, b) frame_pixel_indexed(frames, boxes, index, n_src, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b)
+#include "frames_to_input_body.inc"
+#undef FRAMES_TO_INPUT_KERNEL
+#undef FRAMES_TO_S2D_KERNEL
+#undef FRAMES_EXTRA_PARAMS
+#undef FRAME_PIXEL
+
 hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N, int Hf, int Wf, int S_h, int S_w, const float *mean,
-                                  const float *std, int out_mode, void *out, hipStream_t s, bool s2d) {
+                                  const float *std, int out_mode, void *out, hipStream_t s, bool s2d, const int *index, int n_src) {
     FrameNorm nm;
     for (int c = 0; c < 3; ++c) { nm.mean[c] = mean[c]; nm.inv_std[c] = 1.f / std[c]; }
     if (s2d) {
         const int Hs = (S_h + 1) / 2, Ws = (S_w + 1) / 2;
         const size_t total = (size_t)N * Hs * Ws;
         const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+        if (index) {
+            if (out_mode == 2) hipLaunchKernelGGL(frames_to_s2d_indexed_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            else if (out_mode == 1) hipLaunchKernelGGL(frames_to_s2d_indexed_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            else hipLaunchKernelGGL(frames_to_s2d_indexed_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            return hipGetLastError();
+        }
         if (out_mode == 2) hipLaunchKernelGGL(frames_to_s2d_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
         else if (out_mode == 1) hipLaunchKernelGGL(frames_to_s2d_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
         else hipLaunchKernelGGL(frames_to_s2d_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
@@ -1199,6 +1187,12 @@ hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N
     }
     const size_t total = (size_t)N * S_h * S_w;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    if (index) {
+        if (out_mode == 2) hipLaunchKernelGGL(frames_to_input_indexed_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, nm, out, total);
+        else if (out_mode == 1) hipLaunchKernelGGL(frames_to_input_indexed_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, nm, out, total);
+        else hipLaunchKernelGGL(frames_to_input_indexed_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, nm, out, total);
+        return hipGetLastError();
+    }
     if (out_mode == 2) hipLaunchKernelGGL(frames_to_input_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, nm, out, total);
     else if (out_mode == 1) hipLaunchKernelGGL(frames_to_input_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, nm, out, total);
     else hipLaunchKernelGGL(frames_to_input_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, Hf, Wf, S_h, S_w, nm, out, total);

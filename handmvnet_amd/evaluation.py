@@ -13,6 +13,13 @@ The epoch value.  For every quantity it is
 the batch-size-weighted mean that Lightning's ``self.log(..., on_epoch=True)`` produces from the per-step values the reference logs.
 MPJPE, PA-MPJPE, 2D MPJPE and the PCK curve are linear in the rows, so for them this equals the value on the pooled split and does
 not depend on how the split is cut into batches and ranks; AUC is the trapezoid of that pooled curve (linear in the curve as well).
+Ragged view sets.  A batch may carry ``batch["view_mask"]`` (bool [B, V], True = the view is present; keep it on the HOST, where
+``forward_views`` reads it).  The step then runs ``forward_views``, the ragged loss (``hmv_pose_losses_views``) and the ragged
+accumulation (``hmv_eval_add_views``): still one loss call and one accumulation launch, nothing copied to the host.  The value of a
+view-dependent quantity on such a batch is the mean over its samples of the value the reference logs for that sample alone over its
+present views, so the epoch value again does not depend on the cut into batches and ranks; for a full mask it is the uniform value.
+``view_mask_from_joints`` derives the mask from the ``joints_img_mask`` a reference batch already carries.
+
 Lightning is not a dependency of this package, so the ``_epoch`` / ``_step`` suffixes its loggers add to a key logged with both
 ``on_step`` and ``on_epoch`` cannot be pinned and are not reproduced: the keys are the names the reference passes to ``self.log``.
 """
@@ -26,10 +33,18 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .losses import TERMS, _device_f32, _index
+from .losses import TERMS, _device_f32, _index, device_view_mask
 
 STEPS = 20       # thresholds of the PCK curve (handmvnet.py:359-363)
 _SCALARS = 14    # state[0 .. 14): counts and sums, then the steps + 1 histogram bins (include/handmv.h: "State layout")
+
+
+def view_mask_from_joints(joints_img_mask):
+    """joints_img_mask [..., V, 21] (True = the joint is invisible; tensor or array) -> view mask [..., V], True = the view is present:
+    a view is absent when none of its joints is visible, the dataset's own rule for feeding a black image (datasets/ho3d.py:138-140)."""
+    if isinstance(joints_img_mask, torch.Tensor):
+        return ~joints_img_mask.bool().all(-1)
+    return ~np.asarray(joints_img_mask).astype(bool).all(-1)
 
 
 def reduce_state(state: torch.Tensor, group=None) -> torch.Tensor:
@@ -88,9 +103,11 @@ class EpochEvaluator:
             raise ValueError(f"this epoch's state is on {self.state.device}, the step on {dev}")
         return self.state
 
-    def add(self, out: dict, inputs: dict, cam_params) -> None:
+    def add(self, out: dict, inputs: dict, cam_params, view_mask=None) -> None:
         """One step from the forward's `out` and the labels as _eval_step passes them (joints_cam / root_joint in metres): the loss
-        when the batch carries loss labels, then one hmv_eval_add on the current stream.  Returns nothing; nothing reaches the host."""
+        when the batch carries loss labels, then one hmv_eval_add on the current stream.  Returns nothing; nothing reaches the host.
+        view_mask (bool [B, V], True = present): `out` is forward_views' and the step is a ragged one -- the ragged loss and
+        hmv_eval_add_views; rows of absent views are not read."""
         pc = _device_f32("out['joints_cam']", out["joints_cam"])
         dev = pc.device
         p2 = _device_f32("out['joints_crop_img']", out["joints_crop_img"], dev)
@@ -112,14 +129,23 @@ class EpochEvaluator:
             a.joints_mask = mk.data_ptr()
             keep.append(mk)
         if "heatmap" in inputs or self.model.heatmap_targets == "joints":   # _eval_step's rule
-            self.model._calculate_loss(out, inputs, cam_params, mode=self.mode)
+            if view_mask is None:
+                self.model._calculate_loss(out, inputs, cam_params, mode=self.mode)
+            else:
+                self.model._calculate_loss(out, inputs, cam_params, mode=self.mode, view_mask=view_mask)
             loss = self.model.last_loss_vector
             a.loss_result = loss.data_ptr()
             keep.append(loss)
         state = self._state_on(dev)
         a.state, a.state_doubles = state.data_ptr(), state.numel()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
-            rc = _lib.load().hmv_eval_add(_index(dev), ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if view_mask is None:
+                rc = _lib.load().hmv_eval_add(_index(dev), ctypes.byref(a), stream)
+            else:
+                present = device_view_mask(view_mask, B, V, dev)
+                keep.append(present)
+                rc = _lib.load().hmv_eval_add_views(_index(dev), ctypes.byref(a), present.data_ptr(), stream)
         _lib.check(rc)
         del keep   # allocated on the stream the kernel runs on: the caching allocator reuses them in stream order
 
@@ -127,11 +153,18 @@ class EpochEvaluator:
         """forward + add for one batch of the reference's DataLoader layout; like the reference's test_step it converts
         inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE.  Returns the forward's output dictionary."""
         inputs = batch["data"]
-        out = self.model.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
+        view_mask = batch.get("view_mask")
+        if view_mask is None:
+            out = self.model.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
+        else:   # raises ValueError for a sample without a present view, before anything is launched
+            out = self.model.forward_views(inputs["rgb"], view_mask, inputs["bboxes"], batch["cam_params"])
         inputs["joints_cam"] /= 1000
         if "root_joint" in inputs:
             inputs["root_joint"] /= 1000
-        self.add(out, inputs, batch["cam_params"])
+        if view_mask is None:
+            self.add(out, inputs, batch["cam_params"])
+        else:
+            self.add(out, inputs, batch["cam_params"], view_mask=view_mask)
         return out
 
     def reduce(self, group=None) -> None:

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -113,24 +114,43 @@ def build_loss_args(pred_heatmap, pred_joints_2d, pred_joints_cam, gt_joints_2d,
     return a, dev, projected, keep
 
 
-def run_loss_args(args, dev: torch.device) -> torch.Tensor:
-    """hmv_pose_losses on `dev`'s current stream -> the device fp32 [6] result (order of TERMS).  Nothing synchronises."""
+def run_loss_args(args, dev: torch.device, view_present: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hmv_pose_losses -- with `view_present` (device uint8 [B, V]) hmv_pose_losses_views -- on `dev`'s current stream -> the device
+    fp32 [6] result (order of TERMS).  Nothing synchronises."""
     result = torch.empty(6, device=dev, dtype=torch.float32)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
-        rc = _lib.load().hmv_pose_losses(_index(dev), ctypes.byref(args), result.data_ptr(),
-                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if view_present is None:
+            rc = _lib.load().hmv_pose_losses(_index(dev), ctypes.byref(args), result.data_ptr(), stream)
+        else:
+            rc = _lib.load().hmv_pose_losses_views(_index(dev), ctypes.byref(args), view_present.data_ptr(), result.data_ptr(), stream)
     _lib.check(rc)
     return result
 
 
-def pose_losses(*args, **kwargs):
+def device_view_mask(view_mask, B: int, V: int, dev: torch.device) -> torch.Tensor:
+    """view_mask (bool [B, V] tensor on any device, or array-like; True = the view is present) -> the device uint8 [B, V] the ragged
+    entries read.  No synchronisation: that every sample has a present view is the caller's precondition (forward_views checks it)."""
+    m = view_mask if isinstance(view_mask, torch.Tensor) else torch.as_tensor(np.asarray(view_mask))
+    if tuple(m.shape) != (B, V):
+        raise ValueError(f"view_mask must have shape [{B}, {V}], got {list(m.shape)}")
+    return m.detach().to(dev).ne(0).to(torch.uint8).contiguous()
+
+
+def pose_losses(*args, view_mask=None, **kwargs):
     """One hmv_pose_losses call.  pred_heatmap [B, V, 21, h, w], *_joints_2d [B, V, 21, 2], *_joints_cam [B, 21, 3] (metres).
     weights: train_params["loss_weights"] (heatmap, joints_2d, joints_3d and optionally g2d + p2d: then root_joint [B, 3],
     intrinsic, extrinsic and bbox are read).  target_heatmap None: the targets are synthesised from gt_joints_2d, image_size, sigma.
     -> (result, projected): result device fp32 [6] in the order of TERMS, projected [B, V, 21, 2] or None.  Labels on the host are
-    moved to the predictions' device; nothing synchronises."""
+    moved to the predictions' device; nothing synchronises.
+    view_mask (bool [B, V] on any device, or array-like; True = present): a ragged view set, hmv_pose_losses_views -- every term is
+    the mean over samples of the sample's own value over its present views (include/handmv.h); the tensors keep the full [B, V]
+    layout, rows of absent views are not read, `projected` is zero there.  Every sample needs a present view (not checked here: that
+    would synchronise; a sample without one makes the view-dependent terms NaN).  None: the uniform call."""
     a, dev, projected, keep = build_loss_args(*args, **kwargs)
-    result = run_loss_args(a, dev)
+    present = None if view_mask is None else device_view_mask(view_mask, a.B, a.V, dev)
+    result = run_loss_args(a, dev, present)
+    del present
     del keep   # temporaries were allocated on the stream the kernels run on: the caching allocator reuses them in stream order
     return result, projected
 

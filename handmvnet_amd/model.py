@@ -236,6 +236,20 @@ class HandMvNet(torch.nn.Module):
         self._last_key = (hh, ww, dev.index if dev.index is not None else torch.cuda.current_device(), batch, self._dtype)
         return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
 
+    @staticmethod
+    def _host_view_mask(view_mask, b: int, v: int):
+        """view_mask (tensor, array or nested list) -> (bool array [b, v], int32 counts [b]) on the host; ValueError for a wrong
+        shape or a sample without a present view."""
+        mask = view_mask.detach().cpu().numpy() if isinstance(view_mask, torch.Tensor) else np.asarray(view_mask)
+        if mask.shape != (b, v):
+            raise ValueError(f"view_mask must have shape [{b}, {v}], got {list(mask.shape)}")
+        mask = mask.astype(bool)
+        counts = mask.sum(axis=1).astype(np.int32)
+        if b == 0 or (counts == 0).any():
+            raise ValueError("view_mask: every sample needs at least one present view"
+                             + (f" (sample {int(np.argmin(counts))} has none)" if b else ""))
+        return mask, counts
+
     def forward_views(self, x, view_mask, bbox=None, cam_params=None):
         """forward() for a batch whose samples have different cameras: `x` is the full [b, v, 3, h, w] batch (v == num_views) and
         `view_mask` a bool [b, v] tensor, array or nested list, True = the view is present.  Each sample's result is what the model
@@ -251,14 +265,7 @@ class HandMvNet(torch.nn.Module):
             raise ValueError("x must have 3 channels")
         if v != self.num_views:
             raise ValueError(f"x must hold all {self.num_views} views per sample (absent ones are named by view_mask), got {v}")
-        mask = view_mask.detach().cpu().numpy() if isinstance(view_mask, torch.Tensor) else np.asarray(view_mask)
-        if mask.shape != (b, v):
-            raise ValueError(f"view_mask must have shape [{b}, {v}], got {list(mask.shape)}")
-        mask = mask.astype(bool)
-        counts = mask.sum(axis=1).astype(np.int32)
-        if b == 0 or (counts == 0).any():
-            raise ValueError("view_mask: every sample needs at least one present view"
-                             + (f" (sample {int(np.argmin(counts))} has none)" if b else ""))
+        mask, counts = self._host_view_mask(view_mask, b, v)
         if not x.is_cuda:
             raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
         dev = x.device
@@ -293,13 +300,18 @@ class HandMvNet(torch.nn.Module):
         return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
 
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
-                       image_size=None):
+                       image_size=None, view_mask=None):
         """forward() from raw camera frames: `frames` uint8 [b, v, Hf, Wf, 3] and integer crop windows `crop_boxes`
         [b, v, 4] (x1, y1, x2, y2; may leave the frame, empty = black view) replace the reference's host-side
         crop_and_pad_image -> ToTensor -> Resize(antialias=True) -> Normalize (datasets/ho3d.py:35-40, 136-149); the
-        windows also serve as `bbox` for the crop-FoV columns (ho3d.py:198).  Same return dict as forward()."""
+        windows also serve as `bbox` for the crop-FoV columns (ho3d.py:198).  Same return dict as forward().
+        view_mask (bool [b, v] tensor, array or nested list, True = present; read on the host): forward_views() from raw frames --
+        only the present frames are prepared, straight from where they lie in `frames` (an index table, one small upload; no uint8
+        frame is copied or gathered); return dict and shapes as forward_views(): rows of absent views are zeros."""
         if not isinstance(frames, torch.Tensor) or frames.dim() != 5 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError("frames must be a uint8 [b, v, Hf, Wf, 3] tensor")
+        if view_mask is not None:
+            return self._forward_frames_views(frames, crop_boxes, view_mask, cam_params, mean, std, image_size)
         if not frames.is_cuda:
             raise _lib.HandMvError("handmvnet_amd runs on MI355X only: frames must be a CUDA(HIP) tensor (no CPU fallback)")
         b, v, fh, fw, _ = frames.shape
@@ -336,6 +348,51 @@ class HandMvNet(torch.nn.Module):
         self._last_key = (size, size, idx, batch, self._dtype)
         return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
 
+    def _forward_frames_views(self, frames, crop_boxes, view_mask, cam_params, mean, std, image_size):
+        """forward_frames(view_mask=...): hmv_forward_frames_views."""
+        b, v, fh, fw, _ = frames.shape
+        if v != self.num_views:
+            raise ValueError(f"frames must hold all {self.num_views} views per sample (absent ones are named by view_mask), got {v}")
+        mask, counts = self._host_view_mask(view_mask, b, v)
+        if not frames.is_cuda:
+            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: frames must be a CUDA(HIP) tensor (no CPU fallback)")
+        dev = frames.device
+        size = int(image_size or self.cfg.image_size)
+        frames = frames.contiguous()
+        boxes = crop_boxes.to(dev).reshape(-1, 4).to(torch.int32).contiguous()
+        if boxes.shape[0] != b * v:
+            raise RuntimeError("crop_boxes must hold one row per frame")
+        n = int(counts.sum())
+        present = np.flatnonzero(mask.reshape(-1))                      # present frames, sample-major, camera order
+        table = torch.from_numpy(present.astype(np.int32)).to(dev)      # the one small upload
+        idx = table.long()
+        bb = it = None
+        if "crop" in self.cfg.pos_enc:
+            if cam_params is None:
+                raise TypeError("pos_enc contains 'crop': cam_params['intrinsic'] is required")
+            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).float()
+            if it.shape[0] != b * v:
+                raise RuntimeError("intrinsic must hold one row per frame")
+            bb, it = boxes.float().index_select(0, idx), it.index_select(0, idx)
+        didx = dev.index if dev.index is not None else torch.cuda.current_device()
+        h = self._engine(size, size, didx)
+        hs_h, hs_w = heatmap_size_of(self.cfg, size, size)
+        crop_p = torch.empty(n, 21, 2, device=dev, dtype=torch.float32)
+        hm_p = torch.empty(n, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
+        out_cam = torch.empty(b, 21, 3, device=dev, dtype=torch.float32)
+        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
+        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().hmv_forward_frames_views(h, b, cnt, frames.data_ptr(), fh, fw, boxes.data_ptr(), table.data_ptr(), m3, s3,
+                                                      bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None,
+                                                      crop_p.data_ptr(), out_cam.data_ptr(), hm_p.data_ptr(), ctypes.c_void_p(stream))
+        _lib.check(rc, h)
+        self._last_key = (size, size, didx, b, self._dtype)
+        out_crop = torch.zeros(b * v, 21, 2, device=dev, dtype=torch.float32).index_copy_(0, idx, crop_p)
+        out_hm = torch.zeros(b * v, 21, hs_h, hs_w, device=dev, dtype=torch.float32).index_copy_(0, idx, hm_p)
+        return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
+
     # ------------------------------------------------------------------ evaluation (handmvnet.py:352-383, 493-517)
     def _get_metrics(self, pred_pts, target_pts):
         """handmvnet.py:352-368: (mpjpe mm, pa_mpjpe mm, auc, norm_auc, pck_values, thresholds) for [b, n, 3]
@@ -346,8 +403,10 @@ class HandMvNet(torch.nn.Module):
             pred_pts, target_pts, min_threshold=self.auc_thresh[0], max_threshold=self.auc_thresh[1], steps=20)
         return mpjpe * scale, pa_mpjpe * scale, auc, norm_auc, pck_values, thresholds
 
-    def _calculate_mpjpe(self, out, inputs, mode="train"):
-        """handmvnet.py:370-427 without the Lightning logging; the MANO vertex metrics need manopth (absent)."""
+    def _calculate_mpjpe(self, out, inputs, mode="train", view_mask=None):
+        """handmvnet.py:370-427 without the Lightning logging; the MANO vertex metrics need manopth (absent).
+        view_mask (bool [B, V], True = present): {mode}_mpjpe2d is the mean over samples of each sample's own 2D MPJPE over its present
+        views (masked joints zeroed on both sides as ever); rows of absent views do not enter, whatever they hold."""
         from .metrics import PoseMetrics
         pred2d, gt2d = out["joints_crop_img"], inputs["joints_crop_img"].to(out["joints_crop_img"].device)
         if "joints_img_mask" in inputs:   # models/utils.py:123-131: masked joints are zeroed on both sides
@@ -355,19 +414,27 @@ class HandMvNet(torch.nn.Module):
             pred2d, gt2d = pred2d * keep, gt2d * keep
         gt3d = inputs["joints_cam"].to(out["joints_cam"].device)   # like the 2D ground truth: the caller's batch may sit on the host
         mpjpe, pa_mpjpe, auc_j, norm_auc_j, pck_values_j, _ = self._get_metrics(out["joints_cam"], gt3d)
-        out_metrics = {f"{mode}_mpjpe2d": PoseMetrics.mpjpe(pred2d, gt2d), f"{mode}_mpjpe": mpjpe,
+        if view_mask is None:
+            mpjpe2d = PoseMetrics.mpjpe(pred2d, gt2d)
+        else:   # the per-step path: torch ops
+            present = (view_mask if isinstance(view_mask, torch.Tensor) else torch.as_tensor(np.asarray(view_mask))).to(pred2d.device).bool()
+            dist = (pred2d - gt2d).double().pow(2).sum(-1).sqrt()                                       # [B, V, 21]
+            dist = torch.where(present.unsqueeze(-1), dist, torch.zeros_like(dist))
+            mpjpe2d = (dist.sum((1, 2)) / (present.sum(1) * 21)).mean().float()
+        out_metrics = {f"{mode}_mpjpe2d": mpjpe2d, f"{mode}_mpjpe": mpjpe,
                        f"{mode}_pa_mpjpe": pa_mpjpe, f"{mode}_pck_j": pck_values_j, f"{mode}_auc_j": auc_j,
                        f"{mode}_norm_auc_j": norm_auc_j}
         if self.get_vertices:
             raise NotImplementedError("get_vertices needs manopth + MANO assets (joints_to_vertices.py:14-23), absent here")
         return out_metrics
 
-    def _calculate_loss(self, out, inputs, cam_params, mode="train"):
+    def _calculate_loss(self, out, inputs, cam_params, mode="train", view_mask=None):
         """handmvnet.py:279-351 for a root-relative model as ONE device call (hmv_pose_losses): returns the total as a 0-dim device
         tensor, leaves every term in self.last_losses under the names the reference logs (f"{mode}/heatmap_loss" ...; root_3d_loss
         is the constant 0.) and, when "g2d" is a configured weight, sets out["projected_joints_crop_img"].  Labels on the host are
         moved to the device.  heatmap_targets == "joints": inputs["heatmap"] is not read; the kernel rebuilds each target pixel from
-        inputs["joints_crop_img"], data_params["image_size"] and the predicted map's size."""
+        inputs["joints_crop_img"], data_params["image_size"] and the predicted map's size.
+        view_mask (bool [B, V], True = present): `out` is forward_views' and the loss is the ragged one (hmv_pose_losses_views)."""
         from .losses import pose_losses
         if not self.train_params["root_relative"]:
             raise NotImplementedError("root_relative: false is not supported (no root-joint head in this build)")
@@ -385,6 +452,8 @@ class HandMvNet(torch.nn.Module):
             kw.update(target_heatmap=inputs["heatmap"])
         else:
             kw.update(image_size=self.data_params["image_size"], sigma=2)   # ho3d.py:161
+        if view_mask is not None:
+            kw.update(view_mask=view_mask)
         res, projected = pose_losses(out["heatmap"], out["joints_crop_img"], out["joints_cam"], inputs["joints_crop_img"],
                                      inputs["joints_cam"], weights, **kw)
         if projected is not None:
@@ -401,14 +470,19 @@ class HandMvNet(torch.nn.Module):
         metrics.  "loss" is _calculate_loss(...) when the batch carries inputs["heatmap"] (or heatmap_targets == "joints"), and None
         for a batch without loss labels.  Like the reference, converts inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE."""
         inputs = batch["data"]
-        out = self.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
+        view_mask = batch.get("view_mask")   # bool [B, V], True = present: a ragged view set (forward_views and the ragged loss / metrics)
+        if view_mask is None:
+            out = self.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
+        else:   # raises ValueError for a sample without a present view, before anything is launched
+            out = self.forward_views(inputs["rgb"], view_mask, inputs["bboxes"], batch["cam_params"])
         inputs["joints_cam"] /= 1000
         if "root_joint" in inputs:
             inputs["root_joint"] /= 1000
+        extra = {} if view_mask is None else {"view_mask": view_mask}
         loss = None
         if "heatmap" in inputs or self.heatmap_targets == "joints":
-            loss = self._calculate_loss(out, inputs, batch["cam_params"], mode=mode)
-        return {"loss": loss, "metrics": self._calculate_mpjpe(out, inputs, mode=mode)}
+            loss = self._calculate_loss(out, inputs, batch["cam_params"], mode=mode, **extra)
+        return {"loss": loss, "metrics": self._calculate_mpjpe(out, inputs, mode=mode, **extra)}
 
     def validation_step(self, batch, batch_idx=0):
         """handmvnet.py:468-491: metric keys carry the "val_" prefix (val_mpjpe is what ModelCheckpoint monitors, train.py:34)."""
@@ -423,7 +497,9 @@ class HandMvNet(torch.nn.Module):
         Each step enqueues forward, loss and one accumulation launch and copies nothing to the host; one all-reduce combines the ranks
         when a process group is initialised; one readback ends the epoch.  Every value is sum(B x step value) / sum(B) over steps and
         ranks -- Lightning's on_epoch mean, and for MPJPE, PA-MPJPE, 2D MPJPE and the PCK curve the value on the pooled split
-        (handmvnet_amd/evaluation.py).  Like test_step, converts each batch's joints_cam / root_joint from mm to metres in place."""
+        (handmvnet_amd/evaluation.py).  Like test_step, converts each batch's joints_cam / root_joint from mm to metres in place.
+        A batch that carries batch["view_mask"] (bool [B, V], True = present; on the host) is a ragged view set: forward_views, the
+        ragged loss and the ragged accumulation, at the cost of its present frames; ragged and uniform batches may be mixed."""
         from .evaluation import EpochEvaluator
         ev = EpochEvaluator(self, mode)
         for batch in batches:

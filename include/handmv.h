@@ -355,6 +355,21 @@ int hmv_forward_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32
                        const float *mean, const float *std, const float *bbox, const float *intrinsic, float *joints_crop_img,
                        float *joints_cam, float *heatmap, void *stream);
 
+/* hmv_forward_views from raw camera frames: hmv_forward_views with the frame preparation of hmv_forward_frames in front instead of an
+ * fp32 batch.  The uint8 frames are neither copied nor gathered: `frames` and `crop_boxes` stay in the caller's full layout,
+ *   frames      device uint8 [batch * cfg.num_views][frame_h][frame_w][3],  crop_boxes  device int32 [batch * cfg.num_views][4],
+ * and packed frame n (sample-major, a sample's present views in camera order) is prepared from frames[frame_index[n]] with the
+ * window crop_boxes[frame_index[n]].
+ *   view_counts     HOST, `batch` entries, each in [1, cfg.num_views]
+ *   frame_index     device int32 [sum view_counts], each in [0, batch * cfg.num_views) (an entry outside that range yields the black
+ *                   view of an empty window, never a read outside `frames`); NULL = the identity: frames / crop_boxes are already
+ *                   packed, [sum view_counts] of them
+ *   bbox, intrinsic, joints_crop_img, joints_cam, heatmap: PACKED, exactly as for hmv_forward_views
+ * HMV_ERR_ARG before anything is launched for whatever hmv_forward_views or hmv_forward_frames refuse.  Always eager, records no stages. */
+int hmv_forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
+                             const int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std, const float *bbox,
+                             const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
+
 /* The frame preparation alone (op-level parity tests): out_nhwc4 device fp32 [n_frames][out_h][out_w][4] (4th channel 0). */
 int hmv_op_prepare_frames(int32_t device, const uint8_t *frames, int32_t n_frames, int32_t frame_h, int32_t frame_w,
                           const int32_t *crop_boxes, const float *mean, const float *std, int32_t out_h, int32_t out_w, float *out_nhwc4,
@@ -451,6 +466,27 @@ size_t hmv_pose_losses_scratch_bytes(int32_t B, int32_t V);
  * alignment, nor the target form. */
 int hmv_pose_losses(int32_t device, const hmv_loss_args *args, float *result, void *stream);
 
+/* hmv_pose_losses for a RAGGED view set (hmv_forward_views): view_present is a device uint8 [B][V], non-zero = the view is present.
+ * Same struct (size and layout), the same [B][V] tensor layout, scratch sizing and result vector.  The rule: the value of every term is
+ * the mean, over the batch's samples, of the value the reference logs for that sample alone (batch 1) over its present views P_b only
+ * (v_b = |P_b|) -- what hmv_forward_views computes for the sample, and independent of how a split is cut into batches:
+ *   heatmap_loss        = w * 1/B sum_b [ sum_{v in P_b} sum (pred - target)^2 / (v_b * 21 * hm_h * hm_w) ]
+ *   joints_2d_loss      = w * 1/B sum_b [ sum_{v in P_b} sum |p keep - g keep| / (v_b * 42) ]      (keep: the uniform entry's mask rule)
+ *   g2d_loss / p2d_loss = w * 1/B sum_b [ sum_{v in P_b} sum |proj - g| / (v_b * 42) ],  |proj - p| likewise
+ *   joints_3d_loss has no view axis and is the uniform entry's; loss is the sum of the terms.
+ * intrinsic, extrinsic and bbox stay FULL [B][V] tables and root_idx indexes the full table: calibration is known for a camera whose
+ * frame is absent, so the root camera may itself be absent.  An absent slot contributes nothing whatever its rows hold (zeros from
+ * hmv_forward_views, garbage, NaN): its maps, joints and joint-mask row are not read, and no target map is synthesised for it.
+ * `projected` receives the projection for present slots and zeros for absent ones.  With every view present the result has the bits
+ * of hmv_pose_losses.  view_present == NULL is HMV_ERR_ARG (the uniform entry is the one for that); the other checks are the uniform
+ * entry's, in front of every HIP call.
+ * PRECONDITION: every sample has at least one present view (hmv_forward_views refuses a batch that breaks it).  The mask is device
+ * data and cannot be checked without a synchronisation, so it is not: a sample without a view causes no out-of-bounds access and
+ * makes the view-dependent terms (and loss) NaN.
+ * Two launches like the uniform entry: one workgroup per frame slot (that of an absent slot writes 0 and leaves at once), then one
+ * workgroup that derives v_b from the mask rows and applies the per-sample divisors. */
+int hmv_pose_losses_views(int32_t device, const hmv_loss_args *args, const uint8_t *view_present, float *result, void *stream);
+
 /* ---- evaluation epoch (what trainer.validate / trainer.test hand back: one set of numbers for the whole split) ----
  * hmv_eval_add adds one evaluation step -- everything HandMvNet._calculate_mpjpe (handmvnet.py:370-427) computes for it, and the loss
  * vector the loss entry above wrote -- into a caller-owned fp64 state vector in device memory.  Nothing is copied to the host: the
@@ -464,6 +500,9 @@ int hmv_pose_losses(int32_t device, const hmv_loss_args *args, float *result, vo
  *   [2]   3D rows, sum of B * 21                     [3]   sum of the 3D joint distances (the units of joints_cam: metres)
  *   [4]   sum of the distances after the per-pose similarity alignment
  *   [5]   2D rows, sum of B * V * 21                 [6]   sum of the 2D joint distances (crop-image pixels)
+ *         (a ragged step, hmv_eval_add_views, counts rows in units of a FULL sample: [5] still grows by B * V * 21, and each present
+ *         row of sample b adds its distance times V / v_b to [6], so that [6] / [5] stays the mean over samples of each sample's own 2D
+ *         MPJPE over its v_b present views; the factor is exactly 1.0 for a full sample)
  *   [7]   sum of B over the steps that carried a loss
  *   [8 .. 13]   sum of B * term for the six values of the loss vector, in its order
  *               { heatmap_loss, joints_2d_loss, joints_3d_loss, g2d_loss, p2d_loss, loss }
@@ -500,6 +539,13 @@ size_t hmv_eval_state_doubles(int32_t steps);
 /* Adds one step to args->state, asynchronously on `stream`.  Every argument is checked before any HIP call: a bad one returns
  * HMV_ERR_ARG and the text behind a NULL handle's last error names it. */
 int hmv_eval_add(int32_t device, const hmv_eval_args *args, void *stream);
+
+/* hmv_eval_add for one step of a RAGGED view set: view_present as for hmv_pose_losses_views (device uint8 [B][V], every sample with at
+ * least one present view; NULL is HMV_ERR_ARG), loss_result the vector that entry wrote.  Same struct, state and layout; one
+ * single-workgroup launch.  Everything but the 2D sum is what hmv_eval_add adds; for [5] / [6] see the state layout.  The rows of absent
+ * views are not read (nor their joint mask).  The rows are walked in hmv_eval_add's order: with every view present the state has its
+ * bits, and ragged and uniform steps may be mixed in one epoch. */
+int hmv_eval_add_views(int32_t device, const hmv_eval_args *args, const uint8_t *view_present, void *stream);
 
 const char *hmv_version(void);
 

@@ -15,7 +15,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_prepare_frames", "hmv_set_graphs", "hmv_graph_stats", "hmv_version", "hmv_tile_rule", "hmv_profile_get_bytes", "hmv_poison_workspace", "hmv_launch_count", "hmv_set_tail_fusion", "hmv_set_chain_fusion", "hmv_set_hr_fusion", "hmv_op_conv2d_x3", "hmv_op_hr_fuse_up", "hmv_op_attention_x3",
            "hmv_range_status", "hmv_op_target_heatmaps", "hmv_project_joints", "hmv_pose_losses", "hmv_pose_losses_scratch_bytes",
            "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views", "hmv_pose_losses_views",
-           "hmv_eval_add_views", "hmv_forward_frames_views"]
+           "hmv_eval_add_views", "hmv_forward_frames_views", "hmv_op_next_crop_boxes", "hmv_forward_frames_track",
+           "hmv_forward_frames_views_track"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -147,6 +148,12 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_frames.argtypes = [vp, ci, fp, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                        fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames.restype = ctypes.c_int
+    lib.hmv_op_next_crop_boxes.argtypes = [ci, ci, fp, fp, fp, ci, ci, ci, fp, fp, fp, fp, vp]
+    lib.hmv_op_next_crop_boxes.restype = ctypes.c_int
+    lib.hmv_forward_frames_track.argtypes = lib.hmv_forward_frames.argtypes[:-1] + [ci, ci, fp, fp, vp]
+    lib.hmv_forward_frames_track.restype = ctypes.c_int
+    lib.hmv_forward_frames_views_track.argtypes = lib.hmv_forward_frames_views.argtypes[:-1] + [ci, ci, fp, fp, vp]
+    lib.hmv_forward_frames_views_track.restype = ctypes.c_int
     lib.hmv_op_prepare_frames.argtypes = [ci, fp, ci, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                           ci, ci, fp, vp]
     lib.hmv_op_prepare_frames.restype = ctypes.c_int

@@ -231,12 +231,20 @@ struct hmv_engine {
         int fh = 0, fw = 0;
         float mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
     } fsrc;
+    // set only for the duration of hmv_forward_frames_track / hmv_forward_frames_views_track: behind the forward, on its stream, the windows
+    // (fsrc.boxes) and bbox are moved in place to the box around the joints just found (track.hip)
+    struct TrackTail {
+        bool on = false;
+        int margin = 0, square = 1;
+        float *joints_img = nullptr;
+        int *status = nullptr;
+    } track;
 
     // hipGraph replay of repeated forwards (same batch and the same caller buffers): the ~100 launches of a forward
     // become one graph launch.  Opt-in: measured on MI355X it does not change throughput (eager enqueue already runs
     // ahead of the GPU); what it saves is host time per forward.
     // A key is first run eagerly, captured on its second use, replayed from then on.
-    typedef std::array<uintptr_t, 12> GraphKey;
+    typedef std::array<uintptr_t, 15> GraphKey;
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; unsigned long long stamp; };
     bool graphs = false;
     // fused tail kernels (fusion_kernels.hip); HMV_NO_FFFUSE=1 / HMV_NO_CHEBFUSE=1 in the environment or hmv_set_tail_fusion(h, 0)
@@ -2108,6 +2116,14 @@ static int forward_eager(hmv_handle h, int32_t batch, const float *x, const floa
     h->launches = 0;
     const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream, false, h->plan);
     if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    if (rc == HMV_OK && h->track.on) {   // (under capture this launch becomes the graph's last node)
+        const int n = batch * h->cfg.num_views;
+        int *boxes = const_cast<int *>(h->fsrc.boxes);
+        const TrackParams tp{n, n, joints_crop_img, boxes, nullptr, nullptr, h->cfg.image_size, h->track.margin, h->track.square,
+                             boxes, const_cast<float *>(bbox), h->track.joints_img, h->track.status};
+        HIPCHK(h, launch_next_crop_boxes(tp, stream));
+        ++h->launches;
+    }
     return rc;
 }
 
@@ -2137,6 +2153,10 @@ static int forward_common(hmv_handle h, int32_t batch, const float *x, const flo
         memcpy(bits + 3, h->fsrc.std, 12);
         key[10] = ((uintptr_t)bits[0] << 32) ^ ((uintptr_t)bits[1] << 16) ^ (uintptr_t)bits[2];
         key[11] = ((uintptr_t)bits[3] << 32) ^ ((uintptr_t)bits[4] << 16) ^ (uintptr_t)bits[5];
+    }
+    if (h->track.on) {   // the tracking tail is part of the captured work: its buffers and parameters are part of the key
+        key[12] = (uintptr_t)h->track.joints_img; key[13] = (uintptr_t)h->track.status;
+        key[14] = (uintptr_t(1) << 63) | ((uintptr_t)(h->track.square != 0) << 32) | (uintptr_t)(unsigned)h->track.margin;
     }
     for (auto &e : h->gcache)
         if (e.key == key) {
@@ -2292,6 +2312,24 @@ static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view
     h->launches = 1;
     const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan, &vs);
     if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    if (rc == HMV_OK && h->track.on) {
+        // a full-layout slot is present iff a packed frame names it: every slot starts as absent (status 1, zero joints, its window
+        // untouched) and each packed row then moves the window of the slot it came from
+        const int n_slots = h->fsrc.index ? h->fsrc.n_src : (int)N;
+        if (h->track.joints_img) {
+            HIPCHK(h, hipMemsetAsync(h->track.joints_img, 0, (size_t)n_slots * NJ * 2 * sizeof(float), s));
+            ++h->launches;
+        }
+        if (h->track.status) {
+            HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->track.status), 1, (size_t)n_slots, s));
+            ++h->launches;
+        }
+        int *boxes = const_cast<int *>(h->fsrc.boxes);
+        const TrackParams tp{(int)N, n_slots, joints_crop_img, boxes, nullptr, h->fsrc.index, h->cfg.image_size, h->track.margin,
+                             h->track.square, boxes, const_cast<float *>(bbox), h->track.joints_img, h->track.status};
+        HIPCHK(h, launch_next_crop_boxes(tp, s));
+        ++h->launches;
+    }
     return rc;
 }
 
@@ -2350,6 +2388,42 @@ int hmv_forward_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32
     const int rc = forward_common(h, batch, nullptr, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
     h->fsrc.frames = nullptr;
     h->fsrc.boxes = nullptr;
+    return rc;
+}
+
+/* hmv_forward_frames, then on the same stream the windows and bbox moved in place to the box around the joints just found
+ * (include/handmv.h).  The tail is enqueued by the eager forward itself, so a captured graph holds it as its last node. */
+int hmv_forward_frames_track(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, int32_t *crop_boxes,
+                             const float *mean, const float *std, float *bbox, const float *intrinsic, float *joints_crop_img,
+                             float *joints_cam, float *heatmap, int32_t margin, int32_t square, float *joints_img, int32_t *status,
+                             void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (margin < 0) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_track: margin must not be negative");
+    h->track.on = true;
+    h->track.margin = margin;
+    h->track.square = square != 0;
+    h->track.joints_img = joints_img;
+    h->track.status = status;
+    const int rc = hmv_forward_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, bbox, intrinsic, joints_crop_img,
+                                      joints_cam, heatmap, stream);
+    h->track = hmv_engine::TrackTail();
+    return rc;
+}
+
+int hmv_forward_frames_views_track(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h,
+                                   int32_t frame_w, int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std,
+                                   float *bbox, const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap,
+                                   int32_t margin, int32_t square, float *joints_img, int32_t *status, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (margin < 0) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_views_track: margin must not be negative");
+    h->track.on = true;
+    h->track.margin = margin;
+    h->track.square = square != 0;
+    h->track.joints_img = joints_img;
+    h->track.status = status;
+    const int rc = hmv_forward_frames_views(h, batch, view_counts, frames, frame_h, frame_w, crop_boxes, frame_index, mean, std, bbox,
+                                            intrinsic, joints_crop_img, joints_cam, heatmap, stream);
+    h->track = hmv_engine::TrackTail();
     return rc;
 }
 

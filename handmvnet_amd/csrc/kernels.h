@@ -343,6 +343,23 @@ bool cheb_fusable(int K, int ldx, int ldw1, int c1, int ldw2, int c2, int ldw3, 
 hipError_t launch_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C, hipStream_t s, int ld = 0);
 hipError_t launch_copy_rows(const float *in, int ldi, float *out, int ldo, int rows, int cols, hipStream_t s);
 
+// Next crop windows from this step's 2D joints (track.hip; hmv_op_next_crop_boxes in handmv.h): one wave64 per ROW of joints_crop_img.
+// Row r belongs to window slot index[r] (index == nullptr: slot r; an entry outside [0, n_slots) is skipped); boxes_in / boxes_out /
+// present / joints_img / status are indexed by slot, joints_crop_img / bbox_out by row.  present, bbox_out, joints_img, status may be null.
+struct TrackParams {
+    int n_rows, n_slots;
+    const float *joints_crop_img;
+    const int *boxes_in;
+    const uint8_t *present;
+    const int *index;
+    int image_size, margin, square;
+    int *boxes_out;
+    float *bbox_out;
+    float *joints_img;
+    int *status;
+};
+hipError_t launch_next_crop_boxes(const TrackParams &p, hipStream_t s);
+
 // Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
 void set_thread_error(const std::string &msg);
 

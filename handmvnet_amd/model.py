@@ -576,6 +576,8 @@ class HandMvNet(torch.nn.Module):
         for h in self._engines.values():
             _lib.load().hmv_set_graphs(h, int(enable))
 
+    set_graphs = use_graphs   # the C ABI's name for it (hmv_set_graphs)
+
     def graph_stats(self):
         """(graphs cached, replays so far) of the engine the last forward ran on."""
         hh, ww, idx, _, dt = self._last_key

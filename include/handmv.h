@@ -375,6 +375,58 @@ int hmv_op_prepare_frames(int32_t device, const uint8_t *frames, int32_t n_frame
                           const int32_t *crop_boxes, const float *mean, const float *std, int32_t out_h, int32_t out_w, float *out_nhwc4,
                           void *stream);
 
+/* ---- sequences: the crop window of frame t + 1 is the box around the hand found in frame t ----
+ * A recorded or live sequence has no dataset boxes (datasets/ho3d.py:103); its windows follow the hand.  One launch (track.hip) turns a
+ * step's joints_crop_img into the next step's windows, per frame slot n (sample, view) with S = float(image_size):
+ *   frame-space joints = batch_cropped_joints_to_joints_img (datasets/utils.py:146-162, as handmvnet.py:237 calls it) in its own fp32
+ *     operation order, every operation rounded on its own (no fused multiply-add):
+ *       X = fl(fl(u * fl(fl(float(x2) - float(x1)) / S)) + float(x1)),  Y likewise with y1, y2
+ *   next window = points2d_to_bbox(points, margin, square) (datasets/utils.py:5-27) exactly: minimum / maximum over the 21 joints truncated
+ *     toward zero (Python's int()), the shorter side of a `square` box widened by |h - w| (the odd pixel goes to the low edge), then margin.
+ *   joints_crop_img [n_slots][21][2] fp32, crop pixels as a forward returns them;  crop_boxes_in [n_slots][4] int32 = x1, y1, x2, y2
+ *   present         device uint8 [n_slots] or NULL (= every slot present)
+ *   crop_boxes_out  [n_slots][4] int32;  bbox_out [n_slots][4] fp32 or NULL: the same four numbers as fp32 (what hmv_forward_frames takes as bbox)
+ *   joints_img      [n_slots][21][2] fp32 or NULL: the frame-space joints;  status [n_slots] int32 or NULL
+ * status 0: the window moved.
+ * status 1: present[n] == 0.  Window copied through (bbox_out = its fp32), joints_img row zeros (hmv_forward_views' callers zero an absent
+ *           view's joints: followed blindly they would collapse the window onto the crop corner).
+ * status 2: one of the 42 frame-space coordinates is non-finite or has magnitude >= 1e9 (int conversion would overflow), or the new window
+ *           would be wider or taller than 65536 px (which hmv_forward_frames reads as the black view).  Window copied through (bbox_out =
+ *           its fp32), joints_img as computed.  The reference raises here; device code cannot, so it reports.
+ * An empty input window (x2 <= x1 or y2 <= y1) is not special: the arithmetic is defined for it and is the reference's.
+ * crop_boxes_out may be crop_boxes_in and bbox_out may alias any fp32 copy of it: a slot reads its window before it writes, and no slot
+ * reads another's.  Takes no handle; asynchronous on `stream`.  HMV_ERR_ARG before any launch (hmv_last_error(NULL) names it) for
+ * n_slots <= 0, image_size <= 0, margin < 0, a NULL joints_crop_img / crop_boxes_in / crop_boxes_out. */
+int hmv_op_next_crop_boxes(int32_t device, int32_t n_slots, const float *joints_crop_img, const int32_t *crop_boxes_in, const uint8_t *present,
+                           int32_t image_size, int32_t margin, int32_t square, int32_t *crop_boxes_out, float *bbox_out, float *joints_img,
+                           int32_t *status, void *stream);
+
+/* hmv_forward_frames, then on the same stream hmv_op_next_crop_boxes (image_size = cfg.image_size, every slot present) from the
+ * joints_crop_img just written, IN PLACE: crop_boxes [batch*V][4] becomes the next step's windows and bbox (when not NULL: no 'crop' in
+ * pos_enc needs none) their fp32.  joints_img [batch*V][21][2] and status [batch*V] as above, each may be NULL.  A sequence is this one call
+ * per time step on unchanged buffers: nothing crosses to the host.
+ * Takes part in graph replay exactly like hmv_forward_frames, tracking launch included; the key also covers joints_img, status, margin
+ * and square (a call is never served by a graph of hmv_forward_frames or the other way round).  Stage capture and profiling force the
+ * eager path.  hmv_launch_count counts the extra launch.  HMV_ERR_ARG before any launch for margin < 0 and whatever hmv_forward_frames refuses. */
+int hmv_forward_frames_track(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, int32_t *crop_boxes,
+                             const float *mean, const float *std, float *bbox, const float *intrinsic, float *joints_crop_img,
+                             float *joints_cam, float *heatmap, int32_t margin, int32_t square, float *joints_img, int32_t *status,
+                             void *stream);
+
+/* The same tail behind hmv_forward_frames_views; always eager and records no stages, as that entry.
+ *   crop_boxes   stays in the caller's FULL [batch * cfg.num_views] layout and is updated in place: packed row n (its joints_crop_img row)
+ *                moves the window of slot frame_index[n].  A slot is present iff some packed frame names it; the window of an absent slot
+ *                is left alone.  The entries of frame_index must be distinct (two rows naming one slot race for its window); an entry
+ *                outside the range moves nothing.
+ *   bbox         PACKED, as in that entry: row n receives the fp32 of its slot's new window (NULL: not updated)
+ *   joints_img [batch * cfg.num_views][21][2], status [batch * cfg.num_views]: FULL layout, each may be NULL; an absent slot reads status 1
+ *                and zero joints (two fills in front of the tracking launch).
+ * frame_index == NULL (frames and windows already packed): the layout is the packed one, [sum view_counts] slots, all present. */
+int hmv_forward_frames_views_track(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h,
+                                   int32_t frame_w, int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std,
+                                   float *bbox, const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap,
+                                   int32_t margin, int32_t square, float *joints_img, int32_t *status, void *stream);
+
 /* Evaluation metrics of HandMvNet._get_metrics (handmvnet.py:352-368) on the device, replacing
  * PoseMetrics.mpjpe / pa_mpjpe / pck / pck_auc / compute_similarity_transform (models/metrics.py:6-24, 64-176).
  * pred, target: device fp32 [n_sets][n_pts][dim] (dim 2 or 3; units as given -- the caller applies the x1000 the

@@ -13,4 +13,7 @@ def __getattr__(name):
     if name in ("SequenceTracker", "next_crop_boxes", "joints_to_frame"):   # sequences without dataset boxes (tracking.py)
         from . import tracking
         return getattr(tracking, name)
+    if name in ("SequenceEvaluator", "labels_to_windows"):   # evaluating a followed sequence (sequence_eval.py)
+        from . import sequence_eval
+        return getattr(sequence_eval, name)
     raise AttributeError(name)

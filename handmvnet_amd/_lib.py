@@ -16,7 +16,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_range_status", "hmv_op_target_heatmaps", "hmv_project_joints", "hmv_pose_losses", "hmv_pose_losses_scratch_bytes",
            "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views", "hmv_pose_losses_views",
            "hmv_eval_add_views", "hmv_forward_frames_views", "hmv_op_next_crop_boxes", "hmv_forward_frames_track",
-           "hmv_forward_frames_views_track"]
+           "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
+           "hmv_seq_eval_history_floats", "hmv_seq_eval_add"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -51,6 +52,14 @@ class HmvEvalArgs(ctypes.Structure):
                 ("pred_joints_cam", ctypes.c_void_p), ("gt_joints_cam", ctypes.c_void_p), ("pred_joints_2d", ctypes.c_void_p),
                 ("gt_joints_2d", ctypes.c_void_p), ("joints_mask", ctypes.c_void_p), ("loss_result", ctypes.c_void_p),
                 ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t)]
+
+
+class HmvSeqEvalArgs(ctypes.Structure):
+    """hmv_seq_eval_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("pred_joints_cam", ctypes.c_void_p), ("gt_joints_cam", ctypes.c_void_p), ("track_status", ctypes.c_void_p),
+                ("slot_info", ctypes.c_void_p), ("restart", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("history", ctypes.c_void_p),
+                ("sums_doubles", ctypes.c_size_t), ("history_floats", ctypes.c_size_t)]
 
 
 class HandMvError(RuntimeError):
@@ -154,6 +163,16 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_frames_track.restype = ctypes.c_int
     lib.hmv_forward_frames_views_track.argtypes = lib.hmv_forward_frames_views.argtypes[:-1] + [ci, ci, fp, fp, vp]
     lib.hmv_forward_frames_views_track.restype = ctypes.c_int
+    lib.hmv_op_labels_to_windows.argtypes = [ci, ci, fp, fp, fp, fp, ci, fp, fp, fp, vp]
+    lib.hmv_op_labels_to_windows.restype = ctypes.c_int
+    lib.hmv_op_mka.argtypes = [ci, fp, ci, ci, ci, ci, fp, vp]
+    lib.hmv_op_mka.restype = ctypes.c_int
+    lib.hmv_seq_eval_sums_doubles.argtypes = [ci]
+    lib.hmv_seq_eval_sums_doubles.restype = ctypes.c_size_t
+    lib.hmv_seq_eval_history_floats.argtypes = [ci]
+    lib.hmv_seq_eval_history_floats.restype = ctypes.c_size_t
+    lib.hmv_seq_eval_add.argtypes = [ci, ctypes.POINTER(HmvSeqEvalArgs), vp]
+    lib.hmv_seq_eval_add.restype = ctypes.c_int
     lib.hmv_op_prepare_frames.argtypes = [ci, fp, ci, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                           ci, ci, fp, vp]
     lib.hmv_op_prepare_frames.restype = ctypes.c_int

@@ -1,5 +1,6 @@
 """Device-side mirror of the reference's ``PoseMetrics`` for the methods its evaluation path calls
-(/root/reference/src/models/metrics.py:6-24, 64-176; call sites handmvnet.py:352-368, 381).
+(/root/reference/src/models/metrics.py:6-24, 64-176; call sites handmvnet.py:352-368, 381), and of its sequence metric ``mka``
+(metrics.py:36-49), which measures the jitter of a followed sequence (handmvnet_amd/sequence_eval.py).
 
 Every method takes device tensors and runs ``hmv_pose_metrics`` (include/handmv.h) on the tensor's
 device and the current stream; return types follow the reference (0-dim tensors for mpjpe / pa_mpjpe / pck,
@@ -57,6 +58,29 @@ class PoseMetrics:
         """S1 [B, N, 3] after the scale/rotation/translation that brings it closest to S2 (metrics.py:128-176)."""
         assert S1.shape == S2.shape and S1.dim() == 3 and S1.shape[-1] == 3
         return _run(S1, S2, 0.0, 0.0, 1, True, want_aligned=True)[1].view_as(S1)
+
+    @staticmethod
+    def mka(preds):
+        """Mean keypoint acceleration per sequence (metrics.py:36-49): preds [B, T, n_pts, dim] -> [B] device tensor, through
+        hmv_op_mka: fp64 arithmetic in the reference's operation order, one rounding to fp32.  NaN for T < 3, like the reference's
+        mean of an empty tensor."""
+        if not isinstance(preds, torch.Tensor) or preds.dim() != 4:
+            raise ValueError("preds must be a [B, T, n_pts, dim] tensor")
+        B, T, n_pts, dim = (int(k) for k in preds.shape)
+        if B < 1 or n_pts < 1 or not 1 <= dim <= 4:
+            raise ValueError(f"preds must be [B >= 1, T, n_pts >= 1, dim in 1 .. 4], got {list(preds.shape)}")
+        if not preds.is_cuda:
+            raise _lib.HandMvError("handmvnet_amd metrics run on MI355X only: preds must be a CUDA(HIP) tensor")
+        dev = preds.device
+        p = preds.detach().contiguous().float()
+        out = torch.empty(B, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().hmv_op_mka(dev.index if dev.index is not None else torch.cuda.current_device(),
+                                        p.data_ptr() if T > 0 else out.data_ptr(),   # (nothing is read for T < 3)
+                                        B, T, n_pts, dim, out.data_ptr(), ctypes.c_void_p(stream))
+        _lib.check(rc)
+        return out
 
     @staticmethod
     def pck(preds, labels, threshold, reference_len=None):

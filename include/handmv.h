@@ -599,6 +599,90 @@ int hmv_eval_add(int32_t device, const hmv_eval_args *args, void *stream);
  * bits, and ragged and uniform steps may be mixed in one epoch. */
 int hmv_eval_add_views(int32_t device, const hmv_eval_args *args, const uint8_t *view_present, void *stream);
 
+/* ---- sequence evaluation (a followed sequence, hmv_forward_frames_track: labels in the tracker's windows, jitter, window quality) ----
+ * Under a tracker the windows are the tracker's own, so 2D labels expressed in dataset boxes do not belong to the predictions.  The
+ * three entries below keep the evaluation of such a sequence on the device.  Stateless like the metrics, loss and track entries: a
+ * device ordinal and a stream, asynchronous, device pointers throughout; every argument is checked before any HIP call, a bad one
+ * returns HMV_ERR_ARG with the text behind hmv_last_error(NULL) naming it, and no output is touched. */
+
+/* Frame-space label joints into the windows a step ran on (hmv_forward_frames_track's crop_boxes BEFORE the call; SequenceTracker's
+ * crop_boxes_used): batch_joints_img_to_cropped_joints (datasets/utils.py:124-143) to the bits of the reference's fp32 torch run.  Per
+ * frame slot n with S = float(image_size), every operation rounded on its own (no fused multiply-add):
+ *       wf = fl(float(x2) - float(x1))      d = fl(X - float(x1))      r = fl(fl(1 / wf) * S)      u = fl(d * r)      v likewise with y1, y2
+ * The order matters: `image_size / widths` with a Python scalar on the left is widths.reciprocal() * image_size in torch, which differs
+ * from fl(S / wf) in about a quarter of the coordinates when S is not a power of two (192, 320).
+ *   joints_img     [n_slots][21][2] fp32, frame pixels;   crop_boxes [n_slots][4] int32 = x1, y1, x2, y2
+ *   present        device uint8 [n_slots] or NULL (= every slot present)
+ *   joints_mask_in device uint8 [n_slots][21] or NULL, non-zero = the joint is invisible (inputs["joints_img_mask"])
+ *   joints_crop    [n_slots][21][2] fp32: the labels in crop pixels of the window, what inputs["joints_crop_img"] holds for a dataset box
+ *   mask_out       uint8 [n_slots][21] or NULL: joints_mask_in != 0 || status != 0
+ *   slot_info      int32 [n_slots][3] or NULL = { status, outside, visible }
+ * status 0: mapped.
+ * status 1: present[n] == 0.  joints_crop row zeros, mask_out row all 1.
+ * status 2: an empty window (x2 <= x1 or y2 <= y1), which a tracker can produce (points2d_to_bbox with margin 0 on coincident
+ *           joints).  The reference divides by zero there; this entry writes what status 1 writes and reports the slot, so that one
+ *           such step does not poison an epoch's sums.
+ * visible: the joints of a status-0 slot whose joints_mask_in is zero (21 with a NULL joints_mask_in).  outside: how many of those have a
+ *          mapped coordinate that is non-finite or not in 0 <= c < S on either axis (0 is inside, S is outside).  Both 0 for status 1, 2.
+ * One wave per slot, four slots per workgroup; the counts travel by ballot: no LDS, no atomics.  Outputs must not alias inputs.
+ * HMV_ERR_ARG for n_slots <= 0, image_size <= 0, a NULL joints_img / crop_boxes / joints_crop. */
+int hmv_op_labels_to_windows(int32_t device, int32_t n_slots, const float *joints_img, const int32_t *crop_boxes, const uint8_t *present,
+                             const uint8_t *joints_mask_in, int32_t image_size, float *joints_crop, uint8_t *mask_out, int32_t *slot_info,
+                             void *stream);
+
+/* PoseMetrics.mka (models/metrics.py:36-49), the mean keypoint acceleration that measures tracking jitter; it needs no labels.
+ *   preds [B][T][n_pts][dim] fp32 (dim 1 .. 4; units as given);   out [B] fp32
+ * Per sequence: acc = (p[t] + p[t + 2]) - 2 p[t + 1], the norm over dim, the mean over the (T - 2) * n_pts rows; fp64 arithmetic from the
+ * fp32 inputs in exactly that operation order, one rounding to fp32 at the end.  T < 3 gives NaN (the reference's mean of an empty
+ * tensor).  One workgroup per sequence, fixed-order reduction: two calls give the same bits.
+ * HMV_ERR_ARG for B <= 0, T < 0, n_pts <= 0, dim outside 1 .. 4, a NULL preds / out. */
+int hmv_op_mka(int32_t device, const float *preds, int32_t B, int32_t T, int32_t n_pts, int32_t dim, float *out, void *stream);
+
+/* hmv_seq_eval_add adds ONE time step of B concurrent sequences ("lanes": the tracker's batch) into caller-owned device memory, so
+ * that jitter and window quality of a whole sequence are read back once.  A zero-filled pair of buffers is an empty evaluation, as
+ * for hmv_eval_add; summing the `sums` of several ranks element by element (all but [0]) gives the sums of their union.
+ *
+ * sums: doubles [B][12] (hmv_seq_eval_sums_doubles(B)), per lane
+ *   [0]   steps since the lane's last restart           [1]   steps in total
+ *   [2]   acceleration rows: grows by 21 at a step once [0] >= 3
+ *   [3]   sum of ||acc|| of the predictions (the units of pred_joints_cam), acc as in hmv_op_mka from this step and the two before it
+ *   [4]   sum of ||acc|| of the labels; untouched when gt_joints_cam is NULL.  [4] / [2] is the labels' own jitter only for a lane that
+ *         had labels at every step since its restart: a step without labels leaves the label history as it is
+ *   [5 .. 7]   slot-steps with track_status 0 / 1 / 2 (window moved / view absent / window kept)
+ *   [8]   slot-steps with an empty window (slot_info status 2)      [9]   sum of visible      [10]   sum of outside      [11]   0
+ * history: fp32 [B][2][2][63] (hmv_seq_eval_history_floats(B)): {predictions, labels} x {step t - 2, step t - 1} x [21][3].
+ * restart[b] != 0: a new sequence begins in lane b at this step.  [0] is set to 0 before the step is added, so the lane's history is
+ *   not used until two further steps have filled it; the other sums keep accumulating.  The pooled jitter [3] / [2] over lanes and
+ *   restarts is therefore the mean over every acceleration row of every sequence, hmv_op_mka's value for one sequence.
+ * Counts are integers held in doubles.  One workgroup (one wave) per lane; a lane reads its history before it writes it and no lane
+ * reads another's, so lane b of a B-lane call has the bits of a one-lane call.  The final read-modify-write of sums is by plain
+ * stores from one thread per element: no floating-point atomics, fixed-order reductions.  The buffers belong to one stream at a
+ * time: stream order is what orders successive steps. */
+typedef struct hmv_seq_eval_args {
+    int32_t struct_size;            /* sizeof(hmv_seq_eval_args), ABI guard */
+    int32_t B, V;                   /* lanes, views */
+    int32_t reserved;               /* 0 */
+    const float *pred_joints_cam;   /* out["joints_cam"]   [B][21][3] */
+    const float *gt_joints_cam;     /* labels, same shape and units; may be NULL: a live sequence has none, and jitter needs none */
+    const int32_t *track_status;    /* [B][V] as hmv_forward_frames_track wrote it; may be NULL */
+    const int32_t *slot_info;       /* [B][V][3] as hmv_op_labels_to_windows wrote it; may be NULL */
+    const uint8_t *restart;         /* [B]; may be NULL (= no lane restarts) */
+    double *sums;                   /* device, 8-byte aligned */
+    float *history;                 /* device */
+    size_t sums_doubles;            /* >= hmv_seq_eval_sums_doubles(B) */
+    size_t history_floats;          /* >= hmv_seq_eval_history_floats(B) */
+} hmv_seq_eval_args;
+
+/* Doubles in `sums` for B lanes: 12 * B; 0 when B < 1. */
+size_t hmv_seq_eval_sums_doubles(int32_t B);
+
+/* Floats in `history` for B lanes: 252 * B; 0 when B < 1. */
+size_t hmv_seq_eval_history_floats(int32_t B);
+
+/* Adds one step, asynchronously on `stream`.  HMV_ERR_ARG for a NULL args, a wrong struct_size, B < 1, V < 1, B * V > 2^24, a NULL
+ * pred_joints_cam, a NULL or misaligned sums / history, sums_doubles / history_floats below what the sizing entries give. */
+int hmv_seq_eval_add(int32_t device, const hmv_seq_eval_args *args, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

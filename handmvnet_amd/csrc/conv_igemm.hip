@@ -26,11 +26,14 @@
 //     16-byte chunk index, chunk' = chunk ^ ((row >> 1) & 7); since the DMA destination is
 //     lane-linear, the swizzle is applied to the per-lane SOURCE address and to the read.
 //   * out-of-range taps / rows DMA from a 256-byte zero page: no select after the load.
-//   * per 32-wide k-step: MFMA groups q0..q2, then {vmcnt(0) for tile t+1, ONE s_barrier}, then the
-//     DMA of tile t+2 into the buffer just vacated and the first fragments of tile t+1, all
-//     under the 16 MFMAs of group q3.  In-kernel stamps show the main loop at ~94 % matrix-pipe
-//     occupancy in cycles; what is left is DVFS (the chip drops to 2.0-2.2 GHz under real
-//     operand traffic), which is why the largest tile that still fills the chip wins.
+//   * per 32-wide k-step: MFMA groups q0..q2, then {vmcnt(0) for tile t+1, ONE s_barrier}, then group q3, whose fragments are
+//     in registers already.  fp32: q3's MFMAs follow the barrier at once, and the DMA pieces of tile t+2 (into the buffer just
+//     vacated) and the first fragment reads of tile t+1 go out one by one BETWEEN them (see the fp32 k-step in the kernel).
+//     fp16: the DMA and the fragment reads are issued in front of q3.
+//   * what bounds the fp32 kernels is the matrix pipe's idle cycles, not the clock: PMC passes of the benchmarked step show the
+//     256x256 kernels at 2.37-2.38 GHz with the pipe busy 0.85-0.89 of the time (256x128 / 256x64 / k16,w8: 2.30-2.37 GHz, 0.77-0.82),
+//     so an idle pipe cycle there is a wall-clock cycle.  The fp16 kernels are the ones DVFS holds at 2.0-2.2 GHz under real
+//     operand traffic.  Either way the largest tile that still fills the chip wins: least L2 -> LDS traffic per FLOP.
 //   * XCD-aware block -> tile map: the N-tiles of one M-tile are consecutive on ONE XCD, so an
 //     activation tile is pulled from HBM once per XCD and re-read from that XCD's L2.
 //   * epilogue fused: folded-BN shift / bias, residual add, ReLU / GELU(erf) / LeakyReLU, staged
@@ -336,11 +339,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
     int dtap = 0, dchunk = 0;                          // HALO: (tap, 64-channel chunk) of the next tile the DMA cursor issues
     const int nk = (p.ksl > 1 ? p.kslice : p.Kpad) / KB;
 
-    // issue the DMA of the cursor tile into LDS buffer `buf`, then advance the cursor
-#define HMV_DMA(buf)                                                                                        \
-    {                                                                                                       \
-        int sr_ = 0, ss_ = 0;                                                                               \
-        int sc_ = 0;                                                                                        \
+    // The DMA of the cursor tile into LDS buffer `buf`, in pieces: HMV_DMA_PRE (the lane-private tap of the dense K order), one
+    // LDS-DMA instruction per HMV_DMA_A(buf, i) / HMV_DMA_B(buf, i), and HMV_DMA_TAIL, which advances the cursor and runs exactly
+    // once per tile, after the last piece.  HMV_DMA(buf) is all of them in order; the fp32 main loop places them one by one.
+    int sr_ = 0, ss_ = 0, sc_ = 0;   // MODE_DENSE: (tap row, tap column, channel offset) of this lane's 16-byte vector in the cursor tile
+#define HMV_DMA_PRE                                                                                         \
+    do {                                                                                                    \
         if (MODE == MODE_DENSE) { /* lane-private (tap, channel offset) of this 16-byte vector */           \
             /* fused split loop: 4 (tap, channel) vectors per k-step, chunks 4-7 fetch the same vectors from the lo plane */ \
             const unsigned g_ = (X3CAP && x3n) ? (unsigned)(ck / (2 * EPC) + (kqs & 3)) : (unsigned)(ck / EPC + kqs); \
@@ -352,38 +356,37 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
             ss_ = (int)tap_ - sr_ * p.S;                                                                    \
             if (tap_ >= (unsigned)(p.R * p.S)) sr_ = 1 << 29;                                               \
         }                                                                                                   \
-        if (HALO && dtap == 0) { /* first tap of a 64-channel chunk: its halo image, once */                \
-            _Pragma("unroll") for (int i = 0; i < 6; ++i)                                                   \
-                if (i < 5 || wave == 0)                                                                     \
-                    HMV_GLDS16(hsrc[i] ? hsrc[i] + dchunk * CH : zero, sA + ((dchunk & 1) * HALO_ROWS + i * 64 + wave * 8) * KB); \
+    } while (0)
+#define HMV_DMA_A(buf, i)                                                                                   \
+    do {                                                                                                    \
+        const T *src_;                                                                                      \
+        if (MODE == MODE_1X1) {                                                                             \
+            src_ = aptr[i];                                                                                 \
+            aptr[i] += astep[i];                                                                            \
+        } else if (MODE == MODE_TAPS) {                                                                     \
+            const bool ok_ = (unsigned)(hi0[i] + cr) < (unsigned)p.H && (unsigned)(wi0[i] + cs) < (unsigned)p.W; \
+            src_ = ok_ ? aptr[i] + cdelta : zero;                                                           \
+        } else {                                                                                            \
+            const int hi_ = (hi0[i] + sr_) >> p.up, wi_ = (wi0[i] + ss_) >> p.up;                           \
+            const bool ok_ = (unsigned)hi_ < (unsigned)p.H && (unsigned)wi_ < (unsigned)p.W;                \
+            src_ = ok_ ? aptr[i] + (hi_ * p.W + wi_) * p.lda + sc_ : zero;                                  \
         }                                                                                                   \
-        if (HALO) { if (++dtap == 9) { dtap = 0; ++dchunk; } }                                              \
-        _Pragma("unroll") for (int i = 0; HALO ? false : i < AP; ++i) {                                     \
-            const T *src_;                                                                                  \
-            if (MODE == MODE_1X1) {                                                                         \
-                src_ = aptr[i];                                                                             \
-                aptr[i] += astep[i];                                                                        \
-            } else if (MODE == MODE_TAPS) {                                                                 \
-                const bool ok_ = (unsigned)(hi0[i] + cr) < (unsigned)p.H && (unsigned)(wi0[i] + cs) < (unsigned)p.W; \
-                src_ = ok_ ? aptr[i] + cdelta : zero;                                                       \
-            } else {                                                                                        \
-                const int hi_ = (hi0[i] + sr_) >> p.up, wi_ = (wi0[i] + ss_) >> p.up;                       \
-                const bool ok_ = (unsigned)hi_ < (unsigned)p.H && (unsigned)wi_ < (unsigned)p.W;            \
-                src_ = ok_ ? aptr[i] + (hi_ * p.W + wi_) * p.lda + sc_ : zero;                              \
-            }                                                                                               \
-            HMV_GLDS16(src_, sA + ((buf) * BM + i * RPS + wave * RPW) * KB);                                \
-        }                                                                                                   \
-        _Pragma("unroll") for (int i = 0; i < BP; ++i) {                                                    \
-            HMV_GLDS16(wptr[i], sB + ((buf) * BN + i * RPS + wave * RPW) * KB);                             \
-            wptr[i] += KB;                                                                                  \
-        }                                                                                                   \
+        HMV_GLDS16(src_, sA + ((buf) * BM + (i) * RPS + wave * RPW) * KB);                                  \
+    } while (0)
+#define HMV_DMA_B(buf, i)                                                                                   \
+    do {                                                                                                    \
+        HMV_GLDS16(wptr[i], sB + ((buf) * BN + (i) * RPS + wave * RPW) * KB);                               \
+        wptr[i] += KB;                                                                                      \
+    } while (0)
+#define HMV_DMA_TAIL                                                                                        \
+    do {                                                                                                    \
         ck += KB;                                                                                           \
         if (MODE == MODE_1X1 && p.in2 && ck == p.ksplit) { /* concatenated reduction: the rest comes from the second source */ \
             _Pragma("unroll") for (int i = 0; i < AP; ++i) {                                                \
                 const int m_ = mt * BM + i * RPS + lrow;                                                    \
                 if (m_ < p.M) {                                                                             \
                     const int n_ = m_ / HoWo, rem_ = m_ - n_ * HoWo, ho_ = rem_ / p.Wo, wo_ = rem_ - ho_ * p.Wo; \
-                    aptr[i] = reinterpret_cast<const T *>(p.in2) + ((size_t)n_ * p.H2 * p.W2 +            \
+                    aptr[i] = reinterpret_cast<const T *>(p.in2) + ((size_t)n_ * p.H2 * p.W2 +              \
                               (size_t)(ho_ * p.stride2) * p.W2 + wo_ * p.stride2) * p.lda2 + koff;          \
                 }                                                                                           \
             }                                                                                               \
@@ -404,6 +407,19 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                 }                                                                                           \
             }                                                                                               \
         }                                                                                                   \
+    } while (0)
+#define HMV_DMA(buf)                                                                                        \
+    {                                                                                                       \
+        HMV_DMA_PRE;                                                                                        \
+        if (HALO && dtap == 0) { /* first tap of a 64-channel chunk: its halo image, once */                \
+            _Pragma("unroll") for (int i = 0; i < 6; ++i)                                                   \
+                if (i < 5 || wave == 0)                                                                     \
+                    HMV_GLDS16(hsrc[i] ? hsrc[i] + dchunk * CH : zero, sA + ((dchunk & 1) * HALO_ROWS + i * 64 + wave * 8) * KB); \
+        }                                                                                                   \
+        if (HALO) { if (++dtap == 9) { dtap = 0; ++dchunk; } }                                              \
+        _Pragma("unroll") for (int i = 0; HALO ? false : i < AP; ++i) HMV_DMA_A(buf, i);                    \
+        _Pragma("unroll") for (int i = 0; i < BP; ++i) HMV_DMA_B(buf, i);                                   \
+        HMV_DMA_TAIL;                                                                                       \
     }
     // operand fetch: lane (row l31, k-half kh) reads logical chunk 2q+kh at its swizzled position
     const int fsw = LPR == 8 ? ((l31 >> 1) & 7) : ((l31 >> 2) & 3);
@@ -565,7 +581,77 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
     if constexpr (HALO) HMV_HALO_SET(0, 0);
     if (!done) HMV_FRAGS(fa0, fb0, 0, 0);
 
-    for (int kt = 0; !done && kt < nk; ++kt) {
+    if constexpr (!F16) {
+        // ---- fp32 k-step.  Groups q0 .. q(NQ-2) as in the fp16 loop below.  The last group's MFMAs start right behind the barrier: their
+        // fragments are in registers, and nothing they need comes from the DMA or from LDS.  The group is cut into NU = 4 * TM units
+        // (one e, one a, all b: the MFMA order per accumulator is unchanged); behind each unit of the first half goes one piece of
+        // the DMA of tile kt+2 (then the cursor tail), behind each unit of the second half one fragment read of tile kt+1, so that
+        // no wave sends its 8 DMA requests and 6 LDS reads through the CU in one burst while the matrix pipe has nothing to do.
+        // Every path into the last group and into the next k-step has the same LDS counts pending: the fragment reads are
+        // unconditional (in the last k-step they fetch a tile nobody uses; the epilogue opens with a wait and a barrier), and the
+        // DMA pieces, which the LDS counter does not see, sit under the wave-uniform `kt + 2 < nk`.  So the compiler needs no
+        // wait-for-everything where paths join, and the only wait for the new fragments is q0's of the next k-step.
+        // (ONE loop body on purpose: with the last two k-steps peeled into copies, the compiler kept the accumulators of the
+        // 4-wave kernels in AGPRs in one copy and in VGPRs in the next, moved them in between, and lost a workgroup per CU.)
+        constexpr int NU = 4 * TM, ND = AP + BP, NF = TM + TN, UH = NU / 2;
+        static_assert(NQ % 2 == 0 && NU % 2 == 0, "k-step schedule");
+        // the dead fragment reads of the last k-step are safe because the staged epilogue opens with a wait and a barrier; the
+        // transposed-output epilogue (fp16 only today) has neither
+        static_assert(!TOUT, "the fp32 k-step needs the staged epilogue's opening wait + barrier");
+        for (int kt = 0; kt < nk; ++kt) {
+            const int buf = kt & 1;
+            const bool dma = kt + 2 < nk;
+#pragma unroll
+            for (int q = 0; q + 1 < NQ; ++q) {   // fragment sets alternate by the parity of q (NQ is even)
+                if (q & 1) { HMV_FRAGS(fa0, fb0, buf, q + 1); HMV_MFMA(fa1, fb1); }
+                else { HMV_FRAGS(fa1, fb1, buf, q + 1); HMV_MFMA(fa0, fb0); }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // the last group's fragments (set 1) pass through an empty statement: the compiler's own wait for them lands HERE, in
+            // front of the barrier, where the explicit wait stands anyway, and not between the barrier and the first MFMA
+            // (not in the block-skipping kernels, whose skipped blocks have no fragments: there the compiler's wait follows the
+            // barrier and finds the counter at zero already)
+            if constexpr (!PARTN) {
+#pragma unroll
+                for (int a = 0; a < TM; ++a) asm volatile("" : "+v"(fa1[a]));
+#pragma unroll
+                for (int b = 0; b < TN; ++b) asm volatile("" : "+v"(fb1[b]));
+            }
+            // tile kt+1 (the only DMA in flight) must have landed; everyone is done reading `buf`
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+#pragma unroll
+                for (int b = 0; b < TN; ++b)
+                    if (!PARTN || b < tnr)
+                        acc[u % TM][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[u % TM][u / TM], fb1[b][u / TM], acc[u % TM][b], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (u < UH && dma) {   // the DMA pieces of this slot
+                    if (u == 0) HMV_DMA_PRE;
+#pragma unroll
+                    for (int j = 0; j < ND; ++j)
+                        if (j * UH / ND == u) {
+                            if (j < AP) { HMV_DMA_A(buf, j); } else { HMV_DMA_B(buf, j - AP); }   // (one of the two survives the unrolling)
+                        }
+                    if (u == (ND - 1) * UH / ND) HMV_DMA_TAIL;
+                }
+#pragma unroll
+                for (int f = 0; f < NF; ++f)   // the fragment reads of this slot: group 0 of the next tile
+                    if (UH + f * (UH - 1) / NF == u) {
+                        const int cf_ = (kh ^ (f < TM ? fsw : fswb)) * EPC;
+                        if (f < TM) {
+                            if (!PARTN || tnr > 0) fa0[f] = *reinterpret_cast<const f32x4 *>(arow + ((buf ^ 1) * BM + f * 32) * KB + cf_);
+                        } else if (!PARTN || f - TM < tnr) {
+                            fb0[f - TM] = *reinterpret_cast<const f32x4 *>(brow + ((buf ^ 1) * BN + (f - TM) * 32) * KB + cf_);
+                        }
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        done = true;
+    }
+    for (int kt = 0; F16 && !done && kt < nk; ++kt) {   // the fp16 k-step
         const int buf = kt & 1;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {   // fragment sets alternate by the parity of q (NQ is even)
@@ -586,6 +672,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
         }
     }
 #undef HMV_DMA
+#undef HMV_DMA_PRE
+#undef HMV_DMA_A
+#undef HMV_DMA_B
+#undef HMV_DMA_TAIL
 #undef HMV_HALO_SET
 #undef HMV_FRAGS
 #undef HMV_FRAG_A
@@ -1205,8 +1295,9 @@ ConvTile conv_pick_tile(int M, int Cout, int K, bool f16, bool has_res) {
     static const int forced = HMV_DEV_INT("HMV_FORCE_TILE", -1);   // development knob: HMV_FORCE_TILE=<ConvTile> for layers with Cout > 64
     static const bool force_all = HMV_DEV_ENV("HMV_FORCE_TILE_ALL") != nullptr;   // ... and for the narrow layers too
     if ((Cout > 64 || force_all) && forced >= 0 && forced < TILE_COUNT) return (ConvTile)forced;
-    // Measured on MI355X (tools/conv_sweep.py): the matrix pipe is DVFS/power limited, so the tile with
-    // the least L2->LDS traffic per FLOP wins as long as it still fills the 256 CUs for several rounds.
+    // Measured on MI355X (tools/conv_sweep.py): the tile with the least L2->LDS traffic per FLOP wins as long as it still fills
+    // the 256 CUs for several rounds.  (fp16: the matrix pipe is DVFS / power limited.  fp32: the kernels run at the full clock,
+    // 2.3-2.4 GHz, with the pipe busy 0.77-0.89 of the time -- fewer operand bytes per MFMA mean fewer idle pipe cycles.)
     // tiny-K expanding convs (layer1/2 conv3 + residual) are epilogue/HBM-bound: 4 small blocks per CU
     // overlap one block's residual read / store with the others' short main loops
     // fp32 only: with 16-byte vectors on both sides of the fp16 epilogue the big tile wins there too (forced-tile

@@ -16,4 +16,7 @@ def __getattr__(name):
     if name in ("SequenceEvaluator", "labels_to_windows"):   # evaluating a followed sequence (sequence_eval.py)
         from . import sequence_eval
         return getattr(sequence_eval, name)
+    if name in ("SubsetSweepEvaluator", "k_of_n", "as_subset_table"):   # camera-subset sweeps (subsets.py)
+        from . import subsets
+        return getattr(subsets, name)
     raise AttributeError(name)

@@ -17,7 +17,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views", "hmv_pose_losses_views",
            "hmv_eval_add_views", "hmv_forward_frames_views", "hmv_op_next_crop_boxes", "hmv_forward_frames_track",
            "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
-           "hmv_seq_eval_history_floats", "hmv_seq_eval_add"]
+           "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets"]
 
 HMV_OK = 0
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
@@ -95,6 +95,8 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward.argtypes = [vp, ci, fp, fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_views.restype = ctypes.c_int
+    lib.hmv_forward_subsets.argtypes = [vp, ci, ci, fp, fp, fp, fp, fp, fp, fp, vp]   # (subset_mask: host uint8 [S][V])
+    lib.hmv_forward_subsets.restype = ctypes.c_int
     lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
     lib.hmv_op_attention_views.restype = ctypes.c_int
     lib.hmv_last_error.argtypes = [vp]

@@ -1223,6 +1223,7 @@ struct Runner {
     int rc = HMV_OK;
     Arena &A;
     const ViewSet *vs = nullptr;   // not null: a ragged forward (hmv_forward_views); stages are not captured then
+    bool sweep = false;            // a camera-subset sweep (hmv_forward_subsets): the token rows leave tokens_stage without PE and pair copy; no stages
 
     float *alloc(size_t n) {
         float *ptr = A.alloc(n);
@@ -1609,7 +1610,7 @@ struct Runner {
 
     // feats[0] as fp32 NCHW into the capture buffer
     void capture_feat0(const Map &f) {
-        if (!h->capture || dry || vs || !h->cap_feat0) return;
+        if (!h->capture || dry || vs || sweep || !h->cap_feat0) return;
         if (split) LAUNCH(launch_nhwc_split_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
         else if (h16) LAUNCH(launch_nhwc_f16_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s));
         else LAUNCH(launch_nhwc_to_nchw(f.p, h->cap_feat0, f.N, f.H, f.W, f.C, s, f.ld));
@@ -1823,7 +1824,7 @@ struct Runner {
         float *coords = alloc((size_t)N * NJ * 2);
         LAUNCH(launch_soft_argmax(f.hm.p, f.hm.ld, N, f.hm.H, f.hm.W, coords, crop_img, (float)c.image_size, (float)c.heatmap_size, heatmap, s));
         release(f.hm);
-        if (h->capture && !dry && !vs && h->cap_coords)
+        if (h->capture && !dry && !vs && !sweep && h->cap_coords)
             LAUNCH(hipMemcpyAsync(h->cap_coords, coords, (size_t)N * NJ * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
 
         // ---- sample nets as gather -> conv1x1+BN+ReLU -> bilinear blend (nets.py:46-63; handmvnet.py:185-187)
@@ -1846,9 +1847,11 @@ struct Runner {
         // pos2d / FoV / zero pad / PE (handmvnet.py:189-225; fusion.py:27-28).  In the fp16-kernel modes the q/k/v projections of
         // CrossAttentionFusion read their token rows as (hi, lo) fp16 pairs: the kernel that produces a block's input rows -- this one for
         // block 0, ff_block_kernel for the others -- writes that copy itself (rows_f32_to_half's arithmetic, one launch less per block)
-        if (!h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = alloc((size_t)N * NJ * ldt);
+        // A sweep stops before the part that depends on the camera subset: no PE, no pair copy (tokens_expand_subsets_kernel adds both per subset)
+        if (!sweep && !h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane) Xpairs = alloc((size_t)N * NJ * ldt);
         const float *pe = (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe;   // the learnable-query blocks add their own PE
-        if (vs) LAUNCH(launch_tokens_finalize_views(tokens, ldt, d, h->fdim, N, vs->fpos, coords, bbox, intr, c.pos_enc, pe, s, Xpairs, h->sat));
+        if (sweep) LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc, nullptr, nullptr, s, nullptr, nullptr));
+        else if (vs) LAUNCH(launch_tokens_finalize_views(tokens, ldt, d, h->fdim, N, vs->fpos, coords, bbox, intr, c.pos_enc, pe, s, Xpairs, h->sat));
         else LAUNCH(launch_tokens_finalize(tokens, ldt, d, h->fdim, N, V, coords, bbox, intr, c.pos_enc, pe,
                                            (h->capture && h->cap_tokens) ? h->cap_tokens : nullptr, s, Xpairs, h->sat));
         release(coords);
@@ -2030,17 +2033,24 @@ struct Runner {
 };
 #undef LAUNCH
 
+// the second stream of the HRNet branch overlap, made by the first real forward that needs it
+int ensure_aux_stream(hmv_engine *h) {
+    if (h->hrnet && h->hr_overlap && h->cfg.dtype != HMV_F32 && !h->aux) {   // (the first forward of a handle is never a captured one)
+        if (hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
+            return h->fail(HMV_ERR_HIP, "second stream for the HRNet branches");
+    }
+    return HMV_OK;
+}
+
 // HandMvNet.forward (handmvnet.py:158-266), stage by stage; a planning run (dry) issues the same alloc / release sequence and launches nothing
 // vs (ragged view sets, hmv_forward_views): the backbone and the token stage run on vs->N frames, the fusion over each sample's own rows
 int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const float *intr, float *crop_img, float *joints_cam,
                 float *heatmap, hipStream_t s, bool dry, Arena &A, const ViewSet *vs = nullptr) {
     Runner R{h, s, dry, HMV_OK, A, vs};
     const hmv_config &c = h->cfg;
-    if (!dry && h->hrnet && h->hr_overlap && c.dtype != HMV_F32 && !h->aux) {   // (the first forward of a handle is never a captured one)
-        if (hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
-            return h->fail(HMV_ERR_HIP, "second stream for the HRNet branches");
-    }
+    if (!dry)
+        if (const int rc = ensure_aux_stream(h)) return rc;
     const int N = vs ? vs->N : B * c.num_views;
     const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
     float *Xpairs = nullptr;
@@ -2049,6 +2059,59 @@ int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const f
     X = h->lq ? R.fusion_learnable_query(B, X, Tcur) : R.fusion_cross_attn(B, X, Xpairs, Tcur);
     if (h->capture && !dry && !vs && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, s); });
     R.decoder(B, X, joints_cam);
+    return R.rc;
+}
+
+// One fusion pass of a camera-subset sweep (hmv_forward_subsets).  Virtual sample q is sample q % B under subset q / B; the pass takes the
+// virtual samples q0 .. q0 + nv, n packed frames in all, at most vmax cameras in one.  Its tables start `tab` entries into the call's
+// table: [seg: nv + 1 | fpos: n | src: n], seg and fpos as a ViewSet's, src[m] = the frame b * V + camera that packed frame m repeats.
+struct SubsetChunk { int q0, nv, n, vmax; size_t tab; };
+
+// The sweep: backbone and token stage ONCE on all B * V frames -- the rows [B * V * 21][ldt] stay, finalised without PE -- then per chunk the
+// packed rows of its virtual samples (tokens_expand_subsets_kernel) and the unchanged ragged fusion and decoder over them, which write
+// joints_cam[q0 .. q0 + nv).  tab: the call's device table (null in a planning run).  Per-sample arithmetic never depends on a size, so a
+// subset's bits do not depend on the chunks.  While profiling, one bracketing record around the per-frame stage ("subsets_frames") and one
+// around every pass ("subsets_tail") besides the launches' own.
+int run_forward_subsets(hmv_engine *h, int B, const std::vector<SubsetChunk> &chunks, const int32_t *tab, const float *x, const float *bbox,
+                        const float *intr, float *crop_img, float *joints_cam, float *heatmap, hipStream_t s, bool dry, Arena &A) {
+    Runner R{h, s, dry, HMV_OK, A, nullptr, true};
+    const hmv_config &c = h->cfg;
+    if (!dry)
+        if (const int rc = ensure_aux_stream(h)) return rc;
+    auto bracket_begin = [&](const char *label) {   // (an index: nested records may move the list)
+        if (!h->profiling || dry) return (size_t)-1;
+        R.prof_begin(label);
+        return h->prof_used - 1;
+    };
+    auto bracket_end = [&](size_t i, const char *name) {
+        if (i == (size_t)-1) return;
+        h->prof[i].flops = h->prof[i].bytes = 0;
+        R.prof_end(&h->prof[i], name);
+    };
+    const int N = B * c.num_views, ldt = h->ldt;
+    size_t br = bracket_begin("frames");
+    const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
+    float *no_pairs = nullptr;
+    float *rows = R.tokens_stage(f, bbox, intr, crop_img, heatmap, no_pairs);
+    bracket_end(br, "subsets_frames");
+    const bool want_pairs = !h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane;   // (as tokens_stage decides for a forward)
+    const float *pe = (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe;
+    for (const SubsetChunk &ck : chunks) {
+        br = bracket_begin("tail");
+        const int32_t *t = tab ? tab + ck.tab : nullptr;
+        const ViewSet vs{ck.n, t, t ? t + ck.nv + 1 : nullptr, NJ * ck.vmax};
+        const int32_t *src = t ? t + ck.nv + 1 + ck.n : nullptr;
+        float *X = R.alloc((size_t)ck.n * NJ * ldt);
+        float *Xpairs = want_pairs ? R.alloc((size_t)ck.n * NJ * ldt) : nullptr;
+        R.launch("tokens_expand_subsets", [&] { return launch_tokens_expand_subsets(rows, ldt, h->d, ck.n, src, vs.fpos, pe, X, Xpairs, s, h->sat); });
+        R.vs = &vs;
+        int Tcur = vs.Tmax;
+        X = h->lq ? R.fusion_learnable_query(ck.nv, X, Tcur) : R.fusion_cross_attn(ck.nv, X, Xpairs, Tcur);
+        R.decoder(ck.nv, X, joints_cam ? joints_cam + (size_t)ck.q0 * NJ * 3 : nullptr);
+        R.vs = nullptr;
+        bracket_end(br, "subsets_tail");
+    }
+    R.release(rows);
     return R.rc;
 }
 
@@ -2236,10 +2299,57 @@ static int check_views(hmv_handle h, const char *who, int32_t batch, const int32
     return HMV_OK;
 }
 
+// The next slot of the ring of pinned host tables, free to be rewritten (the upload that last read it has run) and with room for tab_n entries
+static int views_slot(hmv_handle h, size_t tab_n, hmv_engine::ViewsSlot *&out) {
+    hmv_engine::ViewsSlot &slot = h->views_host[h->views_next++ % 4];
+    if (slot.done) HIPCHK(h, hipEventSynchronize(slot.done));
+    else HIPCHK(h, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (tab_n > slot.cap) {
+        if (slot.host) HIPCHK(h, hipHostFree(slot.host));
+        slot.host = nullptr;
+        slot.cap = 0;
+        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
+        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&slot.host), cap * sizeof(int32_t), hipHostMallocDefault));
+        slot.cap = cap;
+    }
+    out = &slot;
+    return HMV_OK;
+}
+
+// A call whose own plan needs more than the reserved workspace (checked before anything is launched): the workspace grows
+static int grow_workspace(hmv_handle h, size_t need) {
+    if (need <= h->arena_bytes) return HMV_OK;
+    HIPCHK(h, hipDeviceSynchronize());
+    h->drop_graphs();   // captured launches point into the old workspace
+    if (h->arena) HIPCHK(h, hipFree(h->arena));
+    h->arena = nullptr;
+    h->arena_bytes = 0;
+    const int served = h->reserved_batch;   // the larger workspace still serves as many uniform samples
+    h->reserved_batch = 0;
+    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->arena), need));
+    h->arena_bytes = need;
+    h->reserved_batch = served;
+    return HMV_OK;
+}
+
+// The slot's tab_n entries to the device table, on the caller's stream
+static int upload_views(hmv_handle h, hmv_engine::ViewsSlot &slot, size_t tab_n, hipStream_t s) {
+    if (tab_n > h->views_cap) {   // (hipFree waits for the launches that still read the old table)
+        if (h->views_dev) HIPCHK(h, hipFree(h->views_dev));
+        h->views_dev = nullptr;
+        h->views_cap = 0;
+        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->views_dev), cap * sizeof(int32_t)));
+        h->views_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->views_dev, slot.host, tab_n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipEventRecord(slot.done, s));
+    return HMV_OK;
+}
+
 // the ragged forward behind hmv_forward_views (x) and hmv_forward_frames_views (h->fsrc set, x null); the arguments have been checked
 static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox,
                                 const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    const int V = h->cfg.num_views;
     size_t N = 0;
     int vmax = 0;
     for (int b = 0; b < batch; ++b) {
@@ -2253,17 +2363,9 @@ static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view
     }
     // the tables: [seg: B + 1 | fpos: N]
     const size_t tab_n = (size_t)batch + 1 + N;
-    hmv_engine::ViewsSlot &slot = h->views_host[h->views_next++ % 4];
-    if (slot.done) HIPCHK(h, hipEventSynchronize(slot.done));
-    else HIPCHK(h, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (tab_n > slot.cap) {
-        if (slot.host) HIPCHK(h, hipHostFree(slot.host));
-        slot.host = nullptr;
-        slot.cap = 0;
-        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (V + 1) + 1);
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&slot.host), cap * sizeof(int32_t), hipHostMallocDefault));
-        slot.cap = cap;
-    }
+    hmv_engine::ViewsSlot *slot_p = nullptr;
+    if (const int rc = views_slot(h, tab_n, slot_p)) return rc;
+    hmv_engine::ViewsSlot &slot = *slot_p;
     int32_t *seg = slot.host, *fpos = seg + batch + 1;
     seg[0] = 0;
     for (int b = 0, n = 0; b < batch; ++b) {
@@ -2281,30 +2383,10 @@ static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view
         h->profiling = false;
         run_forward(h, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry, &vs);
         h->profiling = saved;
-        if (dry.high > h->arena_bytes) {
-            HIPCHK(h, hipDeviceSynchronize());
-            h->drop_graphs();   // captured launches point into the old workspace
-            if (h->arena) HIPCHK(h, hipFree(h->arena));
-            h->arena = nullptr;
-            h->arena_bytes = 0;
-            const int served = h->reserved_batch;   // the larger workspace still serves as many uniform samples
-            h->reserved_batch = 0;
-            HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->arena), dry.high));
-            h->arena_bytes = dry.high;
-            h->reserved_batch = served;
-        }
-    }
-    if (tab_n > h->views_cap) {   // (hipFree waits for the launches that still read the old table)
-        if (h->views_dev) HIPCHK(h, hipFree(h->views_dev));
-        h->views_dev = nullptr;
-        h->views_cap = 0;
-        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (V + 1) + 1);
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->views_dev), cap * sizeof(int32_t)));
-        h->views_cap = cap;
+        if (const int rc = grow_workspace(h, dry.high)) return rc;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(h, hipMemcpyAsync(h->views_dev, slot.host, tab_n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipEventRecord(slot.done, s));
+    if (const int rc = upload_views(h, slot, tab_n, s)) return rc;
     vs.seg = h->views_dev;
     vs.fpos = h->views_dev + batch + 1;
     h->last_ragged = true;
@@ -2342,6 +2424,74 @@ int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, c
     if (batch > 0 && view_counts && (!x || !joints_crop_img || !joints_cam)) return h->fail(HMV_ERR_ARG, "null or empty input/output");
     if (const int rc = check_views(h, "hmv_forward_views", batch, view_counts, bbox, intrinsic)) return rc;
     return forward_views_common(h, batch, view_counts, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
+}
+
+/* A camera-subset sweep (include/handmv.h): one backbone pass, the fusion tail per subset.  Everything that can be refused is refused, and
+ * the whole call is planned on the host -- chunks, tables, workspace -- before the first launch.  Always eager. */
+int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const uint8_t *subset_mask, const float *x, const float *bbox,
+                        const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (batch <= 0) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: batch must be positive (got %d)", (int)batch);
+    if (n_subsets < 1) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: n_subsets must be at least 1 (got %d)", (int)n_subsets);
+    if (!subset_mask) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: subset_mask is null (host uint8 [n_subsets][num_views])");
+    if (!x || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: null or empty input/output");
+    const int V = h->cfg.num_views, S = n_subsets;
+    if ((long long)S * batch > INT32_MAX / (NJ * 3)) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: n_subsets x batch is too large");
+    std::vector<int> count(S, 0);
+    for (int i = 0; i < S; ++i) {
+        for (int v = 0; v < V; ++v) count[i] += subset_mask[(size_t)i * V + v] != 0;
+        if (!count[i]) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: subset %d has no camera", i);
+    }
+    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
+        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (batch > h->reserved_batch) {
+        const int rc = hmv_reserve(h, batch);
+        if (rc != HMV_OK) return rc;
+    }
+    // the passes: at most max(batch, reserved batch) virtual samples each, so that every buffer of a pass stays within the reservation
+    const int total = S * batch, cmax = std::max<int>(batch, h->reserved_batch);
+    std::vector<SubsetChunk> chunks;
+    size_t tab_n = 0;
+    for (int q0 = 0; q0 < total; q0 += cmax) {
+        SubsetChunk ck{q0, std::min(cmax, total - q0), 0, 0, tab_n};
+        for (int q = q0; q < q0 + ck.nv; ++q) {
+            ck.n += count[q / batch];
+            ck.vmax = std::max(ck.vmax, count[q / batch]);
+        }
+        tab_n += (size_t)ck.nv + 1 + 2 * (size_t)ck.n;
+        chunks.push_back(ck);
+    }
+    hmv_engine::ViewsSlot *slot = nullptr;
+    if (const int rc = views_slot(h, tab_n, slot)) return rc;
+    for (const SubsetChunk &ck : chunks) {
+        int32_t *seg = slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
+        seg[0] = 0;
+        for (int i = 0, m = 0; i < ck.nv; ++i) {
+            const int q = ck.q0 + i, sub = q / batch, b = q % batch;
+            seg[i + 1] = seg[i] + NJ * count[sub];
+            for (int v = 0, r = 0; v < V; ++v)
+                if (subset_mask[(size_t)sub * V + v]) { fpos[m] = NJ * r++; src[m++] = b * V + v; }
+        }
+    }
+    {   // the call's own plan -- the retained rows and a pass's packed rows come on top of a forward's buffers -- before anything is launched
+        Arena dry;
+        dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));
+        const bool saved = h->profiling;
+        h->profiling = false;
+        run_forward_subsets(h, batch, chunks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry);
+        h->profiling = saved;
+        if (const int rc = grow_workspace(h, dry.high)) return rc;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = upload_views(h, *slot, tab_n, s)) return rc;
+    h->last_ragged = true;   // (no stages either)
+    h->plan.reset(h->arena);
+    h->launches = 1;
+    const int rc = run_forward_subsets(h, batch, chunks, h->views_dev, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan);
+    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    return rc;
 }
 
 /* hmv_forward_views from raw camera frames (include/handmv.h): the indexed frame preparation in front of the ragged forward. */

@@ -250,6 +250,10 @@ hipError_t launch_attention_d256_views(const float *q, int q_ld, int q_seg, cons
 hipError_t launch_add_pe_views(const float *x, int ldx, int rows, const int *fpos, int d, const float *pe, float *y, int ldy, hipStream_t s);
 // out[b * 21 + j][0, ld) = x[seg[b] + j][0, ld): the cross block's residual rows `_q`, contiguous (ld % 4 == 0)
 hipError_t launch_gather_query_rows(const float *x, int ld, const int *seg, int B, float *out, hipStream_t s);
+// ---- camera-subset sweep (hmv_forward_subsets): out[(m, j)] = rows[(src[m], j)] (+ pe[fpos[m] + j] where pe is not null) for the n_frames
+// packed frames of a chunk of virtual samples; `rows` were finalised without PE; pad columns zero; pairs as launch_tokens_finalize's
+hipError_t launch_tokens_expand_subsets(const float *rows, int ldt, int d, int n_frames, const int *src, const int *fpos, const float *pe,
+                                        float *out, void *pairs, hipStream_t s, int *sat = nullptr);
 // split-K GEMM tail: out[r][c] = act(sum_s slab[s][r][c] + bias[c] + res[r'][c]) for c < N (slices summed in index order)
 hipError_t launch_splitk_layernorm(const float *slab, int S, int rows, int lds, int d, const float *bias, const float *res, int ldr,
                                    int rg_out, int rg_in, const float *g1, const float *b1, float *y, int ldy, const float *g2,

@@ -947,6 +947,70 @@ hipError_t launch_gather_query_rows(const float *x, int ld, const int *seg, int 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ camera-subset sweep (hmv_forward_subsets)
+// The token rows of a chunk of virtual samples from the rows a sweep retained: packed row (frame m, joint j) is retained row
+// (src[m], j) -- finalised WITHOUT the positional encoding: pos2d / FoV columns and zero pad are in place -- plus PE row fpos[m] + j
+// where the fusion adds the sinusoidal PE to its input (pe != null): the one fp32 addition of tokens_finalize_body.inc, so the rows
+// carry the bits tokens_finalize_views_kernel writes for a sample with these views.  Pad columns [d, ldt) are written as zeros; pairs
+// (optional): the rows once more as [hi ldt | lo ldt] halfs, split_f16's arithmetic, as the finalise kernels write them.
+// One wave per row, eight columns per lane and step: 16-byte loads and stores throughout (ldt % 8 == 0; PE rows are 16-byte aligned
+// iff d % 4 == 0, else they are read element by element).
+__global__ __launch_bounds__(256) void tokens_expand_subsets_kernel(const float *__restrict__ rows, int ld8, int d, const int *__restrict__ src,
+        const int *__restrict__ fpos, const float *__restrict__ pe, float *__restrict__ out, _Float16 *__restrict__ pairs, int n_rows, int *sat) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);   // (wave-uniform)
+    if (row >= n_rows) return;
+    const int m = row / 21, j = row - m * 21;
+    const f32x4 *in4 = reinterpret_cast<const f32x4 *>(rows) + ((size_t)src[m] * 21 + j) * (2 * ld8);
+    f32x4 *out4 = reinterpret_cast<f32x4 *>(out) + (size_t)row * (2 * ld8);
+    const float *per = pe ? pe + ((size_t)fpos[m] + j) * d : nullptr;
+    const bool pe_vec = (d & 3) == 0;
+    bool ov = false;
+    for (int c8 = lane; c8 < ld8; c8 += 64) {
+        f32x4 v[2] = {in4[2 * c8], in4[2 * c8 + 1]};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int col = 8 * c8 + 4 * q;
+            if (col >= d) { v[q] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+            if (per && pe_vec) {   // (col + 3 < d)
+                const f32x4 p = *reinterpret_cast<const f32x4 *>(per + col);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[q][e] = v[q][e] + p[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (col + e >= d) v[q][e] = 0.f;
+                    else if (per) v[q][e] = v[q][e] + per[col + e];
+                }
+            }
+        }
+        out4[2 * c8] = v[0];
+        out4[2 * c8 + 1] = v[1];
+        if (pairs) {
+            f16x8 hi, lo;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                _Float16 a, b;
+                ov |= split_f16(v[e >> 2][e & 3], a, b);
+                hi[e] = a; lo[e] = b;
+            }
+            f16x8 *p8 = reinterpret_cast<f16x8 *>(pairs) + (size_t)row * (2 * ld8);
+            p8[c8] = hi;
+            p8[ld8 + c8] = lo;
+        }
+    }
+    note_range(sat, ov);
+}
+hipError_t launch_tokens_expand_subsets(const float *rows, int ldt, int d, int n_frames, const int *src, const int *fpos, const float *pe,
+                                        float *out, void *pairs, hipStream_t s, int *sat) {
+    if (n_frames <= 0) return hipSuccess;
+    if (!src || !fpos || (ldt & 7) || d > ldt) return hipErrorInvalidValue;
+    const int n_rows = n_frames * 21;
+    hipLaunchKernelGGL(tokens_expand_subsets_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, rows, ldt / 8, d, src, fpos, pe, out,
+                       reinterpret_cast<_Float16 *>(pairs), n_rows, sat);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ split-K reduction
 // The token GEMMs of a small batch (to_out: M = B*V*21 rows, N = d, K = 1024) tile into a few dozen workgroups with a long
 // serial reduction.  The engine cuts K into S slices (S times the workgroups, 1/S the k-steps), each slice writes a plain

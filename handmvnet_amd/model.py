@@ -299,6 +299,51 @@ class HandMvNet(torch.nn.Module):
         out_hm = torch.zeros(b * v, 21, hs_h, hs_w, device=dev, dtype=torch.float32).index_copy_(0, idx, hm_p)
         return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
 
+    def forward_subsets(self, x, subsets, bbox=None, cam_params=None):
+        """forward_views() for S camera subsets of the same full batch at the cost of ONE backbone pass (hmv_forward_subsets): `x` is
+        the full [b, v, 3, h, w] batch and `subsets` a bool [S, v] table (array, tensor or nested list) or a sequence of camera-index
+        lists (handmvnet_amd.subsets.k_of_n builds "every k of v"); one table serves the whole batch.  Returns forward()'s dict with
+        `joints_cam` of shape [S, b, 21, 3]: joints_cam[s] holds the bits forward_views() returns with view_mask = subset s on every
+        sample.  `joints_crop_img` and `heatmap` are forward()'s, written once for all v views.  The table is read on the host."""
+        from .subsets import as_subset_table
+        if not isinstance(x, torch.Tensor) or x.dim() != 5:
+            raise ValueError("x must be a [b, v, 3, h, w] tensor")
+        b, v, c, hh, ww = x.shape
+        if c != 3:
+            raise ValueError("x must have 3 channels")
+        if v != self.num_views:
+            raise ValueError(f"x must hold all {self.num_views} views per sample (the subsets name the present ones), got {v}")
+        if b == 0:
+            raise ValueError("x holds no sample")
+        table = as_subset_table(subsets, v)
+        if not x.is_cuda:
+            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
+        dev = x.device
+        x = x.contiguous().float()
+        bb = it = None
+        if "crop" in self.cfg.pos_enc:
+            if bbox is None or cam_params is None:
+                raise TypeError("pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required")
+            bb = bbox.to(dev).reshape(-1, 4).contiguous().float()
+            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).contiguous().float()
+            if bb.shape[0] != b * v or it.shape[0] != b * v:
+                raise RuntimeError("bbox / intrinsic must hold one row per frame")
+        didx = dev.index if dev.index is not None else torch.cuda.current_device()
+        h = self._engine(hh, ww, didx)
+        hs_h, hs_w = heatmap_size_of(self.cfg, hh, ww)
+        S = table.shape[0]
+        out_crop = torch.empty(b, v, 21, 2, device=dev, dtype=torch.float32)
+        out_cam = torch.empty(S, b, 21, 3, device=dev, dtype=torch.float32)
+        out_hm = torch.empty(b, v, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().hmv_forward_subsets(h, b, S, table.ctypes.data_as(ctypes.c_void_p), x.data_ptr(),
+                                                 bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None,
+                                                 out_crop.data_ptr(), out_cam.data_ptr(), out_hm.data_ptr(), ctypes.c_void_p(stream))
+        _lib.check(rc, h)
+        self._last_key = (hh, ww, didx, b, self._dtype)
+        return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
+
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                        image_size=None, view_mask=None):
         """forward() from raw camera frames: `frames` uint8 [b, v, Hf, Wf, 3] and integer crop windows `crop_boxes`
@@ -502,6 +547,21 @@ class HandMvNet(torch.nn.Module):
         ragged loss and the ragged accumulation, at the cost of its present frames; ragged and uniform batches may be mixed."""
         from .evaluation import EpochEvaluator
         ev = EpochEvaluator(self, mode)
+        for batch in batches:
+            ev.step(batch)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            ev.reduce(group)
+        return ev.compute()
+
+    def evaluate_subsets(self, batches, subsets, mode: str = "test", group=None) -> dict:
+        """evaluate() for S camera subsets in one pass over `batches` (full-view batches, no view_mask): per step one forward_subsets
+        call -- one backbone pass, S fusion tails -- then per subset the ragged loss and accumulation evaluate() runs; one all-reduce
+        of the whole [S][state] tensor under torch.distributed, one readback.  Returns {"subsets": the camera-index lists,
+        "per_subset": per subset the dict evaluate() returns for these batches with view_mask = that subset on every sample (equal
+        values), "by_count": per view count k the plain mean of the scalar entries over the subsets with k cameras}
+        (handmvnet_amd/subsets.py).  Like evaluate(), converts each batch's joints_cam / root_joint from mm to metres in place."""
+        from .subsets import SubsetSweepEvaluator
+        ev = SubsetSweepEvaluator(self, subsets, mode)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():

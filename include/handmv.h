@@ -172,6 +172,25 @@ int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, 
 int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
                       float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
 
+/* A camera-subset sweep (the camera ablation: "which k of the V cameras"): hmv_forward_views for n_subsets camera subsets of the SAME
+ * full batch at the cost of ONE backbone pass.  Everything up to the per-frame token rows does not depend on which other views are
+ * present, so it runs once on all batch * V frames; the positional encoding (by a frame's rank among the present views), the fusion
+ * blocks and the decoder run once per subset.  joints_cam[s] holds the bits hmv_forward_views writes for this batch when every sample
+ * brings the cameras of subset s.
+ *   subset_mask     HOST uint8 [n_subsets][cfg.num_views], non-zero = the camera is present; one table for the whole batch; read
+ *                   before the call returns.  Duplicate subsets are allowed
+ *   x, bbox, intrinsic, joints_crop_img, heatmap: the FULL batch, exactly as for hmv_forward; both outputs are written once
+ *   joints_cam      [n_subsets][batch][21][3]  out
+ * The fusion runs in passes of at most max(batch, reserved batch) virtual samples (a virtual sample = one sample under one subset), so
+ * that every buffer of a pass stays within the reservation; the retained token rows and a pass's packed rows come on top, and the
+ * workspace grows before the first launch where that takes it past the reservation.  A subset's bits do not depend on the passes.
+ * Asynchronous on `stream` and without a device synchronisation, like hmv_forward_views (one table upload).  Always eager, records no
+ * stages (reading one afterwards returns HMV_ERR_STATE); the range report covers it.  With profiling on, the record list also holds one
+ * bracketing record "subsets_frames" around the per-frame stage and one "subsets_tail" around every pass.
+ * HMV_ERR_ARG, before anything is launched, for: batch <= 0, n_subsets < 1, a NULL table, a subset without a camera. */
+int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const uint8_t *subset_mask, const float *x, const float *bbox,
+                        const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
+
 /* Human-readable description of the last failure on this handle, or with h == NULL of the calling thread's last failed call
  * without a handle (hmv_create, the hmv_op_* entries ...): per thread, like errno. */
 const char *hmv_last_error(hmv_handle h);

@@ -17,9 +17,12 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_eval_state_doubles", "hmv_eval_add", "hmv_forward_views", "hmv_op_attention_views", "hmv_pose_losses_views",
            "hmv_eval_add_views", "hmv_forward_frames_views", "hmv_op_next_crop_boxes", "hmv_forward_frames_track",
            "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
-           "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets"]
+           "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
+           "hmv_read_attention", "hmv_op_attention_probs"]
 
 HMV_OK = 0
+HMV_ERR_ARG = 1
+HMV_ERR_STATE = 2
 HMV_ERR_RANGE = 7   # a value outside the fp16 range of its mode (include/handmv.h: "Range contract")
 
 
@@ -99,6 +102,14 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_subsets.restype = ctypes.c_int
     lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
     lib.hmv_op_attention_views.restype = ctypes.c_int
+    lib.hmv_set_attention_capture.argtypes = [vp, ctypes.c_uint32]
+    lib.hmv_set_attention_capture.restype = ctypes.c_int
+    lib.hmv_attention_shape.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.hmv_attention_shape.restype = ctypes.c_int
+    lib.hmv_read_attention.argtypes = [vp, ci, fp, ctypes.c_size_t, fp, ctypes.c_size_t, vp]
+    lib.hmv_read_attention.restype = ctypes.c_int
+    lib.hmv_op_attention_probs.argtypes = [ci, ci, fp, fp, ci, ci, ci, ci, ci, ctypes.POINTER(ci), fp, fp, ci, vp]
+    lib.hmv_op_attention_probs.restype = ctypes.c_int
     lib.hmv_last_error.argtypes = [vp]
     lib.hmv_last_error.restype = ctypes.c_char_p
     lib.hmv_destroy.argtypes = [vp]

@@ -222,6 +222,24 @@ struct hmv_engine {
     float *cap_feat0 = nullptr, *cap_coords = nullptr, *cap_tokens = nullptr, *cap_fused = nullptr;
     size_t cap_feat0_n = 0, cap_coords_n = 0, cap_tokens_n = 0, cap_fused_n = 0;
 
+    // attention maps (hmv_set_attention_capture; attention_probs.hip): bit l of att_mask selects fusion block l.  A selected block owns a map
+    // and a view-share buffer outside the workspace, sized for att_batch full-view samples (ensure_attention); B / Tq / Tk / views are
+    // what the LAST forward left in them (valid: it did; every forward and sweep clears it first).  A non-zero mask keeps forwards eager.
+    struct AttMap {
+        float *probs = nullptr, *share = nullptr;
+        size_t probs_cap = 0, share_cap = 0;
+        bool valid = false;
+        int B = 0, Tq = 0, Tk = 0, views = 0;
+    };
+    uint32_t att_mask = 0, att_alloc_mask = 0;   // selected now / what the buffers were allocated for
+    int att_batch = 0;
+    std::vector<AttMap> att;
+    int fusion_blocks() const { return lq ? 5 : cfg.fusion_layers; }
+    int cross_block() const { return lq ? 2 : (cfg.fusion_layers - 1) / 2; }
+    void forget_attention() {
+        for (AttMap &m : att) m.valid = false;
+    }
+
     // set only for the duration of hmv_forward_frames / hmv_forward_frames_views: raw camera frames instead of prepared NCHW input
     struct FrameSrc {
         const uint8_t *frames = nullptr;
@@ -1278,6 +1296,26 @@ struct Runner {
         if (!dry && rc == HMV_OK) { check(f(), what); h->launches += n; }
     }
 
+    // Fusion block l's attention map, directly behind its attention launch, where hmv_set_attention_capture selected the block (a sweep
+    // ignores the mask).  kind / q / k / pr as launch_attention_probs takes them; views > 0: the block's keys are whole views, the share per
+    // view follows (rank0: the view rank of key 0).  A ragged call's map is zero-filled first; a block without keys (one view in the
+    // cross block) launches nothing on an empty grid and leaves a share of zeros.
+    void attention_map(int l, int kind, const void *q, int q_ld, const void *k, int kv_ld, int B, const AttnProbsRows &pr, int rank0, int views) {
+        if (dry || sweep || !((h->att_mask >> l) & 1u) || rc != HMV_OK) return;
+        hmv_engine::AttMap &m = h->att[l];
+        const size_t n = (size_t)B * 8 * pr.Tq_pad * pr.Tk_pad, ns = (size_t)B * 8 * pr.Tq_pad * views;
+        if (n > m.probs_cap || ns > m.share_cap) {
+            rc = h->fail(HMV_ERR_STATE, "attention map of block %d exceeds its buffers", l);
+            return;
+        }
+        if (pr.seg && n) LAUNCH(hipMemsetAsync(m.probs, 0, n * sizeof(float), s));
+        if (n) LAUNCH(launch_attention_probs(kind, q, q_ld, k, kv_ld, B, pr, m.probs, s));
+        if (ns && n) LAUNCH(launch_attention_share(m.probs, B, pr, rank0, views, m.share, s));
+        else if (ns) LAUNCH(hipMemsetAsync(m.share, 0, ns * sizeof(float), s));
+        m.valid = rc == HMV_OK;
+        m.B = B; m.Tq = pr.Tq_pad; m.Tk = pr.Tk_pad; m.views = views;
+    }
+
     const char **kernel_name = nullptr;   // op-level entries: receives the kernel family of the last launch
     ConvRoute route = conv_rule();        // the kernel families its launches may take (op-level entries: from a kernel_sel); planning asks with it too
 
@@ -1879,12 +1917,18 @@ struct Runner {
                 project(a.kv, xp, rows, kv, 2 * INNER_LQ);
                 if (ragged) LAUNCH(launch_attention_d256_views(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, vs->seg, Tcur, att, s, tx3 ? 1 : 0, h->sat));
                 else LAUNCH(launch_attention_d256(a.qprobe, INNER_LQ, 0, kv, kv + INNER_LQ, 2 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                attention_map(l, 2, a.qprobe, INNER_LQ, kv, 2 * INNER_LQ, B,
+                              ragged ? AttnProbsRows{vs->seg, 0, 0, NJ, 0, 0, 0, 0, NJ, Tcur} : AttnProbsRows{nullptr, 0, 0, 0, Tcur, Tq, Tcur, 0, NJ, Tcur},
+                              0, Tcur / NJ);
                 release(kv);
             } else {
                 float *qkv = alloc((size_t)rows * 3 * INNER_LQ);
                 project(a.qkv, xp, rows, qkv, 3 * INNER_LQ);
                 if (ragged) LAUNCH(launch_attention_d256_views(qkv, 3 * INNER_LQ, 1, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, vs->seg, Tcur, att, s, tx3 ? 1 : 0, h->sat));
                 else LAUNCH(launch_attention_d256(qkv, 3 * INNER_LQ, Tcur, qkv + INNER_LQ, qkv + 2 * INNER_LQ, 3 * INNER_LQ, B, Tcur, Tq, att, s, tx3 ? 1 : 0, h->sat));
+                attention_map(l, 2, qkv, 3 * INNER_LQ, qkv + INNER_LQ, 3 * INNER_LQ, B,
+                              ragged ? AttnProbsRows{vs->seg, 1, 0, 0, 0, 0, 0, 0, Tcur, Tcur} : AttnProbsRows{nullptr, 0, 0, 0, Tcur, Tq, Tcur, Tcur, Tcur, Tcur},
+                              0, l < 2 ? Tcur / NJ : 0);
                 release(qkv);
             }
             if (ff_fusable(a, qrows, tx3)) {
@@ -1949,6 +1993,13 @@ struct Runner {
             if (ragged) LAUNCH(launch_attention_views(qkv, B, vs->seg, Tcur, cross ? 1 : 0, att, s, tx3 ? 1 : 0, att_x3, h->sat));
             else if (Tk > 0) LAUNCH(launch_attention(qkv, B, Tcur, Tq, koff, Tk, att, s, tx3 ? 1 : 0, att_x3, h->sat));
             else LAUNCH(hipMemsetAsync(att, 0, (size_t)qrows * INNER * sizeof(float), s));   // (zero rows are zero pairs)
+            {   // (pair rows [hi 3072 | lo 3072]: strides and offsets in halfs)
+                const int ld = att_x3 ? 6 * INNER : 3 * INNER;
+                const void *kp = att_x3 ? static_cast<const void *>(reinterpret_cast<const _Float16 *>(qkv) + INNER) : static_cast<const void *>(qkv + INNER);
+                attention_map(l, att_x3, qkv, ld, kp, ld, B,
+                              ragged ? AttnProbsRows{vs->seg, 1, koff, cross ? NJ : 0, 0, 0, 0, 0, Tq, Tk} : AttnProbsRows{nullptr, 0, koff, 0, Tcur, Tq, Tk, Tcur, Tq, Tk},
+                              cross ? 1 : 0, l <= half ? Tcur / NJ : 0);
+            }
             release(qkv);
             // ragged cross block: the residual `_q` = each sample's first 21 rows, gathered into contiguous rows, so that everything
             // behind the attention addresses its residual row by row (rg_out = 0) as in the self blocks
@@ -2140,6 +2191,34 @@ int ensure_capture(hmv_engine *h, int B) {
     return HMV_OK;
 }
 
+// The buffers of the selected blocks' attention maps, for B full-view samples (no ragged batch of B samples needs more of any): blocks in
+// front of the cross block attend over all 21 V tokens, the cross block's 21 queries over the other views' tokens (cross_attn) or over all of
+// them (the learnable probe), the blocks behind it over the 21 fused tokens.  Only the blocks up to the cross block have views to share among.
+int ensure_attention(hmv_engine *h, int B) {
+    if (!h->att_mask || (h->att_alloc_mask == h->att_mask && h->att_batch >= B)) return HMV_OK;
+    B = std::max(B, h->att_batch);
+    const int V = h->cfg.num_views, cx = h->cross_block();
+    h->att.resize((size_t)h->fusion_blocks());
+    for (int l = 0; l < h->fusion_blocks(); ++l) {
+        hmv_engine::AttMap &m = h->att[(size_t)l];
+        for (float **p : {&m.probs, &m.share}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        m = hmv_engine::AttMap();
+        if (!((h->att_mask >> l) & 1u)) continue;
+        const size_t Tq = l == cx ? NJ : (l < cx ? (size_t)NJ * V : NJ);
+        const size_t Tk = l < cx ? (size_t)NJ * V : (l == cx ? (size_t)NJ * (h->lq ? V : V - 1) : NJ);
+        m.probs_cap = (size_t)B * 8 * Tq * Tk;
+        m.share_cap = l <= cx ? (size_t)B * 8 * Tq * V : 0;
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&m.probs), (m.probs_cap ? m.probs_cap : 1) * sizeof(float)));
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&m.share), (m.share_cap ? m.share_cap : 1) * sizeof(float)));
+    }
+    h->att_batch = B;
+    h->att_alloc_mask = h->att_mask;
+    return HMV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2170,7 +2249,8 @@ int hmv_reserve(hmv_handle h, int32_t batch) {
         h->arena_bytes = need;
         h->reserved_batch = batch;
     }
-    return ensure_capture(h, batch);
+    if (const int rc = ensure_capture(h, batch)) return rc;
+    return ensure_attention(h, batch);
 }
 
 static int forward_eager(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic,
@@ -2195,14 +2275,15 @@ static int forward_common(hmv_handle h, int32_t batch, const float *x, const flo
     if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
         return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch || (h->capture && h->cap_batch < batch)) {
+    if (batch > h->reserved_batch || (h->capture && h->cap_batch < batch) || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask))) {
         const int rc = hmv_reserve(h, batch);
         if (rc != HMV_OK) return rc;
     }
     h->last_ragged = false;
+    h->forget_attention();
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // stage capture copies into side buffers and profiling brackets launches with events: both stay eager
-    if (!h->graphs || h->capture || h->profiling)
+    // stage capture and attention capture copy into side buffers and profiling brackets launches with events: all stay eager
+    if (!h->graphs || h->capture || h->att_mask || h->profiling)
         return forward_eager(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s);
 
     hmv_engine::GraphKey key{};
@@ -2357,10 +2438,11 @@ static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view
         vmax = view_counts[b] > vmax ? view_counts[b] : vmax;
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch) {
+    if (batch > h->reserved_batch || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask))) {
         const int rc = hmv_reserve(h, batch);
         if (rc != HMV_OK) return rc;
     }
+    h->forget_attention();
     // the tables: [seg: B + 1 | fpos: N]
     const size_t tab_n = (size_t)batch + 1 + N;
     hmv_engine::ViewsSlot *slot_p = nullptr;
@@ -2487,6 +2569,7 @@ int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const ui
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const int rc = upload_views(h, *slot, tab_n, s)) return rc;
     h->last_ragged = true;   // (no stages either)
+    h->forget_attention();   // (nor attention maps: a sweep ignores the mask)
     h->plan.reset(h->arena);
     h->launches = 1;
     const int rc = run_forward_subsets(h, batch, chunks, h->views_dev, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan);
@@ -2606,6 +2689,9 @@ void hmv_destroy(hmv_handle h) {
     if (h->arena) (void)hipFree(h->arena);
     for (float *p : {h->cap_feat0, h->cap_coords, h->cap_tokens, h->cap_fused})
         if (p) (void)hipFree(p);
+    for (auto &m : h->att)
+        for (float *p : {m.probs, m.share})
+            if (p) (void)hipFree(p);
     for (auto &r : h->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     delete h;
 }
@@ -2676,6 +2762,55 @@ int hmv_read_stage(hmv_handle h, const char *stage, float *dst, size_t capacity,
     if (!src) return h->fail(HMV_ERR_STATE, "stage capture was not enabled before the forward");
     if (capacity < n) n = capacity;
     HIPCHK(h, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return HMV_OK;
+}
+
+/* Attention maps of the fusion blocks (include/handmv.h).  The buffers of an earlier mask stay until a forward under another non-zero one. */
+int hmv_set_attention_capture(hmv_handle h, uint32_t block_mask) {
+    if (!h) return HMV_ERR_ARG;
+    const int nb = h->fusion_blocks();
+    if (nb < 32 && (block_mask >> nb) != 0)
+        return h->fail(HMV_ERR_ARG, "hmv_set_attention_capture: the mask 0x%x names a block at or above the %d fusion blocks of this model", (unsigned)block_mask, nb);
+    h->att_mask = block_mask;   // (the buffers follow with the next forward or hmv_reserve: ensure_attention)
+    return HMV_OK;
+}
+
+static int attention_block(hmv_handle h, const char *who, int32_t block, const hmv_engine::AttMap *&m) {
+    if (block < 0 || block >= h->fusion_blocks())
+        return h->fail(HMV_ERR_ARG, "%s: block %d is outside the %d fusion blocks of this model", who, (int)block, h->fusion_blocks());
+    if (!((h->att_mask >> block) & 1u) || (size_t)block >= h->att.size() || !h->att[(size_t)block].valid)
+        return h->fail(HMV_ERR_STATE, "%s: the last forward left no attention map of block %d (select it with hmv_set_attention_capture before "
+                                      "the forward; a camera-subset sweep records none)", who, (int)block);
+    m = &h->att[(size_t)block];
+    return HMV_OK;
+}
+
+int hmv_attention_shape(hmv_handle h, int32_t block, int32_t *B, int32_t *Tq, int32_t *Tk, int32_t *views) {
+    if (!h) return HMV_ERR_ARG;
+    const hmv_engine::AttMap *m = nullptr;
+    if (const int rc = attention_block(h, "hmv_attention_shape", block, m)) return rc;
+    if (B) *B = m->B;
+    if (Tq) *Tq = m->Tq;
+    if (Tk) *Tk = m->Tk;
+    if (views) *views = m->views;
+    return HMV_OK;
+}
+
+int hmv_read_attention(hmv_handle h, int32_t block, float *probs, size_t probs_capacity, float *view_share, size_t share_capacity, void *stream) {
+    if (!h) return HMV_ERR_ARG;
+    const hmv_engine::AttMap *m = nullptr;
+    if (const int rc = attention_block(h, "hmv_read_attention", block, m)) return rc;
+    const size_t n = (size_t)m->B * 8 * m->Tq * m->Tk, ns = (size_t)m->B * 8 * m->Tq * m->views;
+    if (view_share && !m->views)
+        return h->fail(HMV_ERR_ARG, "hmv_read_attention: block %d lies behind the cross block, its 21 keys are no views: it has no view share", (int)block);
+    if (probs && probs_capacity < n)
+        return h->fail(HMV_ERR_ARG, "hmv_read_attention: the map of block %d holds %zu floats, probs_capacity is %zu", (int)block, n, probs_capacity);
+    if (view_share && share_capacity < ns)
+        return h->fail(HMV_ERR_ARG, "hmv_read_attention: the view share of block %d holds %zu floats, share_capacity is %zu", (int)block, ns, share_capacity);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (probs && n) HIPCHK(h, hipMemcpyAsync(probs, m->probs, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (view_share && ns) HIPCHK(h, hipMemcpyAsync(view_share, m->share, ns * sizeof(float), hipMemcpyDeviceToDevice, s));
     return HMV_OK;
 }
 
@@ -2810,6 +2945,84 @@ int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const
     if (seg) (void)hipFree(seg);
     if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
     if (kind == 1 && rw.saturated()) { g_create_err = "hmv_op_attention_views: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
+    return HMV_OK;
+}
+
+/* Test hook: the attention-map kernels on their own (include/handmv.h).  Every range is checked against the rows the caller describes
+ * before anything is launched. */
+int hmv_op_attention_probs(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, int32_t T, int32_t Tq, int32_t koff,
+                           int32_t Tk, const int32_t *seg_host, float *probs, float *view_share, int32_t views, void *stream) {
+    auto bad = [](const char *why) { g_create_err = std::string("hmv_op_attention_probs: ") + why; return (int)HMV_ERR_ARG; };
+    if (!qkv || !probs || B <= 0 || kind < 0 || kind > 2) return bad("bad argument");
+    if (probe && kind != 2) return bad("only the 256-wide heads (kind 2) take probe queries");
+    if (koff < 0 || Tq < 0) return bad("koff and Tq must not be negative");
+    if (probe && Tq <= 0) return bad("probe queries need their count Tq");
+    int Tq_pad = Tq, Tk_pad = Tk;
+    if (seg_host) {
+        if (seg_host[0] != 0) return bad("seg[0] must be 0");
+        int Tmax = 0;
+        for (int b = 0; b < B; ++b) {
+            const long long Tb = (long long)seg_host[b + 1] - seg_host[b];
+            if (Tb < 1 || Tb > INT32_MAX / 2) return bad("every sample needs at least one row");
+            if (Tb < koff) return bad("a sample has fewer rows than koff: its keys would start outside it");
+            if (!probe && Tq > Tb) return bad("a sample has fewer rows than Tq: its queries would lie outside it");
+            Tmax = (int)Tb > Tmax ? (int)Tb : Tmax;
+        }
+        Tq_pad = Tq ? Tq : Tmax;
+        Tk_pad = Tmax - koff;
+    } else {
+        if (T <= 0 || Tq <= 0 || Tk <= 0) return bad("T, Tq and Tk must be positive");
+        if (!probe && Tq > T) return bad("Tq > T: the queries would lie outside the sample");
+        if ((long long)koff + Tk > T) return bad("koff + Tk > T: the keys would lie outside the sample");
+        if ((long long)B * T > INT32_MAX / 2) return bad("B x T is too large");
+    }
+    if (view_share) {
+        if (views <= 0 || koff % 21) return bad("a view share needs views > 0 and keys that start at a view (koff % 21 == 0)");
+        for (int b = 0; b < B; ++b) {
+            const int tk = seg_host ? seg_host[b + 1] - seg_host[b] - koff : Tk;
+            if (tk % 21 || (koff + tk) / 21 > views) return bad("a view share needs key ranges of whole views (21 rows each), at most `views` of them");
+        }
+    }
+    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t rows = seg_host ? (size_t)seg_host[B] : (size_t)B * T;
+    int32_t *seg = nullptr;
+    void *pairs = nullptr;
+    RangeWord rw;
+    hipError_t e = hipSuccess;
+    if (seg_host) {
+        e = hipMalloc(reinterpret_cast<void **>(&seg), (size_t)(B + 1) * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpy(seg, seg_host, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+    }
+    // queries: the sample's own rows (q_seg / q_bstride = T), or the probe's, shared by every sample
+    const AttnProbsRows pr = seg_host ? AttnProbsRows{seg, probe ? 0 : 1, koff, Tq, 0, 0, 0, 0, Tq_pad, Tk_pad}
+                                      : AttnProbsRows{nullptr, 0, koff, 0, T, Tq, Tk, probe ? 0 : T, Tq_pad, Tk_pad};
+    const size_t n = (size_t)B * 8 * Tq_pad * Tk_pad;
+    if (e == hipSuccess && seg_host && n) e = hipMemsetAsync(probs, 0, n * sizeof(float), s);
+    if (e == hipSuccess && n) {
+        if (kind == 1) {   // the kernel takes rows of (hi, lo) fp16 pairs: split the fp32 rows first (hmv_op_attention_x3)
+            e = rw.alloc();
+            if (e == hipSuccess) e = hipMalloc(&pairs, rows * 3072 * 4);
+            if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, rows, 3072, 2, s, rw.p);
+            if (e == hipSuccess) e = launch_attention_probs(1, pairs, 6144, static_cast<const _Float16 *>(pairs) + 1024, 6144, B, pr, probs, s);
+        } else if (kind == 0) {
+            e = launch_attention_probs(0, qkv, 3072, qkv + 1024, 3072, B, pr, probs, s);
+        } else if (probe) {
+            e = launch_attention_probs(2, probe, 2048, qkv, 4096, B, pr, probs, s);
+        } else {
+            e = launch_attention_probs(2, qkv, 6144, qkv + 2048, 6144, B, pr, probs, s);
+        }
+    }
+    if (e == hipSuccess && view_share) {
+        const size_t ns = (size_t)B * 8 * Tq_pad * views;
+        if (n) e = launch_attention_share(probs, B, pr, koff / 21, views, view_share, s);
+        else e = hipMemsetAsync(view_share, 0, ns * sizeof(float), s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (pairs) (void)hipFree(pairs);
+    if (seg) (void)hipFree(seg);
+    if (e != hipSuccess) { g_create_err = std::string("attention map launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
+    if (kind == 1 && rw.saturated()) { g_create_err = "hmv_op_attention_probs: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
     return HMV_OK;
 }
 

@@ -250,6 +250,24 @@ hipError_t launch_attention_d256_views(const float *q, int q_ld, int q_seg, cons
 hipError_t launch_add_pe_views(const float *x, int ldx, int rows, const int *fpos, int d, const float *pe, float *y, int ldy, hipStream_t s);
 // out[b * 21 + j][0, ld) = x[seg[b] + j][0, ld): the cross block's residual rows `_q`, contiguous (ld % 4 == 0)
 hipError_t launch_gather_query_rows(const float *x, int ld, const int *seg, int B, float *out, hipStream_t s);
+// ---- attention maps (attention_probs.hip; hmv_set_attention_capture): the softmax of a fusion block, which the kernels above never write.
+// Where a sample's rows are and how large its map is.  seg == nullptr, a uniform batch: queries = rows b * q_bstride + i of q, i < Tq;
+// keys = rows b * T + koff + j of k, j < Tk.  seg != nullptr, a ragged one: q_seg / koff / tq_fixed as AttSeg's (misc_kernels.hip),
+// T / Tq / Tk / q_bstride unused.  The map is probs [B][8][Tq_pad][Tk_pad], Tq_pad / Tk_pad >= every sample's Tq / Tk; a launch
+// writes p[b][h][i][j] for i < Tq_b, j < Tk_b and nothing else (a ragged caller zero-fills the map first).
+struct AttnProbsRows {
+    const int *seg;
+    int q_seg, koff, tq_fixed;
+    int T, Tq, Tk, q_bstride;
+    int Tq_pad, Tk_pad;
+};
+// kind 0: 128-wide heads, fp32 rows (q_ld / kv_ld in floats);  1: the same over rows of fp16 (hi, lo) pairs [hi | lo] (q, k address the hi
+// plane; q_ld = kv_ld in halfs, the lo plane half a row on);  2: 256-wide heads, fp32 rows.  q / k: row 0 at head 0.
+hipError_t launch_attention_probs(int kind, const void *q, int q_ld, const void *k, int kv_ld, int B, const AttnProbsRows &pr, float *probs,
+                                  hipStream_t s);
+// share [B][8][Tq_pad][views]: share[b][h][i][r] = sum_j probs[b][h][i][21 (r - rank0) + j], j < 21, in key order; 0 where the sample
+// has no such query or view.  rank0: the view rank of key 0
+hipError_t launch_attention_share(const float *probs, int B, const AttnProbsRows &pr, int rank0, int views, float *share, hipStream_t s);
 // ---- camera-subset sweep (hmv_forward_subsets): out[(m, j)] = rows[(src[m], j)] (+ pe[fpos[m] + j] where pe is not null) for the n_frames
 // packed frames of a chunk of virtual samples; `rows` were finalised without PE; pad columns zero; pairs as launch_tokens_finalize's
 hipError_t launch_tokens_expand_subsets(const float *rows, int ldt, int d, int n_frames, const int *src, const int *fpos, const float *pe,

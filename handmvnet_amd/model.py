@@ -54,6 +54,7 @@ class HandMvNet(torch.nn.Module):
         self._engines: Dict[tuple, ctypes.c_void_p] = {}
         self._dtype = 0   # 0 = fp32 (HMV_F32), 1 = fp16 conv stack (HMV_F16, BASELINE configs[4]), 2 = split fp16 pairs (HMV_F32X3)
         self._capture = False
+        self._att_mask = 0    # fusion blocks whose attention maps the forwards record (capture_attention)
         self._profiling = False
         self._graphs = None   # None: the engine's default (off unless HMV_GRAPHS=1)
         self._last_key: Optional[tuple] = None
@@ -180,6 +181,7 @@ class HandMvNet(torch.nn.Module):
                 _lib.check(lib.hmv_set_tensor(h, k.encode(), a.ctypes.data_as(ctypes.c_void_p), shape, a.ndim), h)
             _lib.check(lib.hmv_finalize_weights(h), h)
             lib.hmv_set_capture(h, int(self._capture))
+            _lib.check(lib.hmv_set_attention_capture(h, self._att_mask), h)
             lib.hmv_set_profiling(h, int(self._profiling))
             if self._graphs is not None:
                 lib.hmv_set_graphs(h, int(self._graphs))
@@ -583,6 +585,96 @@ class HandMvNet(torch.nn.Module):
         out = torch.empty(shape, device=f"cuda:{idx}", dtype=torch.float32)
         stream = torch.cuda.current_stream(out.device).cuda_stream
         _lib.check(_lib.load().hmv_read_stage(h, name.encode(), out.data_ptr(), out.numel(), ctypes.c_void_p(stream)), h)
+        return out
+
+    # ------------------------------------------------------------------ attention maps (the reference's return_attention=True)
+    @property
+    def fusion_blocks(self) -> int:
+        """Blocks of the fusion module: fusion_layers of CrossAttentionFusion, always 5 of the learnable-query one (fusion.py:39-45)."""
+        return 5 if self.cfg.learnable_query else self.cfg.fusion_layers
+
+    @property
+    def cross_block(self) -> int:
+        from .attention import cross_block_index
+        return cross_block_index(self.model_params)
+
+    def _block_mask(self, blocks) -> int:
+        if blocks is None:
+            return 0
+        if isinstance(blocks, str):
+            if blocks == "cross":
+                return 1 << self.cross_block
+            if blocks == "all":
+                return (1 << self.fusion_blocks) - 1
+            raise ValueError('blocks must be "cross", "all", an iterable of block indices or None')
+        mask = 0
+        for l in blocks:
+            l = int(l)
+            if not 0 <= l < self.fusion_blocks:
+                raise ValueError(f"block {l} is outside the {self.fusion_blocks} fusion blocks of this model")
+            mask |= 1 << l
+        return mask
+
+    def capture_attention(self, blocks="cross"):
+        """Selects the fusion blocks whose attention maps every following forward() / forward_views() / forward_frames() records
+        (hmv_set_attention_capture): "cross" (the block whose 21 outputs draw on the views), "all", an iterable of block indices, or
+        None = off (the default: nothing the engine enqueues changes).  While blocks are selected, forwards stay on the eager path
+        and forward_subsets() ignores the selection."""
+        self._att_mask = self._block_mask(blocks)
+        for h in self._engines.values():
+            _lib.check(_lib.load().hmv_set_attention_capture(h, self._att_mask), h)
+
+    def read_attention(self, block: int):
+        """(probs [b, 8, Tq, Tk], view_share_by_rank [b, 8, Tq, R] or None) of fusion block `block` as the last forward left them:
+        probs[b, h, i, j] is the reference's `attn`; view_share_by_rank[..., r] its sum over the 21 keys of the view of rank r among the
+        sample's present views (None for a block behind the cross block, whose keys are no views).  After forward_views() the shapes
+        are the batch's maxima and a shorter sample's rows and columns beyond its own are zeros.  In cross_attn's cross block the view
+        of rank 0 supplies the queries: its column is exactly 0."""
+        hh, ww, idx, _, dt = self._last_key
+        h = self._engines[(hh, ww, idx, dt)]
+        lib = _lib.load()
+        B, Tq, Tk, views = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(lib.hmv_attention_shape(h, int(block), ctypes.byref(B), ctypes.byref(Tq), ctypes.byref(Tk), ctypes.byref(views)), h)
+        dev = torch.device(f"cuda:{idx}")
+        probs = torch.empty(B.value, 8, Tq.value, Tk.value, device=dev, dtype=torch.float32)
+        share = torch.empty(B.value, 8, Tq.value, views.value, device=dev, dtype=torch.float32) if views.value else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(lib.hmv_read_attention(h, int(block), probs.data_ptr() if probs.numel() else None, probs.numel(),
+                                              share.data_ptr() if share is not None else None, share.numel() if share is not None else 0,
+                                              ctypes.c_void_p(stream)), h)
+        return probs, share
+
+    def forward_attention(self, x, bbox=None, cam_params=None, view_mask=None, blocks="cross"):
+        """forward() (view_mask None) or forward_views() with the attention maps of `blocks` (as capture_attention takes them):
+        the forward's dict plus
+          "attention"       {block: [b, 8, Tq, Tk]}, the reference's `attn` of that block
+          "view_share"      {block: [b, 8, Tq, V]} by CAMERA SLOT for the blocks up to the cross block: ragged samples are scattered by
+                            their mask, absent cameras are 0
+          "view_attention"  [b, 21, V]: the cross block's share averaged over the heads (present when the cross block is selected)
+        The selection made with capture_attention() is restored afterwards."""
+        from .attention import share_to_cameras
+        mask = self._block_mask(blocks)
+        if not mask:
+            raise ValueError("forward_attention needs at least one block")
+        saved = self._att_mask
+        self.capture_attention([l for l in range(self.fusion_blocks) if mask >> l & 1])
+        try:
+            out = self.forward(x, bbox, cam_params) if view_mask is None else self.forward_views(x, view_mask, bbox, cam_params)
+            out["attention"], out["view_share"] = {}, {}
+            for l in range(self.fusion_blocks):
+                if not mask >> l & 1:
+                    continue
+                probs, share = self.read_attention(l)
+                out["attention"][l] = probs
+                if share is not None:
+                    out["view_share"][l] = share_to_cameras(share, view_mask, self.num_views)
+            if self.cross_block in out["view_share"]:
+                out["view_attention"] = out["view_share"][self.cross_block].mean(dim=1)
+        finally:
+            self._att_mask = saved
+            for h in self._engines.values():
+                _lib.check(_lib.load().hmv_set_attention_capture(h, saved), h)
         return out
 
     def launch_count(self) -> int:

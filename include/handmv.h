@@ -206,6 +206,35 @@ void hmv_destroy(hmv_handle h);
 int hmv_set_capture(hmv_handle h, int32_t enable);
 int hmv_read_stage(hmv_handle h, const char *stage, float *dst_device, size_t capacity_floats, void *stream);
 
+/* Attention maps of the fusion blocks: what the reference returns from MultiHeadAttention.forward(x, return_attention=True) and
+ * MultiHeadAttentionLearnableQuery.forward(x, return_attention=True) (layers.py:202-237, 267-301) -- attn[b][h][i][j], the softmax with which
+ * query i of head h draws on key j.  The forward's attention kernels never write it; a selected block gets one more launch directly behind
+ * its attention launch, which recomputes the logits from the block's own q and k rows (the forward's operand order and scale, fp32 matrix
+ * cores) and writes the probabilities.  In the fp16-kernel modes (HMV_F16, HMV_F32X3) the 128-wide heads' q and k exist only as fp16 (hi, lo)
+ * pairs: the map is then fp32 arithmetic on float(hi) + float(lo) of those pairs -- the forward's own operands, not the registers of its
+ * fp16-matrix-core attention.
+ *   block_mask   bit l selects fusion block l (cross_attn: fusion_layers blocks, the cross block is (fusion_layers - 1) / 2; learnable
+ *                query: 5 blocks, the probe block is 2).  0, the default, turns capture off: nothing a forward enqueues changes.  A bit at or
+ *                above the block count is HMV_ERR_ARG.  A non-zero mask keeps forwards on the eager path (as stage capture does); the buffers are
+ *                the handle's own, outside the workspace, and grow with hmv_reserve / the next forward.
+ *   forwards     hmv_forward, hmv_forward_frames, hmv_forward_views, hmv_forward_frames_views (and their _track forms) honour the mask;
+ *                hmv_forward_subsets ignores it and leaves no map.
+ *   shape        of the last forward's map: probs [B][8][Tq][Tk] dense fp32; after a ragged forward Tq / Tk / views are the batch's maxima,
+ *                a shorter sample's rows and columns beyond its own are zeros, and a sample with one view has no keys in cross_attn's cross
+ *                block (its rows are zeros).  views: the view columns of the share, 0 for a block behind the cross block (its 21 fused keys
+ *                are no views).
+ *   view share   share[b][h][i][r] = the sum, in key order in fp32, of p over the 21 keys of the view of RANK r among the sample's present
+ *                views; [B][8][Tq][views].  In cross_attn's cross block the keys start at the second view -- the view of rank 0 supplies the
+ *                queries -- so column 0 is exactly 0 there.
+ * hmv_read_attention copies device-to-device on `stream`; either destination may be NULL.  HMV_ERR_STATE: the block was not selected before
+ * the last forward, or the last call was a sweep.  HMV_ERR_ARG: a capacity (in floats) smaller than the data -- nothing is truncated --, or
+ * view_share for a block without one.  A single-view model's cross block has Tk = 0: the call succeeds, copies no probabilities and returns
+ * a share of zeros. */
+int hmv_set_attention_capture(hmv_handle h, uint32_t block_mask);
+int hmv_attention_shape(hmv_handle h, int32_t block, int32_t *B, int32_t *Tq, int32_t *Tk, int32_t *views);
+int hmv_read_attention(hmv_handle h, int32_t block, float *probs, size_t probs_capacity, float *view_share, size_t share_capacity,
+                       void *stream);
+
 /* Per-launch timing with hipEvents on the forward's stream (0 = off, 1 = on).  When on,
  * hmv_forward records an event pair around every kernel launch of the conv/GEMM kernel
  * family; records accumulate over successive forwards (calling hmv_set_profiling again
@@ -345,6 +374,22 @@ int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_
  * Synchronises the stream. */
 int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, const int32_t *seg, int32_t cross,
                            float *out, void *stream);
+
+/* The attention-map kernels on their own (what a forward launches under hmv_set_attention_capture; op-level tests).
+ *   kind 0  128-wide heads over fp32 rows;  kind 1  the same over fp16 (hi, lo) pairs (the fp32 rows are split first);  qkv device
+ *           [rows][3 * 1024] = [q | k | v] per row
+ *   kind 2  256-wide heads: probe == NULL: qkv device [rows][3 * 2048];  probe != NULL: qkv holds [k | v] rows [rows][2 * 2048] and the
+ *           queries are the Tq rows of `probe` [Tq][2048] for every sample
+ * seg == NULL, a uniform batch of B samples of T rows: the first Tq rows of a sample (or the probe's) query its rows [koff, koff + Tk);
+ * probs device [B][8][Tq][Tk].  seg != NULL, a HOST table of B + 1 first rows (seg[0] = 0; T and Tk are not read): Tq = 0: every row of a
+ * sample queries, Tq > 0: its first Tq rows (or the probe's) do; the keys are its rows from koff on; probs device
+ * [B][8][Tq or the longest sample][the longest sample - koff], zero-filled by the call, exact zeros beyond a sample's own extent.
+ * view_share (or NULL): device [B][8][that Tq][views], the share per view as hmv_read_attention describes it, key 0 belonging to the view
+ * of rank koff / 21; needs koff % 21 == 0 and key ranges of whole views.
+ * HMV_ERR_ARG before any launch, with hmv_last_error(NULL) naming it, for a range that would read outside the rows described (Tq > T,
+ * koff + Tk > T, a sample shorter than koff or Tq), non-positive sizes and a probe with another kind.  Synchronises the stream. */
+int hmv_op_attention_probs(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, int32_t T, int32_t Tq, int32_t koff,
+                           int32_t Tk, const int32_t *seg, float *probs, float *view_share, int32_t views, void *stream);
 
 /* Diagnostic micro-benchmark: average milliseconds of `iters` launches of one NHWC conv shape on
  * pseudo-random data.  tile: -1 = the engine's own choice, else 0..7 = 128x32, 128x64, 128x128, 256x128,

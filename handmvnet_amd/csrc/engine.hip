@@ -240,24 +240,6 @@ struct hmv_engine {
         for (AttMap &m : att) m.valid = false;
     }
 
-    // set only for the duration of hmv_forward_frames / hmv_forward_frames_views: raw camera frames instead of prepared NCHW input
-    struct FrameSrc {
-        const uint8_t *frames = nullptr;
-        const int *boxes = nullptr;
-        const int *index = nullptr;   // hmv_forward_frames_views: packed frame n is frames / boxes [index[n]] of the caller's n_src
-        int n_src = 0;
-        int fh = 0, fw = 0;
-        float mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
-    } fsrc;
-    // set only for the duration of hmv_forward_frames_track / hmv_forward_frames_views_track: behind the forward, on its stream, the windows
-    // (fsrc.boxes) and bbox are moved in place to the box around the joints just found (track.hip)
-    struct TrackTail {
-        bool on = false;
-        int margin = 0, square = 1;
-        float *joints_img = nullptr;
-        int *status = nullptr;
-    } track;
-
     // hipGraph replay of repeated forwards (same batch and the same caller buffers): the ~100 launches of a forward
     // become one graph launch.  Opt-in: measured on MI355X it does not change throughput (eager enqueue already runs
     // ahead of the GPU); what it saves is host time per forward.
@@ -1233,6 +1215,30 @@ struct ConvCall {
 // positions fpos[n] .. fpos[n] + 20 of its sample (device, N entries); Tmax = the longest sample's token count.  A planning run has no tables.
 struct ViewSet { int N; const int32_t *seg, *fpos; int Tmax; };
 
+// Raw camera frames instead of a prepared NCHW input (hmv_forward_frames*); frames == nullptr: the call brings x
+struct FrameSrc {
+    const uint8_t *frames = nullptr;
+    const int *boxes = nullptr;
+    const int *index = nullptr;   // hmv_forward_frames_views: packed frame n is frames / boxes [index[n]] of the caller's n_src
+    int n_src = 0;
+    int fh = 0, fw = 0;
+    float mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
+};
+// The tracking tail (hmv_forward_frames_track / hmv_forward_frames_views_track): behind the forward, on its stream, the windows
+// (src.boxes) and bbox are moved in place to the box around the joints just found (track.hip)
+struct TrackTail { bool on = false; int margin = 0, square = 1; float *joints_img = nullptr; int *status = nullptr; };
+// One forward call, whole: built by the public entry from its arguments and passed down by const reference; the handle keeps nothing of
+// it.  A planning run is the call with nothing but its batch
+struct ForwardCall {
+    int batch = 0;
+    const float *x = nullptr;   // prepared NCHW input, or ...
+    FrameSrc src;               // ... raw frames
+    const float *bbox = nullptr, *intrinsic = nullptr;
+    float *joints_crop_img = nullptr, *joints_cam = nullptr, *heatmap = nullptr;
+    TrackTail track;
+    hipStream_t stream = nullptr;
+};
+
 #define LAUNCH(expr) launch(#expr, [&] { return (expr); })   // (inside Runner: see launch())
 struct Runner {
     hmv_engine *h;
@@ -1242,6 +1248,7 @@ struct Runner {
     Arena &A;
     const ViewSet *vs = nullptr;   // not null: a ragged forward (hmv_forward_views); stages are not captured then
     bool sweep = false;            // a camera-subset sweep (hmv_forward_subsets): the token rows leave tokens_stage without PE and pair copy; no stages
+    const FrameSrc *src = nullptr;   // the call's frame source (null in the op-level entries): the backbones prepare their input from it
 
     float *alloc(size_t n) {
         float *ptr = A.alloc(n);
@@ -1659,7 +1666,7 @@ struct Runner {
         const HrNet &hr = h->hr;
         const int H = h->cfg.height, W = h->cfg.width;
         Map in4 = act(N, H, W, 3, h16 ? 8 : 4);   // 4 fp32 / 8 fp16 / [hi8 | lo8] per pixel
-        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, split ? 2 : (h16 ? 1 : 0), in4.p, s, /*s2d=*/false, h->fsrc.index, h->fsrc.n_src));
+        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, split ? 2 : (h16 ? 1 : 0), in4.p, s, /*s2d=*/false, src->index, src->n_src));
         else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4.p, N, H, W, s, h->sat));
         else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4.p, N, H, W, s));
         else LAUNCH(launch_nchw_to_nhwc4(x, in4.p, N, H, W, s));
@@ -1780,7 +1787,7 @@ struct Runner {
         // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
         const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
         Map in4 = act(N, Hs, Ws, 12, h16 ? 16 : 12);
-        if (h->fsrc.frames) LAUNCH(launch_frames_to_input(h->fsrc.frames, h->fsrc.boxes, N, h->fsrc.fh, h->fsrc.fw, H, W, h->fsrc.mean, h->fsrc.std, smode, in4.p, s, /*s2d=*/true, h->fsrc.index, h->fsrc.n_src));
+        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, smode, in4.p, s, /*s2d=*/true, src->index, src->n_src));
         else LAUNCH(launch_nchw_to_s2d(x, in4.p, N, H, W, smode, s, h->sat));
         const int H1 = conv_out(H, 7, 2, 3), W1 = conv_out(W, 7, 2, 3);   // == Hs, Ws
         const int hp = conv_out(H1, 3, 2, 1), wp = conv_out(W1, 3, 2, 1);
@@ -2096,20 +2103,19 @@ int ensure_aux_stream(hmv_engine *h) {
 
 // HandMvNet.forward (handmvnet.py:158-266), stage by stage; a planning run (dry) issues the same alloc / release sequence and launches nothing
 // vs (ragged view sets, hmv_forward_views): the backbone and the token stage run on vs->N frames, the fusion over each sample's own rows
-int run_forward(hmv_engine *h, int B, const float *x, const float *bbox, const float *intr, float *crop_img, float *joints_cam,
-                float *heatmap, hipStream_t s, bool dry, Arena &A, const ViewSet *vs = nullptr) {
-    Runner R{h, s, dry, HMV_OK, A, vs};
+int run_forward(hmv_engine *h, const ForwardCall &fc, bool dry, Arena &A, const ViewSet *vs = nullptr) {
+    Runner R{h, fc.stream, dry, HMV_OK, A, vs, false, &fc.src};
     const hmv_config &c = h->cfg;
     if (!dry)
         if (const int rc = ensure_aux_stream(h)) return rc;
-    const int N = vs ? vs->N : B * c.num_views;
-    const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
+    const int B = fc.batch, N = vs ? vs->N : B * c.num_views;
+    const Features f = h->hrnet ? R.hrnet_backbone(N, fc.x) : R.resnet_backbone(N, fc.x);
     float *Xpairs = nullptr;
-    float *X = R.tokens_stage(f, bbox, intr, crop_img, heatmap, Xpairs);
+    float *X = R.tokens_stage(f, fc.bbox, fc.intrinsic, fc.joints_crop_img, fc.heatmap, Xpairs);
     int Tcur = vs ? vs->Tmax : c.num_views * NJ;
     X = h->lq ? R.fusion_learnable_query(B, X, Tcur) : R.fusion_cross_attn(B, X, Xpairs, Tcur);
-    if (h->capture && !dry && !vs && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, s); });
-    R.decoder(B, X, joints_cam);
+    if (h->capture && !dry && !vs && h->cap_fused) R.launch("copy_rows", [&] { return launch_copy_rows(X, h->ldt, h->cap_fused, h->d, B * Tcur, h->d, fc.stream); });
+    R.decoder(B, X, fc.joints_cam);
     return R.rc;
 }
 
@@ -2123,10 +2129,11 @@ struct SubsetChunk { int q0, nv, n, vmax; size_t tab; };
 // joints_cam[q0 .. q0 + nv).  tab: the call's device table (null in a planning run).  Per-sample arithmetic never depends on a size, so a
 // subset's bits do not depend on the chunks.  While profiling, one bracketing record around the per-frame stage ("subsets_frames") and one
 // around every pass ("subsets_tail") besides the launches' own.
-int run_forward_subsets(hmv_engine *h, int B, const std::vector<SubsetChunk> &chunks, const int32_t *tab, const float *x, const float *bbox,
-                        const float *intr, float *crop_img, float *joints_cam, float *heatmap, hipStream_t s, bool dry, Arena &A) {
-    Runner R{h, s, dry, HMV_OK, A, nullptr, true};
+int run_forward_subsets(hmv_engine *h, const ForwardCall &fc, const std::vector<SubsetChunk> &chunks, const int32_t *tab, bool dry, Arena &A) {
+    Runner R{h, fc.stream, dry, HMV_OK, A, nullptr, true, &fc.src};
     const hmv_config &c = h->cfg;
+    const hipStream_t s = fc.stream;
+    float *const joints_cam = fc.joints_cam;
     if (!dry)
         if (const int rc = ensure_aux_stream(h)) return rc;
     auto bracket_begin = [&](const char *label) {   // (an index: nested records may move the list)
@@ -2139,11 +2146,11 @@ int run_forward_subsets(hmv_engine *h, int B, const std::vector<SubsetChunk> &ch
         h->prof[i].flops = h->prof[i].bytes = 0;
         R.prof_end(&h->prof[i], name);
     };
-    const int N = B * c.num_views, ldt = h->ldt;
+    const int N = fc.batch * c.num_views, ldt = h->ldt;
     size_t br = bracket_begin("frames");
-    const Features f = h->hrnet ? R.hrnet_backbone(N, x) : R.resnet_backbone(N, x);
+    const Features f = h->hrnet ? R.hrnet_backbone(N, fc.x) : R.resnet_backbone(N, fc.x);
     float *no_pairs = nullptr;
-    float *rows = R.tokens_stage(f, bbox, intr, crop_img, heatmap, no_pairs);
+    float *rows = R.tokens_stage(f, fc.bbox, fc.intrinsic, fc.joints_crop_img, fc.heatmap, no_pairs);
     bracket_end(br, "subsets_frames");
     const bool want_pairs = !h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane;   // (as tokens_stage decides for a forward)
     const float *pe = (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe;
@@ -2219,19 +2226,296 @@ int ensure_attention(hmv_engine *h, int B) {
     return HMV_OK;
 }
 
+// ------------------------------------------------------------------ what the forward entries share
+int check_handle(hmv_handle h) {
+    if (!h) return HMV_ERR_ARG;
+    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    return HMV_OK;
+}
+
+int check_crop_pe(hmv_handle h, const float *bbox, const float *intrinsic) {
+    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
+        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
+    return HMV_OK;
+}
+
+// a call from raw frames: frames / mean / std / frame size (batch and the outputs share the first text)
+int check_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, const int32_t *crop_boxes,
+                 const float *mean, const float *std, const float *joints_crop_img, const float *joints_cam) {
+    if (batch <= 0 || !frames || !crop_boxes || !mean || !std || !joints_crop_img || !joints_cam)
+        return h->fail(HMV_ERR_ARG, "null or empty input/output");
+    if (frame_h <= 0 || frame_w <= 0) return h->fail(HMV_ERR_ARG, "frame size must be positive");
+    for (int c = 0; c < 3; ++c)
+        if (!(std[c] > 0.f)) return h->fail(HMV_ERR_ARG, "std must be positive");
+    return HMV_OK;
+}
+
+int check_views(hmv_handle h, const char *who, int32_t batch, const int32_t *view_counts, const float *bbox, const float *intrinsic) {
+    if (batch <= 0) return h->fail(HMV_ERR_ARG, "%s: batch must be positive (got %d)", who, (int)batch);
+    if (!view_counts) return h->fail(HMV_ERR_ARG, "%s: view_counts is null (one host entry per sample)", who);
+    const int V = h->cfg.num_views;
+    for (int b = 0; b < batch; ++b) {
+        const int v = view_counts[b];
+        if (v < 1 || v > V)
+            return h->fail(HMV_ERR_ARG, "%s: view_counts[%d] = %d, every sample needs between 1 and num_views = %d present views", who, b, v, V);
+    }
+    return check_crop_pe(h, bbox, intrinsic);
+}
+
+FrameSrc frame_src(const uint8_t *frames, int fh, int fw, const int *boxes, const int *index, int n_src, const float *mean, const float *std) {
+    FrameSrc f{frames, boxes, index, n_src, fh, fw};
+    for (int c = 0; c < 3; ++c) { f.mean[c] = mean[c]; f.std[c] = std[c]; }
+    return f;
+}
+
+// The next slot of the ring of pinned host tables, free to be rewritten (the upload that last read it has run) and with room for tab_n entries
+int views_slot(hmv_handle h, size_t tab_n, hmv_engine::ViewsSlot *&out) {
+    hmv_engine::ViewsSlot &slot = h->views_host[h->views_next++ % 4];
+    if (slot.done) HIPCHK(h, hipEventSynchronize(slot.done));
+    else HIPCHK(h, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (tab_n > slot.cap) {
+        if (slot.host) HIPCHK(h, hipHostFree(slot.host));
+        slot.host = nullptr;
+        slot.cap = 0;
+        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
+        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&slot.host), cap * sizeof(int32_t), hipHostMallocDefault));
+        slot.cap = cap;
+    }
+    out = &slot;
+    return HMV_OK;
+}
+
+// A call whose own plan needs more than the reserved workspace (checked before anything is launched): the workspace grows
+int grow_workspace(hmv_handle h, size_t need) {
+    if (need <= h->arena_bytes) return HMV_OK;
+    HIPCHK(h, hipDeviceSynchronize());
+    h->drop_graphs();   // captured launches point into the old workspace
+    if (h->arena) HIPCHK(h, hipFree(h->arena));
+    h->arena = nullptr;
+    h->arena_bytes = 0;
+    const int served = h->reserved_batch;   // the larger workspace still serves as many uniform samples
+    h->reserved_batch = 0;
+    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->arena), need));
+    h->arena_bytes = need;
+    h->reserved_batch = served;
+    return HMV_OK;
+}
+
+// The tables of a ragged call or a sweep: tab_n entries in a slot of the pinned ring
+struct ViewsUpload { hmv_engine::ViewsSlot *slot; size_t tab_n; };
+
+// ... to the device table, on the caller's stream
+int upload_views(hmv_handle h, const ViewsUpload &up, hipStream_t s) {
+    if (up.tab_n > h->views_cap) {   // (hipFree waits for the launches that still read the old table)
+        if (h->views_dev) HIPCHK(h, hipFree(h->views_dev));
+        h->views_dev = nullptr;
+        h->views_cap = 0;
+        const size_t cap = std::max<size_t>(up.tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->views_dev), cap * sizeof(int32_t)));
+        h->views_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->views_dev, up.slot->host, up.tab_n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipEventRecord(up.slot->done, s));
+    return HMV_OK;
+}
+
+// The workspace a call of `batch` samples takes: run(call, dry, arena) plans the call that carries nothing but its batch on an arena at a
+// fake non-null base (offsets only).  A planning run records nothing, so profiling is off meanwhile
+template <class Run> size_t plan_bytes(hmv_engine *h, int batch, Run &&run) {
+    Arena dry;
+    dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));
+    const bool saved = h->profiling;
+    h->profiling = false;
+    run(ForwardCall{batch}, /*dry=*/true, dry);
+    h->profiling = saved;
+    return dry.high;
+}
+
+// "Plan this call, grow the workspace if its own plan needs it, run it, check the high-water mark" in two halves; run(call, dry, arena).
+// The front, for a ragged call or a sweep: the reservation for `batch` uniform samples asks for more of every buffer, but the planner is
+// first-fit and these calls hold a few more small buffers, so the call's own plan is checked BEFORE anything is launched; then the tables
+// go up, the call's first launch.  A uniform forward has no front: it relies on hmv_reserve, so it may run under stream capture
+template <class Run> int plan_and_upload(hmv_engine *h, const ForwardCall &fc, const ViewsUpload &up, Run &&run) {
+    if (const int rc = grow_workspace(h, plan_bytes(h, fc.batch, run))) return rc;
+    if (const int rc = upload_views(h, up, fc.stream)) return rc;
+    h->last_ragged = true;   // no stages are captured (hmv_read_stage)
+    return HMV_OK;
+}
+
+// The back, for every path: the real run on the workspace, its launches counted from `first` (1 behind an upload, else 0)
+template <class Run> int run_checked(hmv_engine *h, const ForwardCall &fc, int first, Run &&run) {
+    h->plan.reset(h->arena);
+    h->launches = first;
+    const int rc = run(fc, /*dry=*/false, h->plan);
+    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
+    return rc;
+}
+
+// The tracking tail, on the call's stream: n_frames rows of joints move the windows of n_slots slots; index names each row's slot (null:
+// row n is slot n)
+int launch_track_tail(hmv_engine *h, const ForwardCall &fc, int n_frames, int n_slots, const int *index) {
+    int *boxes = const_cast<int *>(fc.src.boxes);
+    const TrackParams tp{n_frames, n_slots, fc.joints_crop_img, boxes, nullptr, index, h->cfg.image_size, fc.track.margin, fc.track.square,
+                         boxes, const_cast<float *>(fc.bbox), fc.track.joints_img, fc.track.status};
+    HIPCHK(h, launch_next_crop_boxes(tp, fc.stream));
+    ++h->launches;
+    return HMV_OK;
+}
+
+int forward_eager(hmv_engine *h, const ForwardCall &fc) {
+    const int rc = run_checked(h, fc, 0, [h](const ForwardCall &c, bool dry, Arena &A) { return run_forward(h, c, dry, A); });
+    if (rc != HMV_OK || !fc.track.on) return rc;
+    const int n = fc.batch * h->cfg.num_views;
+    return launch_track_tail(h, fc, n, n, nullptr);   // (under capture this launch becomes the graph's last node)
+}
+
+// The uniform forward behind hmv_forward and hmv_forward_frames(_track): the only path that may be captured and replayed
+int forward_uniform(hmv_engine *h, const ForwardCall &fc) {
+    if (const int rc = check_crop_pe(h, fc.bbox, fc.intrinsic)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int batch = fc.batch;
+    if (batch > h->reserved_batch || (h->capture && h->cap_batch < batch) || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask)))
+        if (const int rc = hmv_reserve(h, batch)) return rc;
+    h->last_ragged = false;
+    h->forget_attention();
+    // stage capture and attention capture copy into side buffers and profiling brackets launches with events: all stay eager
+    if (!h->graphs || h->capture || h->att_mask || h->profiling) return forward_eager(h, fc);
+
+    hmv_engine::GraphKey key{};
+    key[0] = (uintptr_t)batch; key[1] = (uintptr_t)fc.x; key[2] = (uintptr_t)fc.bbox; key[3] = (uintptr_t)fc.intrinsic;
+    key[4] = (uintptr_t)fc.joints_crop_img; key[5] = (uintptr_t)fc.joints_cam; key[6] = (uintptr_t)fc.heatmap;
+    key[7] = (uintptr_t)fc.src.frames; key[8] = (uintptr_t)fc.src.boxes;
+    key[9] = ((uintptr_t)(unsigned)fc.src.fh << 32) | (uintptr_t)(unsigned)fc.src.fw;
+    if (fc.src.frames) {
+        uint32_t bits[6];
+        memcpy(bits, fc.src.mean, 12);
+        memcpy(bits + 3, fc.src.std, 12);
+        key[10] = ((uintptr_t)bits[0] << 32) ^ ((uintptr_t)bits[1] << 16) ^ (uintptr_t)bits[2];
+        key[11] = ((uintptr_t)bits[3] << 32) ^ ((uintptr_t)bits[4] << 16) ^ (uintptr_t)bits[5];
+    }
+    if (fc.track.on) {   // the tracking tail is part of the captured work: its buffers and parameters are part of the key
+        key[12] = (uintptr_t)fc.track.joints_img; key[13] = (uintptr_t)fc.track.status;
+        key[14] = (uintptr_t(1) << 63) | ((uintptr_t)(fc.track.square != 0) << 32) | (uintptr_t)(unsigned)fc.track.margin;
+    }
+    const hipStream_t s = fc.stream;
+    for (auto &e : h->gcache)
+        if (e.key == key) {
+            e.stamp = ++h->gclock;
+            ++h->greplays;
+            HIPCHK(h, hipGraphLaunch(e.exec, s));
+            return HMV_OK;
+        }
+    auto seen = std::find(h->gseen.begin(), h->gseen.end(), key);
+    if (seen == h->gseen.end()) {   // first sighting: run eagerly (also configures kernels, zero page, ...)
+        if (h->gseen.size() >= 16) h->gseen.erase(h->gseen.begin());
+        h->gseen.push_back(key);
+        return forward_eager(h, fc);
+    }
+    // second use of the same buffers: capture on the engine's own stream, then launch the graph on the caller's
+    h->gseen.erase(seen);
+    if (!h->gstream) HIPCHK(h, hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
+    ForwardCall captured = fc;
+    captured.stream = h->gstream;
+    HIPCHK(h, hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal));
+    const int rc = forward_eager(h, captured);
+    hipGraph_t graph = nullptr;
+    const hipError_t ce = hipStreamEndCapture(h->gstream, &graph);
+    hipGraphExec_t exec = nullptr;
+    if (rc != HMV_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();
+        h->graphs = false;   // capture is not available here: stay eager for the life of the handle
+        if (rc != HMV_OK) return rc;
+        return forward_eager(h, fc);
+    }
+    (void)hipGraphDestroy(graph);
+    if (h->gcache.size() >= 8) {   // least recently replayed entry makes room
+        size_t lru = 0;
+        for (size_t i = 1; i < h->gcache.size(); ++i)
+            if (h->gcache[i].stamp < h->gcache[lru].stamp) lru = i;
+        (void)hipGraphExecDestroy(h->gcache[lru].exec);
+        h->gcache.erase(h->gcache.begin() + (long)lru);
+    }
+    h->gcache.push_back({key, exec, ++h->gclock});
+    HIPCHK(h, hipGraphLaunch(exec, s));
+    return HMV_OK;
+}
+
+// The ragged forward behind hmv_forward_views and hmv_forward_frames_views(_track); the arguments have been checked.  Always eager: the
+// tables differ from call to call, so a ragged call never enters the graph replay cache
+int forward_ragged(hmv_engine *h, const ForwardCall &fc, const int32_t *view_counts) {
+    const int batch = fc.batch;
+    size_t N = 0;
+    int vmax = 0;
+    for (int b = 0; b < batch; ++b) {
+        N += (size_t)view_counts[b];
+        vmax = view_counts[b] > vmax ? view_counts[b] : vmax;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (batch > h->reserved_batch || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask)))
+        if (const int rc = hmv_reserve(h, batch)) return rc;
+    h->forget_attention();
+    // the tables: [seg: B + 1 | fpos: N]
+    ViewsUpload up{nullptr, (size_t)batch + 1 + N};
+    if (const int rc = views_slot(h, up.tab_n, up.slot)) return rc;
+    int32_t *seg = up.slot->host, *fpos = seg + batch + 1;
+    seg[0] = 0;
+    for (int b = 0, n = 0; b < batch; ++b) {
+        seg[b + 1] = seg[b] + NJ * view_counts[b];
+        for (int r = 0; r < view_counts[b]; ++r) fpos[n++] = NJ * r;
+    }
+    auto run = [&](const ForwardCall &c, bool dry, Arena &A) {   // (a planning run has no tables)
+        const ViewSet vs{(int)N, dry ? nullptr : h->views_dev, dry ? nullptr : h->views_dev + batch + 1, NJ * vmax};
+        return run_forward(h, c, dry, A, &vs);
+    };
+    if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
+    const int rc = run_checked(h, fc, 1, run);
+    if (rc != HMV_OK || !fc.track.on) return rc;
+    // a full-layout slot is present iff a packed frame names it: every slot starts as absent (status 1, zero joints, its window
+    // untouched) and each packed row then moves the window of the slot it came from
+    const int n_slots = fc.src.index ? fc.src.n_src : (int)N;
+    if (fc.track.joints_img) {
+        HIPCHK(h, hipMemsetAsync(fc.track.joints_img, 0, (size_t)n_slots * NJ * 2 * sizeof(float), fc.stream));
+        ++h->launches;
+    }
+    if (fc.track.status) {
+        HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(fc.track.status), 1, (size_t)n_slots, fc.stream));
+        ++h->launches;
+    }
+    return launch_track_tail(h, fc, (int)N, n_slots, fc.src.index);
+}
+
+// hmv_forward_frames with or without a tracking tail
+int forward_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, const int32_t *crop_boxes,
+                   const float *mean, const float *std, const float *bbox, const float *intrinsic, float *joints_crop_img, float *joints_cam,
+                   float *heatmap, const TrackTail &track, void *stream) {
+    if (const int rc = check_handle(h)) return rc;
+    if (const int rc = check_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, joints_crop_img, joints_cam)) return rc;
+    const ForwardCall fc{batch, nullptr, frame_src(frames, frame_h, frame_w, crop_boxes, nullptr, 0, mean, std), bbox, intrinsic,
+                         joints_crop_img, joints_cam, heatmap, track, static_cast<hipStream_t>(stream)};
+    return forward_uniform(h, fc);
+}
+
+// hmv_forward_frames_views with or without a tracking tail: the indexed frame preparation in front of the ragged forward
+int forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
+                         const int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std, const float *bbox,
+                         const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, const TrackTail &track,
+                         void *stream) {
+    if (const int rc = check_handle(h)) return rc;
+    if (const int rc = check_views(h, "hmv_forward_frames_views", batch, view_counts, bbox, intrinsic)) return rc;
+    if (const int rc = check_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, joints_crop_img, joints_cam)) return rc;
+    const ForwardCall fc{batch, nullptr, frame_src(frames, frame_h, frame_w, crop_boxes, frame_index, batch * h->cfg.num_views, mean, std),
+                         bbox, intrinsic, joints_crop_img, joints_cam, heatmap, track, static_cast<hipStream_t>(stream)};
+    return forward_ragged(h, fc, view_counts);
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t hmv_workspace_bytes(hmv_handle h, int32_t batch) {
     if (!h || batch <= 0) return 0;
-    Arena dry;
-    dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));  // fake non-null base: offsets only
-    const bool saved = h->profiling;
-    h->profiling = false;
-    run_forward(h, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry);
-    h->profiling = saved;
-    return dry.high;
+    return plan_bytes(h, batch, [h](const ForwardCall &c, bool dry, Arena &A) { return run_forward(h, c, dry, A); });
 }
 
 int hmv_reserve(hmv_handle h, int32_t batch) {
@@ -2253,96 +2537,6 @@ int hmv_reserve(hmv_handle h, int32_t batch) {
     return ensure_attention(h, batch);
 }
 
-static int forward_eager(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic,
-                         float *joints_crop_img, float *joints_cam, float *heatmap, hipStream_t stream) {
-    h->plan.reset(h->arena);
-    h->launches = 0;
-    const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream, false, h->plan);
-    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
-    if (rc == HMV_OK && h->track.on) {   // (under capture this launch becomes the graph's last node)
-        const int n = batch * h->cfg.num_views;
-        int *boxes = const_cast<int *>(h->fsrc.boxes);
-        const TrackParams tp{n, n, joints_crop_img, boxes, nullptr, nullptr, h->cfg.image_size, h->track.margin, h->track.square,
-                             boxes, const_cast<float *>(bbox), h->track.joints_img, h->track.status};
-        HIPCHK(h, launch_next_crop_boxes(tp, stream));
-        ++h->launches;
-    }
-    return rc;
-}
-
-static int forward_common(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic,
-                          float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
-        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch || (h->capture && h->cap_batch < batch) || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask))) {
-        const int rc = hmv_reserve(h, batch);
-        if (rc != HMV_OK) return rc;
-    }
-    h->last_ragged = false;
-    h->forget_attention();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // stage capture and attention capture copy into side buffers and profiling brackets launches with events: all stay eager
-    if (!h->graphs || h->capture || h->att_mask || h->profiling)
-        return forward_eager(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s);
-
-    hmv_engine::GraphKey key{};
-    key[0] = (uintptr_t)batch; key[1] = (uintptr_t)x; key[2] = (uintptr_t)bbox; key[3] = (uintptr_t)intrinsic;
-    key[4] = (uintptr_t)joints_crop_img; key[5] = (uintptr_t)joints_cam; key[6] = (uintptr_t)heatmap;
-    key[7] = (uintptr_t)h->fsrc.frames; key[8] = (uintptr_t)h->fsrc.boxes;
-    key[9] = ((uintptr_t)(unsigned)h->fsrc.fh << 32) | (uintptr_t)(unsigned)h->fsrc.fw;
-    if (h->fsrc.frames) {
-        uint32_t bits[6];
-        memcpy(bits, h->fsrc.mean, 12);
-        memcpy(bits + 3, h->fsrc.std, 12);
-        key[10] = ((uintptr_t)bits[0] << 32) ^ ((uintptr_t)bits[1] << 16) ^ (uintptr_t)bits[2];
-        key[11] = ((uintptr_t)bits[3] << 32) ^ ((uintptr_t)bits[4] << 16) ^ (uintptr_t)bits[5];
-    }
-    if (h->track.on) {   // the tracking tail is part of the captured work: its buffers and parameters are part of the key
-        key[12] = (uintptr_t)h->track.joints_img; key[13] = (uintptr_t)h->track.status;
-        key[14] = (uintptr_t(1) << 63) | ((uintptr_t)(h->track.square != 0) << 32) | (uintptr_t)(unsigned)h->track.margin;
-    }
-    for (auto &e : h->gcache)
-        if (e.key == key) {
-            e.stamp = ++h->gclock;
-            ++h->greplays;
-            HIPCHK(h, hipGraphLaunch(e.exec, s));
-            return HMV_OK;
-        }
-    auto seen = std::find(h->gseen.begin(), h->gseen.end(), key);
-    if (seen == h->gseen.end()) {   // first sighting: run eagerly (also configures kernels, zero page, ...)
-        if (h->gseen.size() >= 16) h->gseen.erase(h->gseen.begin());
-        h->gseen.push_back(key);
-        return forward_eager(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s);
-    }
-    // second use of the same buffers: capture on the engine's own stream, then launch the graph on the caller's
-    h->gseen.erase(seen);
-    if (!h->gstream) HIPCHK(h, hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking));
-    HIPCHK(h, hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal));
-    const int rc = forward_eager(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, h->gstream);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(h->gstream, &graph);
-    hipGraphExec_t exec = nullptr;
-    if (rc != HMV_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        h->graphs = false;   // capture is not available here: stay eager for the life of the handle
-        if (rc != HMV_OK) return rc;
-        return forward_eager(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s);
-    }
-    (void)hipGraphDestroy(graph);
-    if (h->gcache.size() >= 8) {   // least recently replayed entry makes room
-        size_t lru = 0;
-        for (size_t i = 1; i < h->gcache.size(); ++i)
-            if (h->gcache[i].stamp < h->gcache[lru].stamp) lru = i;
-        (void)hipGraphExecDestroy(h->gcache[lru].exec);
-        h->gcache.erase(h->gcache.begin() + (long)lru);
-    }
-    h->gcache.push_back({key, exec, ++h->gclock});
-    HIPCHK(h, hipGraphLaunch(exec, s));
-    return HMV_OK;
-}
-
 int hmv_set_graphs(hmv_handle h, int32_t enable) {
     if (!h) return HMV_ERR_ARG;
     (void)hipSetDevice(h->cfg.device);
@@ -2360,160 +2554,28 @@ int hmv_graph_stats(hmv_handle h, int32_t *cached, int64_t *replays) {
 
 int hmv_forward(hmv_handle h, int32_t batch, const float *x, const float *bbox, const float *intrinsic, float *joints_crop_img,
                 float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (const int rc = check_handle(h)) return rc;
     if (batch <= 0 || !x || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "null or empty input/output");
-    return forward_common(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
-}
-
-static int check_views(hmv_handle h, const char *who, int32_t batch, const int32_t *view_counts, const float *bbox, const float *intrinsic) {
-    if (batch <= 0) return h->fail(HMV_ERR_ARG, "%s: batch must be positive (got %d)", who, (int)batch);
-    if (!view_counts) return h->fail(HMV_ERR_ARG, "%s: view_counts is null (one host entry per sample)", who);
-    const int V = h->cfg.num_views;
-    for (int b = 0; b < batch; ++b) {
-        const int v = view_counts[b];
-        if (v < 1 || v > V)
-            return h->fail(HMV_ERR_ARG, "%s: view_counts[%d] = %d, every sample needs between 1 and num_views = %d present views", who, b, v, V);
-    }
-    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
-        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
-    return HMV_OK;
-}
-
-// The next slot of the ring of pinned host tables, free to be rewritten (the upload that last read it has run) and with room for tab_n entries
-static int views_slot(hmv_handle h, size_t tab_n, hmv_engine::ViewsSlot *&out) {
-    hmv_engine::ViewsSlot &slot = h->views_host[h->views_next++ % 4];
-    if (slot.done) HIPCHK(h, hipEventSynchronize(slot.done));
-    else HIPCHK(h, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (tab_n > slot.cap) {
-        if (slot.host) HIPCHK(h, hipHostFree(slot.host));
-        slot.host = nullptr;
-        slot.cap = 0;
-        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&slot.host), cap * sizeof(int32_t), hipHostMallocDefault));
-        slot.cap = cap;
-    }
-    out = &slot;
-    return HMV_OK;
-}
-
-// A call whose own plan needs more than the reserved workspace (checked before anything is launched): the workspace grows
-static int grow_workspace(hmv_handle h, size_t need) {
-    if (need <= h->arena_bytes) return HMV_OK;
-    HIPCHK(h, hipDeviceSynchronize());
-    h->drop_graphs();   // captured launches point into the old workspace
-    if (h->arena) HIPCHK(h, hipFree(h->arena));
-    h->arena = nullptr;
-    h->arena_bytes = 0;
-    const int served = h->reserved_batch;   // the larger workspace still serves as many uniform samples
-    h->reserved_batch = 0;
-    HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->arena), need));
-    h->arena_bytes = need;
-    h->reserved_batch = served;
-    return HMV_OK;
-}
-
-// The slot's tab_n entries to the device table, on the caller's stream
-static int upload_views(hmv_handle h, hmv_engine::ViewsSlot &slot, size_t tab_n, hipStream_t s) {
-    if (tab_n > h->views_cap) {   // (hipFree waits for the launches that still read the old table)
-        if (h->views_dev) HIPCHK(h, hipFree(h->views_dev));
-        h->views_dev = nullptr;
-        h->views_cap = 0;
-        const size_t cap = std::max<size_t>(tab_n, (size_t)h->reserved_batch * (h->cfg.num_views + 1) + 1);
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->views_dev), cap * sizeof(int32_t)));
-        h->views_cap = cap;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->views_dev, slot.host, tab_n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipEventRecord(slot.done, s));
-    return HMV_OK;
-}
-
-// the ragged forward behind hmv_forward_views (x) and hmv_forward_frames_views (h->fsrc set, x null); the arguments have been checked
-static int forward_views_common(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox,
-                                const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    size_t N = 0;
-    int vmax = 0;
-    for (int b = 0; b < batch; ++b) {
-        N += (size_t)view_counts[b];
-        vmax = view_counts[b] > vmax ? view_counts[b] : vmax;
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch || (h->att_mask && (h->att_batch < batch || h->att_alloc_mask != h->att_mask))) {
-        const int rc = hmv_reserve(h, batch);
-        if (rc != HMV_OK) return rc;
-    }
-    h->forget_attention();
-    // the tables: [seg: B + 1 | fpos: N]
-    const size_t tab_n = (size_t)batch + 1 + N;
-    hmv_engine::ViewsSlot *slot_p = nullptr;
-    if (const int rc = views_slot(h, tab_n, slot_p)) return rc;
-    hmv_engine::ViewsSlot &slot = *slot_p;
-    int32_t *seg = slot.host, *fpos = seg + batch + 1;
-    seg[0] = 0;
-    for (int b = 0, n = 0; b < batch; ++b) {
-        seg[b + 1] = seg[b] + NJ * view_counts[b];
-        for (int r = 0; r < view_counts[b]; ++r) fpos[n++] = NJ * r;
-    }
-    ViewSet vs{(int)N, nullptr, nullptr, NJ * vmax};
-    // The workspace: reserved for `batch` uniform samples, which asks for more of every buffer than any ragged batch of as many samples.
-    // The planner is first-fit, though, and the ragged cross block holds one more small buffer, so this call's own plan is
-    // checked BEFORE anything is launched, and the workspace grows in the (unobserved) case that it does not fit.
-    {
-        Arena dry;
-        dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));
-        const bool saved = h->profiling;
-        h->profiling = false;
-        run_forward(h, batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry, &vs);
-        h->profiling = saved;
-        if (const int rc = grow_workspace(h, dry.high)) return rc;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = upload_views(h, slot, tab_n, s)) return rc;
-    vs.seg = h->views_dev;
-    vs.fpos = h->views_dev + batch + 1;
-    h->last_ragged = true;
-    h->plan.reset(h->arena);
-    h->launches = 1;
-    const int rc = run_forward(h, batch, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan, &vs);
-    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
-    if (rc == HMV_OK && h->track.on) {
-        // a full-layout slot is present iff a packed frame names it: every slot starts as absent (status 1, zero joints, its window
-        // untouched) and each packed row then moves the window of the slot it came from
-        const int n_slots = h->fsrc.index ? h->fsrc.n_src : (int)N;
-        if (h->track.joints_img) {
-            HIPCHK(h, hipMemsetAsync(h->track.joints_img, 0, (size_t)n_slots * NJ * 2 * sizeof(float), s));
-            ++h->launches;
-        }
-        if (h->track.status) {
-            HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->track.status), 1, (size_t)n_slots, s));
-            ++h->launches;
-        }
-        int *boxes = const_cast<int *>(h->fsrc.boxes);
-        const TrackParams tp{(int)N, n_slots, joints_crop_img, boxes, nullptr, h->fsrc.index, h->cfg.image_size, h->track.margin,
-                             h->track.square, boxes, const_cast<float *>(bbox), h->track.joints_img, h->track.status};
-        HIPCHK(h, launch_next_crop_boxes(tp, s));
-        ++h->launches;
-    }
-    return rc;
+    const ForwardCall fc{batch, x, FrameSrc{}, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
+    return forward_uniform(h, fc);
 }
 
 /* hmv_forward for a batch whose samples have different cameras (include/handmv.h).  Everything that can be refused is refused before the
- * first launch.  Always eager: the tables differ from call to call, so a ragged call never enters the graph replay cache. */
+ * first launch. */
 int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const float *x, const float *bbox, const float *intrinsic,
                       float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (const int rc = check_handle(h)) return rc;
     if (batch > 0 && view_counts && (!x || !joints_crop_img || !joints_cam)) return h->fail(HMV_ERR_ARG, "null or empty input/output");
     if (const int rc = check_views(h, "hmv_forward_views", batch, view_counts, bbox, intrinsic)) return rc;
-    return forward_views_common(h, batch, view_counts, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
+    const ForwardCall fc{batch, x, FrameSrc{}, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
+    return forward_ragged(h, fc, view_counts);
 }
 
 /* A camera-subset sweep (include/handmv.h): one backbone pass, the fusion tail per subset.  Everything that can be refused is refused, and
  * the whole call is planned on the host -- chunks, tables, workspace -- before the first launch.  Always eager. */
 int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const uint8_t *subset_mask, const float *x, const float *bbox,
                         const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
+    if (const int rc = check_handle(h)) return rc;
     if (batch <= 0) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: batch must be positive (got %d)", (int)batch);
     if (n_subsets < 1) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: n_subsets must be at least 1 (got %d)", (int)n_subsets);
     if (!subset_mask) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: subset_mask is null (host uint8 [n_subsets][num_views])");
@@ -2525,30 +2587,26 @@ int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const ui
         for (int v = 0; v < V; ++v) count[i] += subset_mask[(size_t)i * V + v] != 0;
         if (!count[i]) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: subset %d has no camera", i);
     }
-    if ((h->cfg.pos_enc & HMV_POS_CROP) && (!bbox || !intrinsic))
-        return h->fail(HMV_ERR_ARG, "pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required");
+    if (const int rc = check_crop_pe(h, bbox, intrinsic)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch) {
-        const int rc = hmv_reserve(h, batch);
-        if (rc != HMV_OK) return rc;
-    }
+    if (batch > h->reserved_batch)
+        if (const int rc = hmv_reserve(h, batch)) return rc;
     // the passes: at most max(batch, reserved batch) virtual samples each, so that every buffer of a pass stays within the reservation
     const int total = S * batch, cmax = std::max<int>(batch, h->reserved_batch);
     std::vector<SubsetChunk> chunks;
-    size_t tab_n = 0;
+    ViewsUpload up{nullptr, 0};
     for (int q0 = 0; q0 < total; q0 += cmax) {
-        SubsetChunk ck{q0, std::min(cmax, total - q0), 0, 0, tab_n};
+        SubsetChunk ck{q0, std::min(cmax, total - q0), 0, 0, up.tab_n};
         for (int q = q0; q < q0 + ck.nv; ++q) {
             ck.n += count[q / batch];
             ck.vmax = std::max(ck.vmax, count[q / batch]);
         }
-        tab_n += (size_t)ck.nv + 1 + 2 * (size_t)ck.n;
+        up.tab_n += (size_t)ck.nv + 1 + 2 * (size_t)ck.n;
         chunks.push_back(ck);
     }
-    hmv_engine::ViewsSlot *slot = nullptr;
-    if (const int rc = views_slot(h, tab_n, slot)) return rc;
+    if (const int rc = views_slot(h, up.tab_n, up.slot)) return rc;
     for (const SubsetChunk &ck : chunks) {
-        int32_t *seg = slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
+        int32_t *seg = up.slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
         seg[0] = 0;
         for (int i = 0, m = 0; i < ck.nv; ++i) {
             const int q = ck.q0 + i, sub = q / batch, b = q % batch;
@@ -2557,71 +2615,25 @@ int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const ui
                 if (subset_mask[(size_t)sub * V + v]) { fpos[m] = NJ * r++; src[m++] = b * V + v; }
         }
     }
-    {   // the call's own plan -- the retained rows and a pass's packed rows come on top of a forward's buffers -- before anything is launched
-        Arena dry;
-        dry.reset(reinterpret_cast<char *>(uintptr_t(1) << 40));
-        const bool saved = h->profiling;
-        h->profiling = false;
-        run_forward_subsets(h, batch, chunks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, /*dry=*/true, dry);
-        h->profiling = saved;
-        if (const int rc = grow_workspace(h, dry.high)) return rc;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = upload_views(h, *slot, tab_n, s)) return rc;
-    h->last_ragged = true;   // (no stages either)
-    h->forget_attention();   // (nor attention maps: a sweep ignores the mask)
-    h->plan.reset(h->arena);
-    h->launches = 1;
-    const int rc = run_forward_subsets(h, batch, chunks, h->views_dev, x, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, s, false, h->plan);
-    if (rc == HMV_OK && h->plan.high > h->arena_bytes) return h->fail(HMV_ERR_STATE, "workspace plan exceeded its reservation");
-    return rc;
+    const ForwardCall fc{batch, x, FrameSrc{}, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
+    auto run = [&](const ForwardCall &c, bool dry, Arena &A) { return run_forward_subsets(h, c, chunks, dry ? nullptr : h->views_dev, dry, A); };
+    if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
+    h->forget_attention();   // (no attention maps either: a sweep ignores the mask)
+    return run_checked(h, fc, 1, run);
 }
 
-/* hmv_forward_views from raw camera frames (include/handmv.h): the indexed frame preparation in front of the ragged forward. */
 int hmv_forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
                              const int32_t *crop_boxes, const int32_t *frame_index, const float *mean, const float *std, const float *bbox,
                              const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
-    if (const int rc = check_views(h, "hmv_forward_frames_views", batch, view_counts, bbox, intrinsic)) return rc;
-    if (!frames || !crop_boxes || !mean || !std || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "null or empty input/output");
-    if (frame_h <= 0 || frame_w <= 0) return h->fail(HMV_ERR_ARG, "frame size must be positive");
-    for (int c = 0; c < 3; ++c)
-        if (!(std[c] > 0.f)) return h->fail(HMV_ERR_ARG, "std must be positive");
-    h->fsrc.frames = frames;
-    h->fsrc.boxes = crop_boxes;
-    h->fsrc.index = frame_index;
-    h->fsrc.n_src = batch * h->cfg.num_views;
-    h->fsrc.fh = frame_h;
-    h->fsrc.fw = frame_w;
-    for (int c = 0; c < 3; ++c) { h->fsrc.mean[c] = mean[c]; h->fsrc.std[c] = std[c]; }
-    const int rc = forward_views_common(h, batch, view_counts, nullptr, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
-    h->fsrc.frames = nullptr;
-    h->fsrc.boxes = nullptr;
-    h->fsrc.index = nullptr;
-    h->fsrc.n_src = 0;
-    return rc;
+    return forward_frames_views(h, batch, view_counts, frames, frame_h, frame_w, crop_boxes, frame_index, mean, std, bbox, intrinsic,
+                                joints_crop_img, joints_cam, heatmap, TrackTail{}, stream);
 }
 
 int hmv_forward_frames(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w, const int32_t *crop_boxes,
                        const float *mean, const float *std, const float *bbox, const float *intrinsic, float *joints_crop_img,
                        float *joints_cam, float *heatmap, void *stream) {
-    if (!h) return HMV_ERR_ARG;
-    if (!h->finalized) return h->fail(HMV_ERR_STATE, "hmv_finalize_weights has not succeeded on this handle");
-    if (batch <= 0 || !frames || !crop_boxes || !mean || !std || !joints_crop_img || !joints_cam)
-        return h->fail(HMV_ERR_ARG, "null or empty input/output");
-    if (frame_h <= 0 || frame_w <= 0) return h->fail(HMV_ERR_ARG, "frame size must be positive");
-    for (int c = 0; c < 3; ++c)
-        if (!(std[c] > 0.f)) return h->fail(HMV_ERR_ARG, "std must be positive");
-    h->fsrc.frames = frames;
-    h->fsrc.boxes = crop_boxes;
-    h->fsrc.fh = frame_h;
-    h->fsrc.fw = frame_w;
-    for (int c = 0; c < 3; ++c) { h->fsrc.mean[c] = mean[c]; h->fsrc.std[c] = std[c]; }
-    const int rc = forward_common(h, batch, nullptr, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, stream);
-    h->fsrc.frames = nullptr;
-    h->fsrc.boxes = nullptr;
-    return rc;
+    return forward_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, bbox, intrinsic, joints_crop_img, joints_cam, heatmap,
+                          TrackTail{}, stream);
 }
 
 /* hmv_forward_frames, then on the same stream the windows and bbox moved in place to the box around the joints just found
@@ -2632,15 +2644,8 @@ int hmv_forward_frames_track(hmv_handle h, int32_t batch, const uint8_t *frames,
                              void *stream) {
     if (!h) return HMV_ERR_ARG;
     if (margin < 0) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_track: margin must not be negative");
-    h->track.on = true;
-    h->track.margin = margin;
-    h->track.square = square != 0;
-    h->track.joints_img = joints_img;
-    h->track.status = status;
-    const int rc = hmv_forward_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, bbox, intrinsic, joints_crop_img,
-                                      joints_cam, heatmap, stream);
-    h->track = hmv_engine::TrackTail();
-    return rc;
+    return forward_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, bbox, intrinsic, joints_crop_img, joints_cam, heatmap,
+                          TrackTail{true, margin, square != 0, joints_img, status}, stream);
 }
 
 int hmv_forward_frames_views_track(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h,
@@ -2649,15 +2654,8 @@ int hmv_forward_frames_views_track(hmv_handle h, int32_t batch, const int32_t *v
                                    int32_t margin, int32_t square, float *joints_img, int32_t *status, void *stream) {
     if (!h) return HMV_ERR_ARG;
     if (margin < 0) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_views_track: margin must not be negative");
-    h->track.on = true;
-    h->track.margin = margin;
-    h->track.square = square != 0;
-    h->track.joints_img = joints_img;
-    h->track.status = status;
-    const int rc = hmv_forward_frames_views(h, batch, view_counts, frames, frame_h, frame_w, crop_boxes, frame_index, mean, std, bbox,
-                                            intrinsic, joints_crop_img, joints_cam, heatmap, stream);
-    h->track = hmv_engine::TrackTail();
-    return rc;
+    return forward_frames_views(h, batch, view_counts, frames, frame_h, frame_w, crop_boxes, frame_index, mean, std, bbox, intrinsic,
+                                joints_crop_img, joints_cam, heatmap, TrackTail{true, margin, square != 0, joints_img, status}, stream);
 }
 
 int hmv_op_prepare_frames(int32_t device, const uint8_t *frames, int32_t n_frames, int32_t frame_h, int32_t frame_w,

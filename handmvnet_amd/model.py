@@ -199,44 +199,120 @@ class HandMvNet(torch.nn.Module):
         _lib.check(_lib.load().hmv_reserve(h, batch), h)
         return int(_lib.load().hmv_workspace_bytes(h, batch))
 
-    # ------------------------------------------------------------------ forward (handmvnet.py:158-266)
-    def forward(self, x, bbox=None, cam_params=None):
+    # ------------------------------------------------------------------ what the forward methods share
+    @staticmethod
+    def _need_cuda(t, name: str):
+        if not t.is_cuda:
+            raise _lib.HandMvError(f"handmvnet_amd runs on MI355X only: {name} must be a CUDA(HIP) tensor (no CPU fallback)")
+
+    @staticmethod
+    def _check_x(x):
         if not isinstance(x, torch.Tensor) or x.dim() != 5:
             raise ValueError("x must be a [b, v, 3, h, w] tensor")
-        if not x.is_cuda:
-            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
-        b, v, c, hh, ww = x.shape
-        if c != 3:
+
+    @staticmethod
+    def _check_channels(x):
+        if x.shape[2] != 3:
             raise ValueError("x must have 3 channels")
-        n = b * v
+
+    def _check_all_views(self, v: int, what: str, named_by: str):
+        if v != self.num_views:
+            raise ValueError(f"{what} must hold all {self.num_views} views per sample ({named_by}), got {v}")
+
+    @staticmethod
+    def _check_frames(frames):
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 5 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise ValueError("frames must be a uint8 [b, v, Hf, Wf, 3] tensor")
+
+    def _uniform_batch(self, n: int) -> int:
         if n % self.num_views:
             # the reference's .view(-1, num_views, ...) (handmvnet.py:194) raises here as well
             raise RuntimeError(f"shape '[-1, {self.num_views}, ...]' is invalid for input of {n} frames")
-        batch = n // self.num_views
-        dev = x.device
-        x = x.contiguous().float()
-        need_cam = "crop" in self.cfg.pos_enc
-        bb = it = None
-        if need_cam:
+        return n // self.num_views
+
+    @staticmethod
+    def _window_rows(crop_boxes, dev, n: int):
+        boxes = crop_boxes.to(dev).reshape(-1, 4).to(torch.int32).contiguous()
+        if boxes.shape[0] != n:
+            raise RuntimeError("crop_boxes must hold one row per frame")
+        return boxes
+
+    @staticmethod
+    def _present_table(mask, dev):
+        """The present frames of a host mask [b, v], sample-major, camera order: the int32 table the engine reads from raw frames (the
+        one small upload) and the int64 index made from it on the device."""
+        table = torch.from_numpy(np.flatnonzero(mask.reshape(-1)).astype(np.int32)).to(dev)
+        return table, table.long()
+
+    def _camera_rows(self, dev, n: int, cam_params, bbox=None, boxes=None, idx=None):
+        """(bbox, intrinsic) as fp32 [n, 4] rows on `dev` for the crop-FoV columns, (None, None) for a model without them.  boxes: the
+        int32 windows of a call from raw frames, which serve as bbox.  idx: only the present rows, gathered on the device."""
+        if "crop" not in self.cfg.pos_enc:
+            return None, None
+        if boxes is None:
             if bbox is None or cam_params is None:
                 raise TypeError("pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required")
             bb = bbox.to(dev).reshape(-1, 4).contiguous().float()
-            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).contiguous().float()
-            if bb.shape[0] != n or it.shape[0] != n:
-                raise RuntimeError("bbox / intrinsic must hold one row per frame")
-        h = self._engine(hh, ww, dev.index if dev.index is not None else torch.cuda.current_device())
-        hs_h, hs_w = heatmap_size_of(self.cfg, hh, ww)   # H/8 x W/8 at the release sizes; the conv arithmetic otherwise
-        out_crop = torch.empty(batch, self.num_views, 21, 2, device=dev, dtype=torch.float32)
-        out_cam = torch.empty(batch, 21, 3, device=dev, dtype=torch.float32)
-        out_hm = torch.empty(batch, self.num_views, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        else:
+            if cam_params is None:
+                raise TypeError("pos_enc contains 'crop': cam_params['intrinsic'] is required")
+            bb = boxes.float()
+        it = cam_params["intrinsic"].to(dev).reshape(-1, 4).contiguous().float()
+        if bb.shape[0] != n or it.shape[0] != n:
+            raise RuntimeError(("bbox / intrinsic" if boxes is None else "intrinsic") + " must hold one row per frame")
+        return (bb, it) if idx is None else (bb.index_select(0, idx), it.index_select(0, idx))
+
+    @staticmethod
+    def _outputs(dev, frames_shape, cam_shape, hs):
+        """(joints_crop_img, joints_cam, heatmap) buffers: per frame [*frames_shape, 21, ...], per sample [*cam_shape, 21, 3]."""
+        f32 = torch.float32
+        return (torch.empty(frames_shape + (21, 2), device=dev, dtype=f32), torch.empty(cam_shape + (21, 3), device=dev, dtype=f32),
+                torch.empty(frames_shape + (21,) + tuple(hs), device=dev, dtype=f32))
+
+    @staticmethod
+    def _scatter_rows(packed, idx, full):
+        """The packed rows of the present frames into `full` [b, v, ...], zeroed first: the rows of absent views are zeros."""
+        full.zero_().view((-1,) + tuple(packed.shape[1:])).index_copy_(0, idx, packed)
+        return full
+
+    def _call(self, entry: str, hh: int, ww: int, dev, batch: int, *args):
+        """One raw engine call on `dev`'s current stream: entry(handle, batch, *args, stream); tensors are passed by address."""
+        didx = dev.index if dev.index is not None else torch.cuda.current_device()
+        h = self._engine(hh, ww, didx)
+        args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
         with torch.cuda.device(dev):
-            rc = _lib.load().hmv_forward(h, batch, x.data_ptr(), bb.data_ptr() if bb is not None else None,
-                                         it.data_ptr() if it is not None else None, out_crop.data_ptr(), out_cam.data_ptr(),
-                                         out_hm.data_ptr(), ctypes.c_void_p(stream))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = getattr(_lib.load(), entry)(h, batch, *args, ctypes.c_void_p(stream))
         _lib.check(rc, h)
-        self._last_key = (hh, ww, dev.index if dev.index is not None else torch.cuda.current_device(), batch, self._dtype)
-        return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
+        self._last_key = (hh, ww, didx, batch, self._dtype)
+
+    def _call_views(self, entry: str, size, dev, mask, counts, idx, args, bb, it, tail=(), into=None):
+        """A ragged call: packed outputs for the present frames, scattered back to the full [b, v] layout (`into`: the caller's own
+        joints_crop_img / joints_cam / heatmap buffers).  args: the entry's arguments between view_counts and bbox."""
+        b, v = mask.shape
+        hs = tuple(heatmap_size_of(self.cfg, *size)) if into is None else tuple(into["heatmap"].shape[-2:])
+        if into is None:
+            into = dict(zip(("joints_crop_img", "joints_cam", "heatmap"), self._outputs(dev, (b, v), (b,), hs)))
+        crop_p, hm_p = into["joints_crop_img"].new_empty(idx.numel(), 21, 2), into["heatmap"].new_empty((idx.numel(), 21) + hs)
+        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
+        self._call(entry, *size, dev, b, cnt, *args, bb, it, crop_p, into["joints_cam"], hm_p, *tail)
+        return {"joints_crop_img": self._scatter_rows(crop_p, idx, into["joints_crop_img"]), "joints_cam": into["joints_cam"],
+                "heatmap": self._scatter_rows(hm_p, idx, into["heatmap"])}
+
+    # ------------------------------------------------------------------ forward (handmvnet.py:158-266)
+    def forward(self, x, bbox=None, cam_params=None):
+        self._check_x(x)
+        self._need_cuda(x, "x")
+        self._check_channels(x)
+        b, v, _, hh, ww = x.shape
+        batch = self._uniform_batch(b * v)
+        dev = x.device
+        x = x.contiguous().float()
+        bb, it = self._camera_rows(dev, b * v, cam_params, bbox=bbox)
+        hs = heatmap_size_of(self.cfg, hh, ww)   # H/8 x W/8 at the release sizes; the conv arithmetic otherwise
+        crop, cam, hm = self._outputs(dev, (batch, self.num_views), (batch,), hs)
+        self._call("hmv_forward", hh, ww, dev, batch, x, bb, it, crop, cam, hm)
+        return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
 
     @staticmethod
     def _host_view_mask(view_mask, b: int, v: int):
@@ -260,46 +336,17 @@ class HandMvNet(torch.nn.Module):
         as forward(); the `joints_crop_img` and `heatmap` rows of absent views are zeros (as mask_joints zeroes both sides,
         models/utils.py:123-131).  The mask is read on the host: pass it as a host tensor, array or list -- a device mask costs one
         synchronising copy.  Present frames and their bbox / intrinsic rows are packed with one device gather each."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 5:
-            raise ValueError("x must be a [b, v, 3, h, w] tensor")
-        b, v, c, hh, ww = x.shape
-        if c != 3:
-            raise ValueError("x must have 3 channels")
-        if v != self.num_views:
-            raise ValueError(f"x must hold all {self.num_views} views per sample (absent ones are named by view_mask), got {v}")
+        self._check_x(x)
+        self._check_channels(x)
+        b, v, _, hh, ww = x.shape
+        self._check_all_views(v, "x", "absent ones are named by view_mask")
         mask, counts = self._host_view_mask(view_mask, b, v)
-        if not x.is_cuda:
-            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
+        self._need_cuda(x, "x")
         dev = x.device
-        n = int(counts.sum())
         idx = torch.from_numpy(np.flatnonzero(mask.reshape(-1))).to(dev)   # present frames, sample-major, camera order
         xp = x.reshape(b * v, 3, hh, ww).float().index_select(0, idx)
-        bb = it = None
-        if "crop" in self.cfg.pos_enc:
-            if bbox is None or cam_params is None:
-                raise TypeError("pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required")
-            bb = bbox.to(dev).reshape(-1, 4).float()
-            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).float()
-            if bb.shape[0] != b * v or it.shape[0] != b * v:
-                raise RuntimeError("bbox / intrinsic must hold one row per frame")
-            bb, it = bb.index_select(0, idx), it.index_select(0, idx)
-        didx = dev.index if dev.index is not None else torch.cuda.current_device()
-        h = self._engine(hh, ww, didx)
-        hs_h, hs_w = heatmap_size_of(self.cfg, hh, ww)
-        crop_p = torch.empty(n, 21, 2, device=dev, dtype=torch.float32)
-        hm_p = torch.empty(n, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
-        out_cam = torch.empty(b, 21, 3, device=dev, dtype=torch.float32)
-        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().hmv_forward_views(h, b, cnt, xp.data_ptr(), bb.data_ptr() if bb is not None else None,
-                                               it.data_ptr() if it is not None else None, crop_p.data_ptr(), out_cam.data_ptr(),
-                                               hm_p.data_ptr(), ctypes.c_void_p(stream))
-        _lib.check(rc, h)
-        self._last_key = (hh, ww, didx, b, self._dtype)
-        out_crop = torch.zeros(b * v, 21, 2, device=dev, dtype=torch.float32).index_copy_(0, idx, crop_p)
-        out_hm = torch.zeros(b * v, 21, hs_h, hs_w, device=dev, dtype=torch.float32).index_copy_(0, idx, hm_p)
-        return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
+        bb, it = self._camera_rows(dev, b * v, cam_params, bbox=bbox, idx=idx)
+        return self._call_views("hmv_forward_views", (hh, ww), dev, mask, counts, idx, (xp,), bb, it)
 
     def forward_subsets(self, x, subsets, bbox=None, cam_params=None):
         """forward_views() for S camera subsets of the same full batch at the cost of ONE backbone pass (hmv_forward_subsets): `x` is
@@ -308,43 +355,21 @@ class HandMvNet(torch.nn.Module):
         `joints_cam` of shape [S, b, 21, 3]: joints_cam[s] holds the bits forward_views() returns with view_mask = subset s on every
         sample.  `joints_crop_img` and `heatmap` are forward()'s, written once for all v views.  The table is read on the host."""
         from .subsets import as_subset_table
-        if not isinstance(x, torch.Tensor) or x.dim() != 5:
-            raise ValueError("x must be a [b, v, 3, h, w] tensor")
-        b, v, c, hh, ww = x.shape
-        if c != 3:
-            raise ValueError("x must have 3 channels")
-        if v != self.num_views:
-            raise ValueError(f"x must hold all {self.num_views} views per sample (the subsets name the present ones), got {v}")
+        self._check_x(x)
+        self._check_channels(x)
+        b, v, _, hh, ww = x.shape
+        self._check_all_views(v, "x", "the subsets name the present ones")
         if b == 0:
             raise ValueError("x holds no sample")
         table = as_subset_table(subsets, v)
-        if not x.is_cuda:
-            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: x must be a CUDA(HIP) tensor (no CPU fallback)")
+        self._need_cuda(x, "x")
         dev = x.device
         x = x.contiguous().float()
-        bb = it = None
-        if "crop" in self.cfg.pos_enc:
-            if bbox is None or cam_params is None:
-                raise TypeError("pos_enc contains 'crop': bbox and cam_params['intrinsic'] are required")
-            bb = bbox.to(dev).reshape(-1, 4).contiguous().float()
-            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).contiguous().float()
-            if bb.shape[0] != b * v or it.shape[0] != b * v:
-                raise RuntimeError("bbox / intrinsic must hold one row per frame")
-        didx = dev.index if dev.index is not None else torch.cuda.current_device()
-        h = self._engine(hh, ww, didx)
-        hs_h, hs_w = heatmap_size_of(self.cfg, hh, ww)
+        bb, it = self._camera_rows(dev, b * v, cam_params, bbox=bbox)
         S = table.shape[0]
-        out_crop = torch.empty(b, v, 21, 2, device=dev, dtype=torch.float32)
-        out_cam = torch.empty(S, b, 21, 3, device=dev, dtype=torch.float32)
-        out_hm = torch.empty(b, v, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().hmv_forward_subsets(h, b, S, table.ctypes.data_as(ctypes.c_void_p), x.data_ptr(),
-                                                 bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None,
-                                                 out_crop.data_ptr(), out_cam.data_ptr(), out_hm.data_ptr(), ctypes.c_void_p(stream))
-        _lib.check(rc, h)
-        self._last_key = (hh, ww, didx, b, self._dtype)
-        return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
+        crop, cam, hm = self._outputs(dev, (b, v), (S, b), heatmap_size_of(self.cfg, hh, ww))
+        self._call("hmv_forward_subsets", hh, ww, dev, b, S, table.ctypes.data_as(ctypes.c_void_p), x, bb, it, crop, cam, hm)
+        return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
 
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                        image_size=None, view_mask=None):
@@ -352,93 +377,31 @@ class HandMvNet(torch.nn.Module):
         [b, v, 4] (x1, y1, x2, y2; may leave the frame, empty = black view) replace the reference's host-side
         crop_and_pad_image -> ToTensor -> Resize(antialias=True) -> Normalize (datasets/ho3d.py:35-40, 136-149); the
         windows also serve as `bbox` for the crop-FoV columns (ho3d.py:198).  Same return dict as forward().
-        view_mask (bool [b, v] tensor, array or nested list, True = present; read on the host): forward_views() from raw frames --
-        only the present frames are prepared, straight from where they lie in `frames` (an index table, one small upload; no uint8
-        frame is copied or gathered); return dict and shapes as forward_views(): rows of absent views are zeros."""
-        if not isinstance(frames, torch.Tensor) or frames.dim() != 5 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
-            raise ValueError("frames must be a uint8 [b, v, Hf, Wf, 3] tensor")
+        view_mask (bool [b, v] tensor, array or nested list, True = present; read on the host): forward_views() from raw frames
+        (hmv_forward_frames_views) -- only the present frames are prepared, straight from where they lie in `frames` (an index table,
+        one small upload; no uint8 frame is copied or gathered); return dict and shapes as forward_views(): rows of absent views are
+        zeros."""
+        self._check_frames(frames)
+        b, v, fh, fw, _ = frames.shape
+        mask = None
         if view_mask is not None:
-            return self._forward_frames_views(frames, crop_boxes, view_mask, cam_params, mean, std, image_size)
-        if not frames.is_cuda:
-            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: frames must be a CUDA(HIP) tensor (no CPU fallback)")
-        b, v, fh, fw, _ = frames.shape
-        n = b * v
-        if n % self.num_views:
-            raise RuntimeError(f"shape '[-1, {self.num_views}, ...]' is invalid for input of {n} frames")
-        batch = n // self.num_views
+            self._check_all_views(v, "frames", "absent ones are named by view_mask")
+            mask, counts = self._host_view_mask(view_mask, b, v)
+        self._need_cuda(frames, "frames")
+        batch = b if mask is not None else self._uniform_batch(b * v)
         dev = frames.device
         size = int(image_size or self.cfg.image_size)
         frames = frames.contiguous()
-        boxes = crop_boxes.to(dev).reshape(-1, 4).to(torch.int32).contiguous()
-        if boxes.shape[0] != n:
-            raise RuntimeError("crop_boxes must hold one row per frame")
-        bb = it = None
-        if "crop" in self.cfg.pos_enc:
-            if cam_params is None:
-                raise TypeError("pos_enc contains 'crop': cam_params['intrinsic'] is required")
-            bb = boxes.float()
-            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).contiguous().float()
-            if it.shape[0] != n:
-                raise RuntimeError("intrinsic must hold one row per frame")
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        h = self._engine(size, size, idx)
-        out_crop = torch.empty(batch, self.num_views, 21, 2, device=dev, dtype=torch.float32)
-        out_cam = torch.empty(batch, 21, 3, device=dev, dtype=torch.float32)
-        out_hm = torch.empty((batch, self.num_views, 21) + tuple(heatmap_size_of(self.cfg, size, size)), device=dev, dtype=torch.float32)
+        boxes = self._window_rows(crop_boxes, dev, b * v)
         m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().hmv_forward_frames(h, batch, frames.data_ptr(), fh, fw, boxes.data_ptr(), m3, s3,
-                                                bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None,
-                                                out_crop.data_ptr(), out_cam.data_ptr(), out_hm.data_ptr(), ctypes.c_void_p(stream))
-        _lib.check(rc, h)
-        self._last_key = (size, size, idx, batch, self._dtype)
-        return {"joints_crop_img": out_crop, "joints_cam": out_cam, "heatmap": out_hm}
-
-    def _forward_frames_views(self, frames, crop_boxes, view_mask, cam_params, mean, std, image_size):
-        """forward_frames(view_mask=...): hmv_forward_frames_views."""
-        b, v, fh, fw, _ = frames.shape
-        if v != self.num_views:
-            raise ValueError(f"frames must hold all {self.num_views} views per sample (absent ones are named by view_mask), got {v}")
-        mask, counts = self._host_view_mask(view_mask, b, v)
-        if not frames.is_cuda:
-            raise _lib.HandMvError("handmvnet_amd runs on MI355X only: frames must be a CUDA(HIP) tensor (no CPU fallback)")
-        dev = frames.device
-        size = int(image_size or self.cfg.image_size)
-        frames = frames.contiguous()
-        boxes = crop_boxes.to(dev).reshape(-1, 4).to(torch.int32).contiguous()
-        if boxes.shape[0] != b * v:
-            raise RuntimeError("crop_boxes must hold one row per frame")
-        n = int(counts.sum())
-        present = np.flatnonzero(mask.reshape(-1))                      # present frames, sample-major, camera order
-        table = torch.from_numpy(present.astype(np.int32)).to(dev)      # the one small upload
-        idx = table.long()
-        bb = it = None
-        if "crop" in self.cfg.pos_enc:
-            if cam_params is None:
-                raise TypeError("pos_enc contains 'crop': cam_params['intrinsic'] is required")
-            it = cam_params["intrinsic"].to(dev).reshape(-1, 4).float()
-            if it.shape[0] != b * v:
-                raise RuntimeError("intrinsic must hold one row per frame")
-            bb, it = boxes.float().index_select(0, idx), it.index_select(0, idx)
-        didx = dev.index if dev.index is not None else torch.cuda.current_device()
-        h = self._engine(size, size, didx)
-        hs_h, hs_w = heatmap_size_of(self.cfg, size, size)
-        crop_p = torch.empty(n, 21, 2, device=dev, dtype=torch.float32)
-        hm_p = torch.empty(n, 21, hs_h, hs_w, device=dev, dtype=torch.float32)
-        out_cam = torch.empty(b, 21, 3, device=dev, dtype=torch.float32)
-        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
-        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().hmv_forward_frames_views(h, b, cnt, frames.data_ptr(), fh, fw, boxes.data_ptr(), table.data_ptr(), m3, s3,
-                                                      bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None,
-                                                      crop_p.data_ptr(), out_cam.data_ptr(), hm_p.data_ptr(), ctypes.c_void_p(stream))
-        _lib.check(rc, h)
-        self._last_key = (size, size, didx, b, self._dtype)
-        out_crop = torch.zeros(b * v, 21, 2, device=dev, dtype=torch.float32).index_copy_(0, idx, crop_p)
-        out_hm = torch.zeros(b * v, 21, hs_h, hs_w, device=dev, dtype=torch.float32).index_copy_(0, idx, hm_p)
-        return {"joints_crop_img": out_crop.view(b, v, 21, 2), "joints_cam": out_cam, "heatmap": out_hm.view(b, v, 21, hs_h, hs_w)}
+        if mask is not None:
+            table, idx = self._present_table(mask, dev)
+            bb, it = self._camera_rows(dev, b * v, cam_params, boxes=boxes, idx=idx)
+            return self._call_views("hmv_forward_frames_views", (size, size), dev, mask, counts, idx, (frames, fh, fw, boxes, table, m3, s3), bb, it)
+        bb, it = self._camera_rows(dev, b * v, cam_params, boxes=boxes)
+        crop, cam, hm = self._outputs(dev, (batch, self.num_views), (batch,), heatmap_size_of(self.cfg, size, size))
+        self._call("hmv_forward_frames", size, size, dev, batch, frames, fh, fw, boxes, m3, s3, bb, it, crop, cam, hm)
+        return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
 
     # ------------------------------------------------------------------ evaluation (handmvnet.py:352-383, 493-517)
     def _get_metrics(self, pred_pts, target_pts):

@@ -154,61 +154,36 @@ class SequenceTracker:
             self._bbox.copy_(self._boxes)
 
     def step(self, frames: torch.Tensor, view_mask=None) -> dict:
-        if not isinstance(frames, torch.Tensor) or frames.dim() != 5 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
-            raise ValueError("frames must be a uint8 [b, v, Hf, Wf, 3] tensor")
-        b, v = self.batch, self.num_views
+        model, dev, b, v, out = self.model, self.device, self.batch, self.num_views, self._out
+        model._check_frames(frames)
         if tuple(frames.shape[:2]) != (b, v):
             raise ValueError(f"frames must hold {b} x {v} views like the tracker's windows, got {list(frames.shape[:2])}")
         if self._frames is None:
-            self._frames = torch.empty(tuple(frames.shape), device=self.device, dtype=torch.uint8)
+            self._frames = torch.empty(tuple(frames.shape), device=dev, dtype=torch.uint8)
         elif tuple(frames.shape) != tuple(self._frames.shape):
             raise ValueError(f"frame size {list(frames.shape[2:4])} differs from the first step's {list(self._frames.shape[2:4])}")
         if not frames.is_cuda and not frames.is_pinned():
             raise _lib.HandMvError("handmvnet_amd runs on MI355X only: frames must be a CUDA(HIP) tensor or pinned host memory")
-        dev, model, lib = self.device, self.model, _lib.load()
         mask = counts = None
         if view_mask is not None:
             mask, counts = model._host_view_mask(view_mask, b, v)
-        fh, fw = int(frames.shape[2]), int(frames.shape[3])
-        size = self.image_size
-        h = model._engine(size, size, dev.index)
-        out = self._out
-        with torch.cuda.device(dev):
-            self._frames.copy_(frames, non_blocking=True)
-            self._used.copy_(self._boxes)
-            if mask is None:
-                rc = lib.hmv_forward_frames_track(
-                    h, b, self._frames.data_ptr(), fh, fw, self._boxes.data_ptr(), self._mean, self._std,
-                    self._bbox.data_ptr() if self._bbox is not None else None, self._intr.data_ptr() if self._intr is not None else None,
-                    out["joints_crop_img"].data_ptr(), out["joints_cam"].data_ptr(), out["heatmap"].data_ptr(), self.margin,
-                    int(self.square), self._joints_img.data_ptr(), self._status.data_ptr(), _stream(dev))
-                _lib.check(rc, h)
-            else:
-                self._ragged_step(h, mask, counts, fh, fw)
-        model._last_key = (size, size, dev.index, b, model._dtype)
+        size = (self.image_size, self.image_size)
+        src = (self._frames, int(frames.shape[2]), int(frames.shape[3]), self._boxes)
+        tail = (self.margin, int(self.square), self._joints_img, self._status)
+        model._engine(*size, dev.index)   # (made, or refused, before anything is enqueued)
+        self._frames.copy_(frames, non_blocking=True)   # copies run on the current stream of the tensors' own device, like the call
+        self._used.copy_(self._boxes)
+        if mask is None:
+            model._call("hmv_forward_frames_track", *size, dev, b, *src, self._mean, self._std, self._bbox, self._intr,
+                        out["joints_crop_img"], out["joints_cam"], out["heatmap"], *tail)
+        else:   # hmv_forward_frames_views_track: the packed rows of the present frames, scattered back into the tracker's full buffers
+            table, idx = model._present_table(mask, dev)
+            bb = it = None
+            if self._need_cam:
+                bb, it = self._bbox.view(-1, 4).index_select(0, idx), self._intr.index_select(0, idx)
+            model._call_views("hmv_forward_frames_views_track", size, dev, mask, counts, idx, src + (table, self._mean, self._std), bb, it,
+                              tail=tail, into=out)
+            if self._bbox is not None:
+                self._bbox.copy_(self._boxes)   # the full fp32 copy follows the windows (the entry updated the packed rows)
         return {"joints_crop_img": out["joints_crop_img"], "joints_cam": out["joints_cam"], "heatmap": out["heatmap"],
                 "joints_img": self._joints_img, "status": self._status, "crop_boxes": self._boxes, "crop_boxes_used": self._used}
-
-    def _ragged_step(self, h, mask, counts, fh, fw):
-        """hmv_forward_frames_views_track: the packed rows of the present frames, scattered back into the tracker's full buffers."""
-        dev, b, v, out = self.device, self.batch, self.num_views, self._out
-        n = int(counts.sum())
-        table = torch.from_numpy(np.flatnonzero(mask.reshape(-1)).astype(np.int32)).to(dev)   # the one small upload
-        idx = table.long()
-        bb = it = None
-        if self._need_cam:
-            bb, it = self._bbox.view(-1, 4).index_select(0, idx), self._intr.index_select(0, idx)
-        hs = tuple(out["heatmap"].shape[-2:])
-        crop_p = torch.empty(n, 21, 2, device=dev)
-        hm_p = torch.empty((n, 21) + hs, device=dev)
-        cnt = (ctypes.c_int32 * b)(*[int(k) for k in counts])
-        rc = _lib.load().hmv_forward_frames_views_track(
-            h, b, cnt, self._frames.data_ptr(), fh, fw, self._boxes.data_ptr(), table.data_ptr(), self._mean, self._std,
-            bb.data_ptr() if bb is not None else None, it.data_ptr() if it is not None else None, crop_p.data_ptr(),
-            out["joints_cam"].data_ptr(), hm_p.data_ptr(), self.margin, int(self.square), self._joints_img.data_ptr(),
-            self._status.data_ptr(), _stream(dev))
-        _lib.check(rc, h)
-        out["joints_crop_img"].zero_().view(b * v, 21, 2).index_copy_(0, idx, crop_p)
-        out["heatmap"].zero_().view((b * v, 21) + hs).index_copy_(0, idx, hm_p)
-        if self._bbox is not None:
-            self._bbox.copy_(self._boxes)   # the full fp32 copy follows the windows (the entry updated the packed rows)

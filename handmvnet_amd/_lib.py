@@ -18,7 +18,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_eval_add_views", "hmv_forward_frames_views", "hmv_op_next_crop_boxes", "hmv_forward_frames_track",
            "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
-           "hmv_read_attention", "hmv_op_attention_probs"]
+           "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
+           "hmv_eval_breakdown_add"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -55,6 +56,16 @@ class HmvEvalArgs(ctypes.Structure):
                 ("pred_joints_cam", ctypes.c_void_p), ("gt_joints_cam", ctypes.c_void_p), ("pred_joints_2d", ctypes.c_void_p),
                 ("gt_joints_2d", ctypes.c_void_p), ("joints_mask", ctypes.c_void_p), ("loss_result", ctypes.c_void_p),
                 ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t)]
+
+
+class HmvEvalBreakdownArgs(ctypes.Structure):
+    """hmv_eval_breakdown_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("thr_min", ctypes.c_float), ("thr_max", ctypes.c_float),
+                ("pred_joints_cam", ctypes.c_void_p), ("gt_joints_cam", ctypes.c_void_p), ("pred_joints_2d", ctypes.c_void_p),
+                ("gt_joints_2d", ctypes.c_void_p), ("joints_mask", ctypes.c_void_p), ("view_present", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t), ("records", ctypes.c_void_p),
+                ("record_capacity", ctypes.c_int64), ("record_base", ctypes.c_int64)]
 
 
 class HmvSeqEvalArgs(ctypes.Structure):
@@ -164,6 +175,12 @@ def load() -> ctypes.CDLL:
     lib.hmv_eval_add.restype = ctypes.c_int
     lib.hmv_eval_add_views.argtypes = [ci, ctypes.POINTER(HmvEvalArgs), fp, vp]
     lib.hmv_eval_add_views.restype = ctypes.c_int
+    lib.hmv_eval_breakdown_doubles.argtypes = [ci, ci]
+    lib.hmv_eval_breakdown_doubles.restype = ctypes.c_size_t
+    lib.hmv_eval_record_floats.argtypes = [ci]
+    lib.hmv_eval_record_floats.restype = ctypes.c_size_t
+    lib.hmv_eval_breakdown_add.argtypes = [ci, ctypes.POINTER(HmvEvalBreakdownArgs), vp]
+    lib.hmv_eval_breakdown_add.restype = ctypes.c_int
     lib.hmv_forward_frames_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, ci, ci, fp, fp, ctypes.POINTER(ctypes.c_float),
                                              ctypes.POINTER(ctypes.c_float), fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames_views.restype = ctypes.c_int

@@ -20,6 +20,13 @@ view-dependent quantity on such a batch is the mean over its samples of the valu
 present views, so the epoch value again does not depend on the cut into batches and ranks; for a full mask it is the uniform value.
 ``view_mask_from_joints`` derives the mask from the ``joints_img_mask`` a reference batch already carries.
 
+The breakdown.  ``EpochEvaluator(model, mode, breakdown=True, records=n)`` enqueues one more launch per step
+(``hmv_eval_breakdown_add``) on the same tensors: a second fp64 state that keeps the same errors apart per joint and per camera, and
+up to ``n`` fp32 record rows, one per sample in feed order.  The pooled state is byte for byte what it is without the switch;
+``reduce()`` stays one collective (both states live in one tensor), ``compute()`` one copy, ``records()`` one more.  A camera's
+value on ragged steps is the plain mean over the samples that had the camera -- not the pooled value's mean over samples of
+per-sample means.  Records stay on their rank.
+
 Lightning is not a dependency of this package, so the ``_epoch`` / ``_step`` suffixes its loggers add to a key logged with both
 ``on_step`` and ``on_epoch`` cannot be pinned and are not reproduced: the keys are the names the reference passes to ``self.log``.
 """
@@ -37,6 +44,9 @@ from .losses import TERMS, _device_f32, _index, device_view_mask
 
 STEPS = 20       # thresholds of the PCK curve (handmvnet.py:359-363)
 _SCALARS = 14    # state[0 .. 14): counts and sums, then the steps + 1 histogram bins (include/handmv.h: "State layout")
+NJ = 21
+_HEADER = 4      # breakdown state[0 .. 4): samples, steps added, V, S (include/handmv.h: "evaluation breakdown")
+RECORD_KEYS = ("mpjpe", "pa_mpjpe", "mpjpe2d", "views", "mpjpe2d_per_camera")
 
 
 def view_mask_from_joints(joints_img_mask):
@@ -79,6 +89,81 @@ def finish_state(state, thr_min: float, thr_max: float, steps: int, mode: str) -
     return out
 
 
+def breakdown_doubles(views: int, steps: int) -> int:
+    """hmv_eval_breakdown_doubles on the host: header, J3, JPA, H[21][steps + 1], CN[V], C2[V][21], CV[V][21]."""
+    return _HEADER + 2 * NJ + NJ * (steps + 1) + views * (1 + 2 * NJ)
+
+
+def _breakdown_views(size: int, steps: int) -> int:
+    views, rest = divmod(size - breakdown_doubles(0, steps), 1 + 2 * NJ)
+    if views < 1 or rest:
+        raise ValueError(f"{size} elements are not a breakdown state with {steps} thresholds (4 + 42 + 21 (steps + 1) + 43 V)")
+    return views
+
+
+def merge_breakdown_states(*states) -> np.ndarray:
+    """The breakdown state of the union of several epochs, on the host: every element added but [2] and [3] (V and S), which the
+    non-empty ones must share.  (reduce() does the same on the device with one all_reduce.)"""
+    out = None
+    for st in states:
+        st = np.asarray(st, dtype=np.float64).reshape(-1)
+        if out is None:
+            out = st.copy()
+            continue
+        if st.size != out.size or (st[1] > 0 and out[1] > 0 and (st[2] != out[2] or st[3] != out[3])):
+            raise ValueError("breakdown states of different V or steps cannot be added")
+        head = out[2:4].copy() if out[1] > 0 else st[2:4].copy()
+        out += st
+        out[2:4] = head
+    if out is None:
+        raise ValueError("no state given")
+    return out
+
+
+def finish_breakdown(state, thr_min: float, thr_max: float, steps: int, mode: str) -> dict:
+    """The per-joint and per-camera numbers from a breakdown state on the host (include/handmv.h: "evaluation breakdown"); V comes
+    from its length.  Millimetres for the 3D errors, crop pixels for the 2D ones; the PCK curves and their trapezoids in fp32 like
+    finish_state.  {mode}_mpjpe2d_per_camera[_joint] divide by the samples that had the camera (a masked joint adds 0 and still
+    counts, the pooled rule), {mode}_mpjpe2d_visible_per_camera[_joint] by the unmasked joints alone; an entry whose count is 0 is
+    None.  Raises ValueError for an empty epoch, a length that is no state's, or a header that names another V or steps."""
+    s = np.asarray(state, dtype=np.float64).reshape(-1)
+    V = _breakdown_views(s.size, steps)
+    if not s[0] > 0:
+        raise ValueError("empty epoch: no step was added")
+    if s[2] != V or s[3] != steps:
+        raise ValueError(f"this breakdown state was accumulated with V = {s[2]:g}, steps = {s[3]:g}, not V = {V}, steps = {steps}")
+    at = _HEADER
+    j3, jpa = s[at:at + NJ], s[at + NJ:at + 2 * NJ]
+    at += 2 * NJ
+    hist = s[at:at + NJ * (steps + 1)].reshape(NJ, steps + 1)
+    at += NJ * (steps + 1)
+    cn, c2, cv = s[at:at + V], s[at + V:at + V + V * NJ].reshape(V, NJ), s[at + V + V * NJ:].reshape(V, NJ)
+    thr = torch.linspace(thr_min, thr_max, steps).numpy()                       # fp32, as metrics.py:106 builds them
+    pck = np.cumsum(hist[:, :steps], axis=1).astype(np.float32) / np.float32(s[0])
+    auc = np.zeros(NJ, np.float32)                                               # fp32 trapezoid (metrics.py:114-121)
+    for i in range(1, steps):
+        auc += (thr[i] - thr[i - 1]) * (pck[:, i] + pck[:, i - 1]) * np.float32(0.5)
+
+    def over(total, count):
+        return float(total / count) if count > 0 else None
+
+    return {f"{mode}_mpjpe_per_joint": (j3 / s[0] * 1000).tolist(), f"{mode}_pa_mpjpe_per_joint": (jpa / s[0] * 1000).tolist(),
+            f"{mode}_pck_per_joint": pck.tolist(), f"{mode}_auc_per_joint": auc.tolist(),
+            f"{mode}_mpjpe2d_per_camera": [over(c2[v].sum(), cn[v] * NJ) for v in range(V)],
+            f"{mode}_mpjpe2d_per_camera_joint": [[over(c2[v, j], cn[v]) for j in range(NJ)] for v in range(V)],
+            f"{mode}_mpjpe2d_visible_per_camera": [over(c2[v].sum(), cv[v].sum()) for v in range(V)],
+            f"{mode}_mpjpe2d_visible_per_camera_joint": [[over(c2[v, j], cv[v, j]) for j in range(NJ)] for v in range(V)],
+            "camera_samples": [int(n) for n in cn], "visible_joints": cv.astype(np.int64).tolist()}
+
+
+def worst(records: dict, key: str = "mpjpe", k: int = 10) -> list:
+    """The indices (feed order) of the k samples with the largest records[key], worst first; equal values in feed order, NaN last."""
+    values = np.asarray(records[key], dtype=np.float64)
+    if values.ndim != 1:
+        raise ValueError(f"records[{key!r}] has one value per camera; pass one column of it")
+    return np.argsort(-values, kind="stable")[:max(int(k), 0)].tolist()
+
+
 class EpochEvaluator:
     """Accumulates evaluation steps of `model` (a HandMvNet) on the device; see the module docstring for the epoch value.
 
@@ -88,20 +173,50 @@ class EpochEvaluator:
         numbers = ev.compute()
 
     The state lives on the device of the first step (a zeroed fp64 tensor of hmv_eval_state_doubles(20) elements) and belongs to
-    the stream the steps run on."""
+    the stream the steps run on.
 
-    def __init__(self, model, mode: str = "test"):
+    breakdown=True: every step also runs hmv_eval_breakdown_add, and compute() adds finish_breakdown's keys.  records=n > 0: that
+    launch also fills one record row per sample, up to n on this rank, read with records(); the launch runs for them even with
+    breakdown=False.  Every step must then have the V of the first (ValueError otherwise, before anything is launched), and the
+    two states are the two ends of ONE tensor, so that reduce() stays one collective."""
+
+    def __init__(self, model, mode: str = "test", breakdown: bool = False, records: int = 0):
         self.model, self.mode = model, mode
         self.thr_min, self.thr_max = float(model.auc_thresh[0]), float(model.auc_thresh[1])
         self.state_doubles = int(_lib.load().hmv_eval_state_doubles(STEPS))
         self.state: Optional[torch.Tensor] = None
+        if int(records) < 0:
+            raise ValueError("records must be >= 0")
+        self.breakdown, self.record_capacity = bool(breakdown), int(records)
+        self._detail = self.breakdown or self.record_capacity > 0        # the breakdown launch runs
+        self.views: Optional[int] = None                                 # V of the breakdown state
+        self.breakdown_state: Optional[torch.Tensor] = None
+        self.record_table: Optional[torch.Tensor] = None                 # fp32 [records][4 + V], NaN until a row is written
+        self.record_rows = 0                                             # samples fed so far, counted on the host
+        self._both: Optional[torch.Tensor] = None
 
-    def _state_on(self, dev: torch.device) -> torch.Tensor:
+    def _state_on(self, dev: torch.device, views: Optional[int] = None) -> torch.Tensor:
         if self.state is None:
-            self.state = torch.zeros(self.state_doubles, device=dev, dtype=torch.float64)
+            if not self._detail:
+                self.state = torch.zeros(self.state_doubles, device=dev, dtype=torch.float64)
+            else:
+                if views is None:
+                    raise ValueError("the breakdown state is sized by V: a rank that saw no batch needs a model with num_views")
+                self.views = int(views)
+                self._both = torch.zeros(self.state_doubles + breakdown_doubles(self.views, STEPS), device=dev, dtype=torch.float64)
+                self.state, self.breakdown_state = self._both[:self.state_doubles], self._both[self.state_doubles:]
+                if self.record_capacity:
+                    self.record_table = torch.full((self.record_capacity, 4 + self.views), float("nan"), device=dev)
         elif self.state.device != dev:
             raise ValueError(f"this epoch's state is on {self.state.device}, the step on {dev}")
         return self.state
+
+    def _check_detail(self, B: int, V: int) -> None:
+        """What the breakdown launch would refuse or cannot see, in front of every launch of the step."""
+        if self.views is not None and V != self.views:
+            raise ValueError(f"this epoch's breakdown was begun with {self.views} views, the step has {V}")
+        if self.record_capacity and self.record_rows + B > self.record_capacity:
+            raise ValueError(f"{self.record_rows} + {B} samples do not fit the {self.record_capacity} record rows of this evaluator")
 
     def add(self, out: dict, inputs: dict, cam_params, view_mask=None) -> None:
         """One step from the forward's `out` and the labels as _eval_step passes them (joints_cam / root_joint in metres): the loss
@@ -119,6 +234,8 @@ class EpochEvaluator:
         if p2.dim() != 4 or p2.shape[0] != B or tuple(p2.shape[2:]) != (21, 2) or g2.shape != p2.shape:
             raise ValueError(f"joints_crop_img must be [{B}, V, 21, 2] in the output and in the labels")
         V = p2.shape[1]
+        if self._detail:
+            self._check_detail(B, V)
         keep = [pc, p2, gc, g2]
         a = _lib.HmvEvalArgs()
         a.struct_size = ctypes.sizeof(_lib.HmvEvalArgs)
@@ -136,9 +253,10 @@ class EpochEvaluator:
             loss = self.model.last_loss_vector
             a.loss_result = loss.data_ptr()
             keep.append(loss)
-        state = self._state_on(dev)
+        state = self._state_on(dev, V)
         a.state, a.state_doubles = state.data_ptr(), state.numel()
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        present = None
         with torch.cuda.device(dev):
             if view_mask is None:
                 rc = _lib.load().hmv_eval_add(_index(dev), ctypes.byref(a), stream)
@@ -146,7 +264,19 @@ class EpochEvaluator:
                 present = device_view_mask(view_mask, B, V, dev)
                 keep.append(present)
                 rc = _lib.load().hmv_eval_add_views(_index(dev), ctypes.byref(a), present.data_ptr(), stream)
-        _lib.check(rc)
+            _lib.check(rc)
+            if self._detail:   # the same tensors, the same stream, right behind the pooled launch
+                d = _lib.HmvEvalBreakdownArgs()
+                d.struct_size = ctypes.sizeof(_lib.HmvEvalBreakdownArgs)
+                d.B, d.V, d.steps, d.thr_min, d.thr_max = B, V, STEPS, self.thr_min, self.thr_max
+                d.pred_joints_cam, d.gt_joints_cam, d.pred_joints_2d, d.gt_joints_2d = a.pred_joints_cam, a.gt_joints_cam, a.pred_joints_2d, a.gt_joints_2d
+                d.joints_mask = a.joints_mask
+                d.view_present = None if present is None else present.data_ptr()
+                d.state, d.state_doubles = self.breakdown_state.data_ptr(), self.breakdown_state.numel()
+                if self.record_table is not None:
+                    d.records, d.record_capacity, d.record_base = self.record_table.data_ptr(), self.record_capacity, self.record_rows
+                _lib.check(_lib.load().hmv_eval_breakdown_add(_index(dev), ctypes.byref(d), stream))
+                self.record_rows += B
         del keep   # allocated on the stream the kernel runs on: the caching allocator reuses them in stream order
 
     def step(self, batch: dict) -> dict:
@@ -171,18 +301,46 @@ class EpochEvaluator:
         """One all_reduce(SUM) of the state over `group`: afterwards every rank holds the global sums.  A rank that saw no batch
         takes part with a zero state."""
         if self.state is None:
-            self._state_on(torch.device("cuda", torch.cuda.current_device()))
-        reduce_state(self.state, group)
+            self._state_on(torch.device("cuda", torch.cuda.current_device()), getattr(self.model, "num_views", None))
+        if not self._detail:
+            reduce_state(self.state, group)
+            return
+        reduce_state(self._both, group)          # both states in one collective; records stay on their rank
+        self.breakdown_state[2].fill_(float(self.views))   # V and S are not sums (include/handmv.h)
+        self.breakdown_state[3].fill_(float(STEPS))
 
     def compute(self) -> dict:
         """ONE device->host copy of the state, the rest on the host (finish_state).  {mode}_mpjpe / {mode}_pa_mpjpe in millimetres,
         {mode}_mpjpe2d in crop pixels, {mode}_pck_j (list), {mode}_auc_j, {mode}_norm_auc_j, thresholds (list), {mode}/heatmap_loss
         ... {mode}/p2d_loss, {mode}/root_3d_loss, {mode}/loss (None when no step carried a loss), samples, steps.
         Raises ValueError for an empty epoch."""
-        host = np.zeros(self.state_doubles) if self.state is None else self.state.cpu().numpy()
-        return finish_state(host, self.thr_min, self.thr_max, STEPS, self.mode)
+        if not self.breakdown:
+            host = np.zeros(self.state_doubles) if self.state is None else self.state.cpu().numpy()
+            return finish_state(host, self.thr_min, self.thr_max, STEPS, self.mode)
+        if self.state is None:
+            raise ValueError("empty epoch: no step was added")
+        host = self._both.cpu().numpy()           # still ONE copy: the two states are one tensor
+        out = finish_state(host[:self.state_doubles], self.thr_min, self.thr_max, STEPS, self.mode)
+        out.update(finish_breakdown(host[self.state_doubles:], self.thr_min, self.thr_max, STEPS, self.mode))
+        return out
+
+    def records(self) -> dict:
+        """ONE device->host copy of the record rows filled so far, in feed order, as numpy arrays: mpjpe and pa_mpjpe [n] in
+        millimetres, mpjpe2d [n] in crop pixels (the sample's own value over its present views), views [n] (int), and
+        mpjpe2d_per_camera [n, V] with NaN for an absent camera.  This rank's samples only."""
+        if not self.record_capacity:
+            raise ValueError("this evaluator was built with records=0")
+        n = min(self.record_rows, self.record_capacity)
+        rows = np.zeros((0, 4 + (self.views or 0))) if self.record_table is None else self.record_table[:n].cpu().numpy().astype(np.float64)
+        return {"mpjpe": rows[:, 0] * 1000, "pa_mpjpe": rows[:, 1] * 1000, "mpjpe2d": rows[:, 2].copy(), "views": rows[:, 3].astype(np.int64),
+                "mpjpe2d_per_camera": rows[:, 4:].copy()}
 
     def reset(self) -> None:
         """An empty epoch again (a zero state is one)."""
-        if self.state is not None:
+        if self._both is not None:
+            self._both.zero_()
+        elif self.state is not None:
             self.state.zero_()
+        if self.record_table is not None:
+            self.record_table.fill_(float("nan"))
+        self.record_rows = 0

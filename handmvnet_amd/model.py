@@ -502,21 +502,27 @@ class HandMvNet(torch.nn.Module):
         """handmvnet.py:493-517: metric keys carry the "test_" prefix."""
         return self._eval_step(batch, "test")
 
-    def evaluate(self, batches, mode: str = "test", group=None) -> dict:
+    def evaluate(self, batches, mode: str = "test", group=None, breakdown: bool = False, records: int = 0) -> dict:
         """What trainer.test(model, dm) / trainer.validate hand back (eval.py): the epoch's numbers over every batch of `batches`.
         Each step enqueues forward, loss and one accumulation launch and copies nothing to the host; one all-reduce combines the ranks
         when a process group is initialised; one readback ends the epoch.  Every value is sum(B x step value) / sum(B) over steps and
         ranks -- Lightning's on_epoch mean, and for MPJPE, PA-MPJPE, 2D MPJPE and the PCK curve the value on the pooled split
         (handmvnet_amd/evaluation.py).  Like test_step, converts each batch's joints_cam / root_joint from mm to metres in place.
         A batch that carries batch["view_mask"] (bool [B, V], True = present; on the host) is a ragged view set: forward_views, the
-        ragged loss and the ragged accumulation, at the cost of its present frames; ragged and uniform batches may be mixed."""
+        ragged loss and the ragged accumulation, at the cost of its present frames; ragged and uniform batches may be mixed.
+        breakdown=True adds the per-joint and per-camera tables (evaluation.finish_breakdown's keys) at one more launch per step,
+        reduced in the same collective; records=n > 0 adds "records": one row per sample of THIS rank in feed order, at most n
+        (EpochEvaluator.records; evaluation.worst picks the worst of them).  With the defaults the result is what it always was."""
         from .evaluation import EpochEvaluator
-        ev = EpochEvaluator(self, mode)
+        ev = EpochEvaluator(self, mode, breakdown=breakdown, records=records)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             ev.reduce(group)
-        return ev.compute()
+        out = ev.compute()
+        if records > 0:
+            out["records"] = ev.records()
+        return out
 
     def evaluate_subsets(self, batches, subsets, mode: str = "test", group=None) -> dict:
         """evaluate() for S camera subsets in one pass over `batches` (full-view batches, no view_mask): per step one forward_subsets

@@ -663,6 +663,74 @@ int hmv_eval_add(int32_t device, const hmv_eval_args *args, void *stream);
  * bits, and ragged and uniform steps may be mixed in one epoch. */
 int hmv_eval_add_views(int32_t device, const hmv_eval_args *args, const uint8_t *view_present, void *stream);
 
+/* ---- evaluation breakdown (the epoch's errors kept apart by joint, by camera and by sample) ----
+ * hmv_eval_breakdown_add adds the step that hmv_eval_add / hmv_eval_add_views pooled -- same tensors, same stream -- into a SECOND
+ * caller-owned fp64 state, and optionally writes one fp32 record row per sample.  The pooled state and its entries are untouched by
+ * it.  Every number is the reference's PoseMetrics.mpjpe / compute_similarity_transform / pck / mask_joints applied to one joint
+ * column or one camera slice.
+ *
+ * State layout: hmv_eval_breakdown_doubles(V, steps) = 4 + 42 + 21 (S + 1) + 43 V doubles, S = steps, every slice a sum over the
+ * steps added:
+ *   [0]   samples, sum of B            [1]   steps added
+ *   [2]   V        [3]   S             written by the first add (the one that finds [1] == 0), not added to afterwards: a state is
+ *                                      additive only with one of the same V and S, and whoever sums two states keeps [2] and [3]
+ *   J3  [21]          per joint: sum over samples of the fp32 3D distance (metres)
+ *   JPA [21]          per joint: sum of the distance that remains after the pose's similarity alignment (the fp64 arithmetic of [4]
+ *                     of the pooled state)
+ *   H   [21][S + 1]   per joint: the PCK histogram bins of the pooled state's [14 ..], integer-valued; summed over the joints they
+ *                     are that histogram
+ *   CN  [V]           per camera: samples in which it is present
+ *   C2  [V][21]       per camera and joint: sum over its present slots of the 2D distance, a masked joint zeroed on both sides and
+ *                     adding 0 (the pooled state's rule for [6])
+ *   CV  [V][21]       per camera and joint: present slots in which the joint is NOT masked; CN[v] without a joint mask
+ * C2[v] / CN[v] is the camera's 2D MPJPE under the masking rule, C2[v][j] / CV[v][j] the error over the visible joints alone.
+ * A ragged step (view_present not NULL) adds each PRESENT slot unweighted and does not read an absent one: the value of a camera is
+ * the one over the samples that had this camera.  That is deliberately not the V / v_b weighting of the pooled [6], which is a mean
+ * over samples; the sum of C2 equals [6] only for steps with every view.
+ *
+ * Record row of sample b: hmv_eval_record_floats(V) = 4 + V floats at records[(record_base + b) * (4 + V)]
+ *   [0]   the mean of its 21 fp32 3D distances (metres)      [1]   that mean after its similarity alignment
+ *   [2]   its 2D MPJPE over its present views and 21 joints under the masking rule (the per-sample value of the ragged convention);
+ *         NaN for a sample without a present view, which is a broken precondition as for hmv_eval_add_views -- nothing is indexed
+ *         by a count
+ *   [3]   v_b, its present views
+ *   [4 + v]   camera v's 2D error over the 21 joints; NaN when the camera is absent
+ * each the fp64 mean of fp32 distances, rounded to fp32 once.  The caller counts samples on the host and passes the row of this
+ * step's sample 0, so nothing is read back to place a row; rows outside record_base .. record_base + B - 1 are not touched.
+ *
+ * One launch of 2 + V workgroups (3 + V with records), each the only writer of its slice: fp32 where the reference compares, fp64
+ * sums and Procrustes, every sum in a fixed order, no floating-point atomics -- two identical epochs give identical bits in state and
+ * records.  Like the pooled state, this one belongs to one stream at a time, and a zero-filled buffer is an empty epoch.  The V of a
+ * later step cannot be compared with [2] without a synchronisation, so it is not: the caller keeps V and steps the same. */
+typedef struct hmv_eval_breakdown_args {
+    int32_t struct_size;            /* sizeof(hmv_eval_breakdown_args), ABI guard */
+    int32_t B, V;                   /* samples, views */
+    int32_t steps;                  /* PCK thresholds, 1 .. 256 */
+    float thr_min, thr_max;         /* thr_min <= thr_max, the units of joints_cam */
+    const float *pred_joints_cam;   /* as in hmv_eval_args, all five */
+    const float *gt_joints_cam;
+    const float *pred_joints_2d;
+    const float *gt_joints_2d;
+    const uint8_t *joints_mask;     /* may be NULL */
+    const uint8_t *view_present;    /* device uint8 [B][V], non-zero = the view is there; NULL: every view is present */
+    double *state;                  /* device, 8-byte aligned */
+    size_t state_doubles;           /* >= hmv_eval_breakdown_doubles(V, steps) */
+    float *records;                 /* device fp32 [record_capacity][4 + V]; may be NULL: no records, the next two are ignored */
+    int64_t record_capacity;        /* rows */
+    int64_t record_base;            /* the row of this step's sample 0 */
+} hmv_eval_breakdown_args;
+
+/* Doubles in a breakdown state: 4 + 42 + 21 (steps + 1) + 43 V (831 for V = 8, steps = 20); 0 for V < 1 or steps outside 1 .. 256. */
+size_t hmv_eval_breakdown_doubles(int32_t V, int32_t steps);
+
+/* Floats in one record row: 4 + V; 0 for V < 1. */
+size_t hmv_eval_record_floats(int32_t V);
+
+/* Adds one step, asynchronously on `stream`.  Every argument is checked before any HIP call, with hmv_eval_add's rules and texts;
+ * further HMV_ERR_ARG, with nothing launched: state_doubles too small, and with records a misaligned pointer, record_capacity < 1,
+ * record_base < 0 or a last sample that would land at record_base + B > record_capacity. */
+int hmv_eval_breakdown_add(int32_t device, const hmv_eval_breakdown_args *args, void *stream);
+
 /* ---- sequence evaluation (a followed sequence, hmv_forward_frames_track: labels in the tracker's windows, jitter, window quality) ----
  * Under a tracker the windows are the tracker's own, so 2D labels expressed in dataset boxes do not belong to the predictions.  The
  * three entries below keep the evaluation of such a sequence on the device.  Stateless like the metrics, loss and track entries: a

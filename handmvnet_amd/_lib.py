@@ -19,7 +19,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
-           "hmv_eval_breakdown_add"]
+           "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -203,6 +203,10 @@ def load() -> ctypes.CDLL:
     lib.hmv_seq_eval_history_floats.restype = ctypes.c_size_t
     lib.hmv_seq_eval_add.argtypes = [ci, ctypes.POINTER(HmvSeqEvalArgs), vp]
     lib.hmv_seq_eval_add.restype = ctypes.c_int
+    lib.hmv_op_hand_ik.argtypes = [ci, fp, fp, ci, fp, fp, fp, fp, vp]
+    lib.hmv_op_hand_ik.restype = ctypes.c_int
+    lib.hmv_op_rigid_unapply.argtypes = [ci, fp, fp, ci, ci, fp, vp]
+    lib.hmv_op_rigid_unapply.restype = ctypes.c_int
     lib.hmv_op_prepare_frames.argtypes = [ci, fp, ci, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                           ci, ci, fp, vp]
     lib.hmv_op_prepare_frames.restype = ctypes.c_int

@@ -382,6 +382,21 @@ struct TrackParams {
 };
 hipError_t launch_next_crop_boxes(const TrackParams &p, hipStream_t s);
 
+// Hand pose parameters from 21 joints (hand_ik.hip; hmv_op_hand_ik / hmv_op_rigid_unapply in handmv.h): one wave64 per sample.
+// aligned may be null; every other pointer is required.
+struct HandIkParams {
+    const float *joints;   // [n][21][3]
+    const float *tmpl;     // [21][3]
+    long n;
+    float *pose_R;         // [n][16][3][3]
+    double *align;         // [n][12]: R row-major, t
+    float *aligned;        // [n][21][3]
+    int *status;           // [n]
+};
+hipError_t launch_hand_ik(const HandIkParams &p, hipStream_t s);
+// out[i] = R_i^T (points[i] - t_i) over [n][n_pts][3]; out may be points
+hipError_t launch_rigid_unapply(const float *points, const double *align, long n, int n_pts, float *out, hipStream_t s);
+
 // Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
 void set_thread_error(const std::string &msg);
 

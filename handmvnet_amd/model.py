@@ -44,6 +44,8 @@ class HandMvNet(torch.nn.Module):
         self.pos_enc_list = list(self.cfg.pos_enc)
         self.fusion_layers = self.cfg.fusion_layers
         self.get_vertices = model_params.get("get_vertices", False)
+        # get_vertices: the caller's handmvnet_amd.ik.JointsToVertices (it owns the MANO layer); unset, the vertex metrics are refused
+        self.joints_to_vertices = None
         # handmvnet.py:117-125 (config_from_params has already rejected unknown dataset names)
         self.auc_thresh = {"dexycb": [0.0, 0.02], "ho3d": [0.0, 0.05], "mvhand": [0.0, 0.02]}[data_params.get("name", "dexycb")]
         self.example_input_array = {  # handmvnet.py:110-115 ("just for summary")
@@ -414,7 +416,8 @@ class HandMvNet(torch.nn.Module):
         return mpjpe * scale, pa_mpjpe * scale, auc, norm_auc, pck_values, thresholds
 
     def _calculate_mpjpe(self, out, inputs, mode="train", view_mask=None):
-        """handmvnet.py:370-427 without the Lightning logging; the MANO vertex metrics need manopth (absent).
+        """handmvnet.py:370-427 without the Lightning logging; the MANO vertex metrics (get_vertices) need self.joints_to_vertices,
+        the caller's ik.JointsToVertices around their MANO layer (manopth and the MANO files are not part of this package).
         view_mask (bool [B, V], True = present): {mode}_mpjpe2d is the mean over samples of each sample's own 2D MPJPE over its present
         views (masked joints zeroed on both sides as ever); rows of absent views do not enter, whatever they hold."""
         from .metrics import PoseMetrics
@@ -435,7 +438,14 @@ class HandMvNet(torch.nn.Module):
                        f"{mode}_pa_mpjpe": pa_mpjpe, f"{mode}_pck_j": pck_values_j, f"{mode}_auc_j": auc_j,
                        f"{mode}_norm_auc_j": norm_auc_j}
         if self.get_vertices:
-            raise NotImplementedError("get_vertices needs manopth + MANO assets (joints_to_vertices.py:14-23), absent here")
+            if self.joints_to_vertices is None:
+                raise NotImplementedError("get_vertices needs manopth + MANO assets (joints_to_vertices.py:14-23), absent here")
+            # handmvnet.py:390-408, the per-sample host loop as one batched device call (handmvnet_amd/ik.py)
+            out["vertices"] = self.joints_to_vertices(out["joints_cam"] * 1000)
+            gt_v = inputs["vertices"].to(out["vertices"].device)
+            mpvpe, pa_mpvpe, auc_v, norm_auc_v, pck_values_v, _ = self._get_metrics(out["vertices"] / 1000., gt_v / 1000.)
+            out_metrics.update({f"{mode}_mpvpe": mpvpe, f"{mode}_pa_mpvpe": pa_mpvpe, f"{mode}_pck_v": pck_values_v,
+                                f"{mode}_auc_v": auc_v, f"{mode}_norm_auc_v": norm_auc_v})
         return out_metrics
 
     def _calculate_loss(self, out, inputs, cam_params, mode="train", view_mask=None):

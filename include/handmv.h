@@ -815,6 +815,46 @@ size_t hmv_seq_eval_history_floats(int32_t B);
  * pred_joints_cam, a NULL or misaligned sums / history, sums_doubles / history_floats below what the sizing entries give. */
 int hmv_seq_eval_add(int32_t device, const hmv_seq_eval_args *args, void *stream);
 
+/* ---- hand IK: pose parameters from 21 joints ----
+ * Everything the reference's JointsToVertices.__call__ (models/joints_to_vertices.py:25-50) does around its MANO layer, per sample and
+ * on the host there, as two stateless device entries (hand_ik.hip).  The MANO layer itself is the caller's (handmvnet_amd/ik.py).
+ *
+ * hmv_op_hand_ik: the three-point rigid alignment onto the template (rigid_transform_3D, utils/misc.py:10-47, on joints 0, 9, 13 of
+ * both sides as joints_to_vertices.py:27-39 calls it) and the analytic inverse kinematics (adaptive_IK, utils/analytical_ik.py:50-138).
+ *   joints           [n][21][3] fp32, the prediction in millimetres (joints_cam * 1000, handmvnet.py:396)
+ *   template_joints  [21][3] fp32, the flat-hand template of the caller's MANO layer in its units; one template for every sample
+ *   pose_R           [n][16][3][3] fp32: slot 0 = R[0], slot ID2ROT[k] = R_pa_k[k] (analytical_ik.py:132-136); every slot is written
+ *   align            [n][12] fp64: ret_R row-major, then ret_t (fp64 because the reference keeps them in float64 for the un-alignment)
+ *   joints_aligned   [n][21][3] fp32 or NULL: joints_to_mano (joints_to_vertices.py:39)
+ *   status           [n] int32
+ * fp64 arithmetic from the fp32 inputs in the reference's operation order, no fused multiply-add; outputs rounded once.
+ *   alignment: centroids, H = Am Bm^T, R = V U^T; det(R) < 0: the last row of V^T negated and R recomputed; t = -R cA + cB.  H has rank
+ *     2, the signs of the third singular vectors are arbitrary, and the determinant rule is what makes R unique: a proper rotation.
+ *   global rotation: H from the five palm vectors (joints 1, 5, 9, 13, 17 minus joint 0) of the template and of the aligned joints,
+ *     R0 = V U^T, then THE REFERENCE'S reflection rule, which is not the textbook one: the last column of V is negated only when
+ *     |det R0 + 1| < 1e-6 AND some |S_i| < 1e-4.  A mirrored (left) hand with a non-planar palm keeps a reflection as R0.
+ *   chain: the 15 joints of kinematic_tree with SNAP_PARENT as parents, the + 1e-8 terms where the reference has them, acos of the
+ *     unclamped cosine, D_sw = the Rodrigues matrix of transforms3d's axangle2mat(axis, angle, is_normalized=False) (the axis divided by
+ *     its norm once more; rows [xxC+c, xyC-zs, zxC+ys], [xyC+zs, yyC+c, yzC-xs], [zxC-ys, yzC+xs, zzC+c]), D_tw the same function of the
+ *     template bone and angle 0, R_pa_k = D_sw D_tw, R[k] = R[pa] R_pa_k.  inv(R[pa]) is the transpose: R[pa] is R0 times Rodrigues
+ *     matrices, orthogonal by construction, a reflection R0 included.
+ * status 0: the normal case.
+ * status 1: some written value (pose_R, align, joints_aligned whether or not it is requested) is non-finite: a non-finite input, a
+ *           target bone exactly collinear with its template bone, coincident points, a cosine above 1, a zero template bone.  The
+ *           reference produces NaN there too; the values are written as computed, nothing is repaired.
+ * One wave64 per sample, four samples per workgroup; the two SVDs on one lane, the five fingers on five; no LDS, no atomics.  Row i of
+ * an n-row call has the bits of a one-row call.  Outputs must not alias inputs.  Takes no handle; asynchronous on `stream`.
+ * HMV_ERR_ARG before any HIP call (hmv_last_error(NULL) names the argument) for n <= 0, a NULL joints / template_joints / pose_R /
+ * status, a NULL or misaligned align. */
+int hmv_op_hand_ik(int32_t device, const float *joints, const float *template_joints, int32_t n, float *pose_R, double *align,
+                   float *joints_aligned, int32_t *status, void *stream);
+
+/* The inverse of that alignment on any points (joints_to_vertices.py:48: the MANO vertices back to where the joints were):
+ *   out[i][p] = R_i^T (points[i][p] - t_i)   with (R_i, t_i) = align[i], in fp64, rounded once to fp32
+ *   points, out  [n][n_pts][3] fp32, may be the same buffer;   align [n][12] fp64 as hmv_op_hand_ik wrote it
+ * HMV_ERR_ARG before any HIP call for n <= 0, n_pts <= 0, a NULL points / out, a NULL or misaligned align. */
+int hmv_op_rigid_unapply(int32_t device, const float *points, const double *align, int32_t n, int32_t n_pts, float *out, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

@@ -1497,12 +1497,13 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
 #undef HMV_RD
     }
     if (dense) {
-        if (p.Cin % epc != 0 || p.lda % epc != 0 || generic || p.Kpad > (1 << 16)) return hipErrorInvalidValue;
+        // (fp16 rows that are no whole 16-byte vectors -- Cout % 8 != 0, the op-level entries only -- take the staged epilogue below)
+        if (p.Cin % epc != 0 || p.lda % epc != 0 || (generic && !p.in_f16) || p.Kpad > (1 << 16)) return hipErrorInvalidValue;
         p.cpt = (p.x3_plane ? p.x3_plane : p.Cin) / epc;   // 16-byte vectors per tap (of one plane in the fused split loop)
         p.cpt_magic = p.cpt > 1 ? (unsigned)(0xFFFFFFFFu / (unsigned)p.cpt) + 1u : 0u;
         p.s_magic = p.S > 1 ? (unsigned)(0xFFFFFFFFu / (unsigned)p.S) + 1u : 0u;
         if (p.up && (p.R != 1 || p.S != 1 || p.pad_h || p.pad_w || p.stride != 1)) return hipErrorInvalidValue;
-        tile = conv_dense_tile(tile, p.in_f16 != 0);
+        tile = generic ? TILE_128x128 : conv_dense_tile(tile, p.in_f16 != 0);
     }
     // fp16 3x3 stride-1 pad-1 convs on 256 x 256 tiles: 16 x 16 pixel blocks with the halo image in LDS (MODE_HALO)
     static const bool halo = HMV_DEV_ENV("HMV_NO_HALO") == nullptr;   // development knob: HMV_NO_HALO=1 keeps the nine-fetch MODE_TAPS loop (A/B runs)
@@ -1539,6 +1540,7 @@ hipError_t launch_conv(ConvParams p, ConvTile tile, hipStream_t s, const char **
             // 129 .. 192 output channels (HRNet-w40's 160-channel branch): ONE 192-wide N-tile instead of two 128-wide ones whose
             // second is three quarters padding (6 instead of 8 MFMA column blocks per pixel block)
             static const bool no192 = HMV_DEV_ENV("HMV_NO_N192") != nullptr;   // development knob (A/B runs)
+            if (generic) return launch_one<_Float16, 128, 128, 2, 2, MODE_DENSE, true, 64>(p, s);
             if (tile == TILE_256x128 && p.Cout > 128 && p.Cout <= 192 && !generic && !no192) {
                 // (128 x 192 tiles, two 4-wave workgroups per CU, measured 28 % slower on the one-round launches of HRNet-w40: 3.82 vs 2.98 ms)
                 if (name) *name = "conv_igemm_f16<256x192,dense>";

@@ -2884,11 +2884,11 @@ int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, 
     void *pairs = nullptr;
     RangeWord rw;
     hipError_t e = rw.alloc();
-    if (e == hipSuccess) e = hipMalloc(&pairs, (size_t)B * T * 3072 * 4);
+    if (e == hipSuccess) e = op_guarded_alloc(&pairs, (size_t)B * T * 3072 * 4, s);
     if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, (size_t)B * T, 3072, 2, s, rw.p);
     if (e == hipSuccess) e = launch_attention(static_cast<const float *>(pairs), B, T, Tq, koff, Tk, out, s, 0, 1, rw.p);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (pairs) (void)hipFree(pairs);
+    op_guarded_free(pairs);
     if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
     if (rw.saturated()) { g_create_err = "hmv_op_attention_x3: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
     return HMV_OK;
@@ -2929,7 +2929,7 @@ int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const
     if (e == hipSuccess) e = hipMemcpy(seg, seg_host, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && kind == 1) {   // the kernel takes rows of (hi, lo) fp16 pairs: split the fp32 rows first (hmv_op_attention_x3)
         e = rw.alloc();
-        if (e == hipSuccess) e = hipMalloc(&pairs, rows * 3072 * 4);
+        if (e == hipSuccess) e = op_guarded_alloc(&pairs, rows * 3072 * 4, s);
         if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, rows, 3072, 2, s, rw.p);
         if (e == hipSuccess) e = launch_attention_views(static_cast<const float *>(pairs), B, seg, Tmax, cross, out, s, 0, 1, rw.p);
     } else if (e == hipSuccess && kind == 0) {
@@ -2939,7 +2939,7 @@ int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const
         else e = launch_attention_d256_views(qkv, 6144, 1, qkv + 2048, qkv + 4096, 6144, B, seg, Tmax, out, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (pairs) (void)hipFree(pairs);
+    op_guarded_free(pairs);
     if (seg) (void)hipFree(seg);
     if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
     if (kind == 1 && rw.saturated()) { g_create_err = "hmv_op_attention_views: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
@@ -3000,7 +3000,7 @@ int hmv_op_attention_probs(int32_t device, int32_t kind, const float *qkv, const
     if (e == hipSuccess && n) {
         if (kind == 1) {   // the kernel takes rows of (hi, lo) fp16 pairs: split the fp32 rows first (hmv_op_attention_x3)
             e = rw.alloc();
-            if (e == hipSuccess) e = hipMalloc(&pairs, rows * 3072 * 4);
+            if (e == hipSuccess) e = op_guarded_alloc(&pairs, rows * 3072 * 4, s);
             if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, rows, 3072, 2, s, rw.p);
             if (e == hipSuccess) e = launch_attention_probs(1, pairs, 6144, static_cast<const _Float16 *>(pairs) + 1024, 6144, B, pr, probs, s);
         } else if (kind == 0) {
@@ -3017,7 +3017,7 @@ int hmv_op_attention_probs(int32_t device, int32_t kind, const float *qkv, const
         else e = hipMemsetAsync(view_share, 0, ns * sizeof(float), s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (pairs) (void)hipFree(pairs);
+    op_guarded_free(pairs);
     if (seg) (void)hipFree(seg);
     if (e != hipSuccess) { g_create_err = std::string("attention map launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
     if (kind == 1 && rw.saturated()) { g_create_err = "hmv_op_attention_probs: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
@@ -3080,8 +3080,8 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
     if (rc == HMV_OK && e == hipSuccess && half) {   // fp16 rows, or (hi, lo) pairs in HMV_F32X3
         const int mode = dtype == HMV_F32X3 ? 2 : 1;
         const size_t rows_in = (size_t)N * H * W, rows_out = (size_t)N * Ho * Wo;
-        e = hipMalloc(&din, rows_in * Cin * 2 * mode);
-        if (e == hipSuccess && residual) e = hipMalloc(&dres, rows_out * Cout * 2 * mode);
+        e = op_guarded_alloc(&din, rows_in * Cin * 2 * mode, s);
+        if (e == hipSuccess && residual) e = op_guarded_alloc(&dres, rows_out * Cout * 2 * mode, s);
         if (e == hipSuccess) e = launch_rows_f32_to_half(in, din, rows_in, Cin, mode, s, rw.p);
         if (e == hipSuccess && residual) e = launch_rows_f32_to_half(residual, dres, rows_out, Cout, mode, s, rw.p);
         x = din;
@@ -3097,8 +3097,8 @@ static int op_conv(const char *who, int32_t device, int32_t dtype, const float *
         rc = Rn.rc;
         if (rc == HMV_OK) e = hipStreamSynchronize(s);
     }
-    if (din) (void)hipFree(din);
-    if (dres) (void)hipFree(dres);
+    op_guarded_free(din);
+    op_guarded_free(dres);
     for (void *ptr : eng.dev_allocs) (void)hipFree(ptr);
     if (rc != HMV_OK) { g_create_err = std::string(who) + ": " + eng.err; return rc; }
     if (e != hipSuccess) { g_create_err = std::string(who) + ": " + hipGetErrorString(e); return HMV_ERR_HIP; }
@@ -3213,9 +3213,13 @@ extern "C" int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base,
     hipStream_t s = static_cast<hipStream_t>(stream);
     HrFuseParams p{};
     p.N = N; p.H = H; p.W = W; p.C = C; p.ldc = C; p.nsrc = nsrc; p.relu = relu ? 1 : 0; p.f16 = f16 ? 1 : 0;
-    std::vector<void *> owned;
-    auto fail = [&](int rc, const std::string &msg) {
+    std::vector<void *> owned, halves;   // halves: the fp16 copies the kernel reads, each framed by guard bands (op_guarded_alloc)
+    auto release = [&]() {
         for (void *q : owned) (void)hipFree(q);
+        for (void *q : halves) op_guarded_free(q);
+    };
+    auto fail = [&](int rc, const std::string &msg) {
+        release();
         g_create_err = "hmv_op_hr_fuse_up: " + msg;
         return rc;
     };
@@ -3228,8 +3232,8 @@ extern "C" int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base,
     };
     auto as_half = [&](const float *x, size_t rows, int ch) -> const void * {   // fp16 copy of fp32 rows
         void *d = nullptr;
-        if (e == hipSuccess) e = hipMalloc(&d, rows * ch * 2);
-        if (e == hipSuccess) { owned.push_back(d); e = launch_rows_f32_to_half(x, d, rows, ch, 1, s); }
+        if (e == hipSuccess) e = op_guarded_alloc(&d, rows * ch * 2, s);
+        if (e == hipSuccess) { halves.push_back(d); e = launch_rows_f32_to_half(x, d, rows, ch, 1, s); }
         return d;
     };
     for (int q = 0; q < nsrc; ++q) {
@@ -3253,6 +3257,6 @@ extern "C" int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base,
     e = launch_hr_fuse_up(p, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(HMV_ERR_HIP, hipGetErrorString(e));
-    for (void *q : owned) (void)hipFree(q);
+    release();
     return HMV_OK;
 }

@@ -210,6 +210,24 @@ hipError_t launch_maxpool3s2_split(const void *in, void *out, int N, int H, int 
 hipError_t launch_nhwc_split_to_nchw(const void *in, float *out, int N, int H, int W, int C, hipStream_t s);
 // fp32 rows -> fp16 rows (mode 1) / split [hi | lo] rows (mode 2)
 hipError_t launch_rows_f32_to_half(const float *in, void *out, size_t rows, int C, int mode, hipStream_t s, int *sat = nullptr);
+// The internal device copy an op-level test entry converts the caller's rows into, and which the kernel under test then reads: `bytes`
+// framed by kOpGuardBytes of 0xFF (a NaN in fp16 and fp32) on each side, set on the call's stream before the conversion is enqueued, so the
+// kernel reads NaN beyond its operand just as an fp32 kernel does beyond a caller's guarded rows.  op_guarded_free releases the whole block.
+constexpr size_t kOpGuardBytes = 4096;
+inline hipError_t op_guarded_alloc(void **payload, size_t bytes, hipStream_t s) {
+    char *blk = nullptr;
+    *payload = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&blk), kOpGuardBytes + bytes + kOpGuardBytes);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(blk, 0xFF, kOpGuardBytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk + kOpGuardBytes + bytes, 0xFF, kOpGuardBytes, s);
+    if (e != hipSuccess) { (void)hipFree(blk); return e; }
+    *payload = blk + kOpGuardBytes;
+    return hipSuccess;
+}
+inline void op_guarded_free(void *payload) {
+    if (payload) (void)hipFree(static_cast<char *>(payload) - kOpGuardBytes);
+}
 hipError_t launch_maxpool3s2_f16(const void *in, void *out, int N, int H, int W, int C, int Ho, int Wo, hipStream_t s);
 hipError_t launch_nhwc_f16_to_nchw(const void *in, float *out, int N, int H, int W, int C, hipStream_t s);
 // tokens[(n*21+j)][col0 + c] = sum_t w_t * s[(n*21+j)*4+t][c]

@@ -263,6 +263,9 @@ int hmv_launch_count(hmv_handle h);
  * synchronisation; the word lives outside the workspace, so hmv_poison_workspace and cached graphs leave it alone). */
 int hmv_range_status(hmv_handle h, int32_t *saturated, void *stream);
 
+/* Op-level entries.  For every device pointer of these entries -- and of every other entry of this header -- a caller may rely on this:
+ * bytes outside an operand never influence a result, bytes outside an output are never written, and inputs are never modified. */
+
 /* One NHWC convolution through the engine's conv kernel (op-level parity tests).
  * in [N][H][W][Cin] device; weight OIHW host (Cin must be a multiple of 4);
  * bias host[Cout] or NULL; residual device [N][Ho][Wo][Cout] or NULL; out device NHWC. */
@@ -321,7 +324,8 @@ int hmv_op_conv2d_sel(int32_t device, const float *in, int32_t N, int32_t H, int
  * its tiles with the next tile's operands in flight; what a launch of two or more tiles per CU runs on; 3 is one workgroup per tile
  * whatever the size; same bits; channel-tile counts other than 1, 2, 4 have no persistent form and run as 3); 8 = as 2 with conv_gemm8's
  * PERSISTENT form wherever it exists (2 is one workgroup per tile whatever the size; same bits).  *kernel_name (optional) receives the family that ran.
- * The kernel_sel of the hmv_op_* entries applies to that call alone. */
+ * Cout % 4 == 0; output rows that are no whole 16-byte vectors (Cout % 8 != 0: no backbone layer has them) run on conv_igemm's staged
+ * epilogue, whatever Cin is.  The kernel_sel of the hmv_op_* entries applies to that call alone. */
 int hmv_op_conv2d_f16(int32_t device, const float *in, int32_t N, int32_t H, int32_t W, int32_t Cin,
                       const float *weight_oihw_host, const float *bias_host, int32_t Cout, int32_t R, int32_t S, int32_t stride,
                       int32_t pad, const float *residual, int32_t relu, void *out_f16, int32_t kernel_sel,

@@ -12,12 +12,12 @@ import torch
 
 import attention_oracle as ao
 from cases import ALL_POS, CASES, case_params
+from guards import Guards
 from helpers import load_case
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -23
-GUARD = 1024   # floats of NaN in front of and behind every op-level output
 
 # (B, T, Tq, koff, Tk)
 SHAPES = [(2, 21, 21, 0, 21),        # one partial chunk
@@ -33,13 +33,13 @@ OP_CASES = [("f32", s) for s in SHAPES] + [("pairs", s) for s in SHAPES] + [("lq
 OP_IDS = [f"{k}-{'x'.join(str(int(v)) for v in s)}" for k, s in OP_CASES]
 
 
-def _guarded(n, dev):
-    buf = torch.full((GUARD + n + GUARD,), float("nan"), device=dev)
-    return buf, buf.data_ptr() + GUARD * 4
-
-
-def _guards_untouched(buf, n):
-    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + n:]).all())
+def _guards_hold(gd):
+    try:
+        gd.check()
+    except AssertionError as e:
+        print(e)
+        return False
+    return True
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,13 +56,13 @@ def _op_run(kind, shape):
         if probe:
             q = torch.randn(Tq, 8, 256, generator=g) * 3.0
             kv = torch.randn(B, T, 2, 8, 256, generator=g)
-            rows, pq = kv.reshape(B, T, 4096).contiguous().to(dev), q.reshape(Tq, 2048).contiguous().to(dev)
+            rows, pq = kv.reshape(B, T, 4096), q.reshape(Tq, 2048)
             q64 = q.double().permute(1, 0, 2)[None].expand(B, -1, -1, -1)
             k64 = kv[:, :, 0].double().permute(0, 2, 1, 3)
         else:
             qkv = torch.randn(B, T, 3, 8, 256, generator=g)
             qkv[:, :, 0] *= 3.0
-            rows, pq = qkv.reshape(B, T, 6144).contiguous().to(dev), None
+            rows, pq = qkv.reshape(B, T, 6144), None
             q64 = qkv[:, :Tq, 0].double().permute(0, 2, 1, 3)
             k64 = qkv[:, :, 1].double().permute(0, 2, 1, 3)
         code = 2
@@ -72,7 +72,7 @@ def _op_run(kind, shape):
         g = torch.Generator().manual_seed(B * 1000 + T)
         qkv = torch.randn(B, T, 3, 8, 128, generator=g)
         qkv[:, :, 0] *= 3.0                                   # logits of std ~3: sharp rows
-        rows, pq = qkv.reshape(B, T, 3072).contiguous().to(dev), None
+        rows, pq = qkv.reshape(B, T, 3072), None
         q64 = qkv[:, :Tq, 0].double().permute(0, 2, 1, 3)
         k64 = qkv[:, koff:koff + Tk, 1].double().permute(0, 2, 1, 3)
         code = 0 if kind == "f32" else 1
@@ -80,17 +80,16 @@ def _op_run(kind, shape):
     views = (koff + Tk) // 21 if (koff % 21 == 0 and Tk % 21 == 0) else 0
 
     def run(nb):
-        n, ns = nb * 8 * Tq * Tk, nb * 8 * Tq * views
-        pbuf, pptr = _guarded(n, dev)
-        sbuf, sptr = _guarded(ns, dev) if views else (None, None)
-        rc = lib.hmv_op_attention_probs(0, code, rows[:nb].contiguous().data_ptr(), pq.data_ptr() if pq is not None else None, nb, T, Tq, koff,
-                                        Tk, None, pptr, sptr, views, None)
+        gd = Guards(dev)                    # 0xFF bands (tests/guards.py) around the rows, the probe and both outputs, which start as NaN
+        rd = gd.inp(rows[:nb])
+        pd = gd.inp(pq) if pq is not None else None
+        pout = gd.out((nb, 8, Tq, Tk))
+        sout = gd.out((nb, 8, Tq, views)) if views else None
+        rc = lib.hmv_op_attention_probs(0, code, rd.data_ptr(), pd.data_ptr() if pd is not None else None, nb, T, Tq, koff,
+                                        Tk, None, pout.data_ptr(), sout.data_ptr() if views else None, views, None)
         assert rc == 0, lib.hmv_last_error(None)
         torch.cuda.synchronize()
-        ok = _guards_untouched(pbuf, n) and (sbuf is None or _guards_untouched(sbuf, ns))
-        probs = pbuf[GUARD:GUARD + n].reshape(nb, 8, Tq, Tk).cpu()
-        share = sbuf[GUARD:GUARD + ns].reshape(nb, 8, Tq, views).cpu() if views else None
-        return probs, share, ok
+        return pout.cpu(), sout.cpu() if views else None, _guards_hold(gd)
 
     probs, share, ok = run(B)
     alone, _, ok1 = run(1)
@@ -147,16 +146,15 @@ def test_probs_kernel_ragged_op():
     g = torch.Generator().manual_seed(77)
     qkv = torch.randn(126, 3, 8, 128, generator=g)
     qkv[:, 0] *= 3.0
-    rows = qkv.reshape(126, 3072).contiguous().to(dev)
     for code in (0, 1):
-        n, ns = 3 * 8 * 21 * 42, 3 * 8 * 21 * 3
-        pbuf, pptr = _guarded(n, dev)
-        sbuf, sptr = _guarded(ns, dev)
-        rc = lib.hmv_op_attention_probs(0, code, rows.data_ptr(), None, 3, 0, 21, 21, 0, (ctypes.c_int32 * 4)(*seg), pptr, sptr, 3, None)
+        gd = Guards(dev)
+        rows = gd.inp(qkv.reshape(126, 3072))
+        probs, share = gd.out((3, 8, 21, 42)), gd.out((3, 8, 21, 3))
+        rc = lib.hmv_op_attention_probs(0, code, rows.data_ptr(), None, 3, 0, 21, 21, 0, (ctypes.c_int32 * 4)(*seg), probs.data_ptr(),
+                                        share.data_ptr(), 3, None)
         assert rc == 0, lib.hmv_last_error(None)
         torch.cuda.synchronize()
-        assert _guards_untouched(pbuf, n) and _guards_untouched(sbuf, ns)
-        probs, share = pbuf[GUARD:GUARD + n].reshape(3, 8, 21, 42), sbuf[GUARD:GUARD + ns].reshape(3, 8, 21, 3)
+        gd.check()
         assert torch.isfinite(probs).all() and torch.isfinite(share).all()
         for b in range(3):
             T = seg[b + 1] - seg[b]
@@ -166,11 +164,12 @@ def test_probs_kernel_ragged_op():
             if Tk == 0:
                 assert float(probs[b].abs().max()) == 0.0 and float(share[b].abs().max()) == 0.0
                 continue
-            one = torch.full((8, 21, Tk), float("nan"), device=dev)
-            rc = lib.hmv_op_attention_probs(0, code, rows[seg[b]:seg[b + 1]].contiguous().data_ptr(), None, 1, T, 21, 21, Tk, None,
+            one = gd.out((8, 21, Tk))
+            rc = lib.hmv_op_attention_probs(0, code, gd.inp(qkv[seg[b]:seg[b + 1]].reshape(T, 3072)).data_ptr(), None, 1, T, 21, 21, Tk, None,
                                             one.data_ptr(), None, 0, None)
             assert rc == 0, lib.hmv_last_error(None)
             torch.cuda.synchronize()
+            gd.check()
             assert torch.equal(probs[b, :, :, :Tk], one)
 
 

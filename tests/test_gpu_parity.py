@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from cases import CASES
+from guards import Guards
 from helpers import check_against_fixture, cond_bounds, load_case, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -344,15 +345,16 @@ def _run_conv(shape, dtype):
     N, H, W, Cin, Cout, k, stride, pad, use_res, relu = shape
     x, w, b, res, ref = _conv_case(shape)
     Ho, Wo = ref.shape[2:]
-    dev = torch.device("cuda:0")
-    xin = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    out = torch.full((N, Ho, Wo, Cout), float("nan"), device=dev)
-    rdev = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
+    gd = Guards(torch.device("cuda:0"))     # 0xFF bands around every device buffer: the output starts as NaN
+    xin = gd.inp(x.permute(0, 2, 3, 1))
+    out = gd.out((N, Ho, Wo, Cout))
+    rdev = gd.inp(res.permute(0, 2, 3, 1)) if use_res else None
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
     rc = lib.hmv_op_conv2d_ex(0, dtype, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p),
                               bc.ctypes.data_as(ctypes.c_void_p), Cout, k, k, stride, pad,
                               rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), None)
     assert rc == 0, lib.hmv_last_error(None)
+    gd.check()
     got = out.cpu().permute(0, 3, 1, 2).double()
     assert torch.isfinite(got).all()
     return (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-9)
@@ -401,16 +403,17 @@ def test_split_pair_gemm_large_tiles_by_kernel_sel(shape):
     lib = _lib.load()
     N, H, W, Cin, Cout, k, stride, pad, use_res, relu = shape
     x, w, b, res, ref = _conv_case(shape)
-    dev = torch.device("cuda:0")
-    xin = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    gd = Guards(torch.device("cuda:0"))
+    xin = gd.inp(x.permute(0, 2, 3, 1))
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
     outs, names = [], []
     for sel in (2, 1):   # gemm_x3k16 whenever the shape allows / the fused split loop only
-        out = torch.full((N, H, W, Cout), float("nan"), device=dev)
+        out = gd.out((N, H, W, Cout))
         kname = ctypes.c_char_p()
         rc = lib.hmv_op_conv2d_x3(0, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p), Cout, 1, 1, 1, 0,
                                   None, 0, out.data_ptr(), sel, ctypes.byref(kname), None)
         assert rc == 0, lib.hmv_last_error(None)
+        gd.check()
         outs.append(out.cpu())
         names.append(kname.value.decode())
     assert names[0].startswith("gemm_x3k16_f16") and "gemm_x3k16" not in names[1], names
@@ -482,16 +485,17 @@ def _run_conv_f16(shape, sel):
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     b = torch.randn(Cout, generator=g)
     res = torch.randn(N, H, W, Cout, generator=g) if use_res else None
-    dev = torch.device("cuda:0")
-    xin = x.to(dev)
-    rdev = res.to(dev) if use_res else None
-    out = torch.full((N, H, W, Cout), float("nan"), device=dev, dtype=torch.float16)
+    gd = Guards(torch.device("cuda:0"))     # 0xFF bands around every device buffer: the output starts as NaN
+    xin = gd.inp(x)
+    rdev = gd.inp(res) if use_res else None
+    out = gd.out((N, H, W, Cout), torch.float16)
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
     kname = ctypes.c_char_p()
     rc = lib.hmv_op_conv2d_f16(0, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p),
                                Cout, k, k, stride, pad, rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), sel,
                                ctypes.byref(kname), None)
     assert rc == 0, lib.hmv_last_error(None)
+    gd.check()
     return out.cpu(), kname.value.decode(), (x, w, b, res, relu)
 
 
@@ -571,13 +575,14 @@ def test_tall_tile_kernel(shape):
         # same seed stream: _run_conv_f16 seeds by the shape, so rebuild image 0 from the batch's own tensors
         from handmvnet_amd import _lib
         lib = _lib.load()
-        dev = torch.device("cuda:0")
-        x0 = x[:1].contiguous().to(dev)
-        out = torch.full((1,) + tuple(a.shape[1:]), float("nan"), device=dev, dtype=torch.float16)
+        gd = Guards(torch.device("cuda:0"))
+        x0 = gd.inp(x[:1])
+        out = gd.out((1,) + tuple(a.shape[1:]), torch.float16)
         wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
         rc = lib.hmv_op_conv2d_f16(0, x0.data_ptr(), 1, one[1], one[2], one[3], wc.ctypes.data_as(ctypes.c_void_p),
                                    bc.ctypes.data_as(ctypes.c_void_p), one[4], 3, 3, 1, 1, None, int(relu), out.data_ptr(), 4, None, None)   # on the small-launch tiles
         assert rc == 0, lib.hmv_last_error(None)
+        gd.check()
         assert torch.equal(out.cpu()[0].view(torch.int16), a[0].view(torch.int16))
 
 
@@ -683,10 +688,11 @@ def test_op_hooks_run_beside_forwards_of_other_handles():
     solo = forward()
     N, H, W, Cin, Cout, k, stride, pad, _, relu = HT_SHAPES[0]
     g = torch.Generator().manual_seed(11)
-    xo = torch.randn(N, H, W, Cin, generator=g).to(dev)
+    gd = Guards(dev)
+    xo = gd.inp(torch.randn(N, H, W, Cin, generator=g))
     wc = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).numpy()
     bc = torch.randn(Cout, generator=g).numpy()
-    outs = {sel: torch.empty(N, H, W, Cout, device=dev, dtype=torch.float16) for sel in (5, 6)}
+    outs = {sel: gd.out((N, H, W, Cout), torch.float16) for sel in (5, 6)}
     torch.cuda.synchronize()
     names, errors = set(), []
 
@@ -711,6 +717,9 @@ def test_op_hooks_run_beside_forwards_of_other_handles():
     finally:
         t.join()
     assert not errors, errors
+    torch.cuda.synchronize()
+    gd.check()
+    assert all(torch.isfinite(o.float()).all() for o in outs.values())
     assert len(names) == 2 and "conv_ht_f16<512x128,3x3>" in names and all("m16" not in n for n in names), names
 
 
@@ -735,16 +744,17 @@ def test_stream32_kernel_is_bit_identical(shape):
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     b = torch.randn(Cout, generator=g)
     res = torch.randn(N, H, W, Cout, generator=g)
-    dev = torch.device("cuda:0")
-    xin, rdev = x.to(dev), res.to(dev)
+    gd = Guards(torch.device("cuda:0"))
+    xin, rdev = gd.inp(x), gd.inp(res)
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
     outs, names = [], []
     for sel in (2, 1):
-        out = torch.full((N, H, W, Cout), float("nan"), device=dev)
+        out = gd.out((N, H, W, Cout))
         kname = ctypes.c_char_p()
         rc = lib.hmv_op_conv2d_sel(0, xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p),
                                    Cout, k, k, stride, pad, rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), sel, ctypes.byref(kname), None)
         assert rc == 0, lib.hmv_last_error(None)
+        gd.check()
         outs.append(out.cpu())
         names.append(kname.value.decode())
     assert names[0].startswith("conv_stream_f32") and names[1].startswith("conv_igemm_f32"), names
@@ -778,16 +788,17 @@ def test_rds_kernel_is_bit_identical(shape):
     w = torch.randn(C, C, 3, 3, generator=g) / (C * 9) ** 0.5
     b = torch.randn(C, generator=g)
     res = torch.randn(N, H, W, C, generator=g)
-    dev = torch.device("cuda:0")
-    xin, rdev = x.to(dev), res.to(dev)
+    gd = Guards(torch.device("cuda:0"))
+    xin, rdev = gd.inp(x), gd.inp(res)
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
     outs, names = [], []
     for sel in (2, 1):
-        out = torch.full((N, H, W, C), float("nan"), device=dev)
+        out = gd.out((N, H, W, C))
         kname = ctypes.c_char_p()
         rc = lib.hmv_op_conv2d_rd(0, xin.data_ptr(), N, H, W, C, wc.ctypes.data_as(ctypes.c_void_p), bc.ctypes.data_as(ctypes.c_void_p),
                                   rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), sel, ctypes.byref(kname), None)
         assert rc == 0, lib.hmv_last_error(None)
+        gd.check()
         outs.append(out.cpu())
         names.append(kname.value.decode())
     assert names[0].startswith("conv_rds_f32") and names[1].startswith("conv_igemm_f32") and "rowsum" in names[1], names
@@ -977,9 +988,10 @@ def test_hr_fuse_up_vs_torch(shape, f16):
         ref = ref + gq.repeat_interleave(1 << sh, dim=1).repeat_interleave(1 << sh, dim=2)
     if relu:
         ref = ref.clamp_min(0)
-    dbase = base.to(dev)
-    dxs = [x.contiguous().to(dev) for x in xs]
-    out = torch.full((N, H, W, C), float("nan"), device=dev, dtype=torch.float16 if f16 else torch.float32)
+    gd = Guards(dev)                        # 0xFF bands around the base, every source and the output (which starts as NaN)
+    dbase = gd.inp(base)
+    dxs = [gd.inp(x) for x in xs]
+    out = gd.out((N, H, W, C), torch.float16 if f16 else torch.float32)
     n = len(srcs)
     vp = ctypes.c_void_p
     src_p = (vp * n)(*[vp(t.data_ptr()) for t in dxs])
@@ -991,6 +1003,7 @@ def test_hr_fuse_up_vs_torch(shape, f16):
     sh_a = (ctypes.c_int32 * n)(*[sh for _, sh in srcs])
     rc = lib.hmv_op_hr_fuse_up(0, f16, vp(dbase.data_ptr()), N, H, W, C, n, src_p, cs_a, sh_a, w_p, b_p, int(relu), vp(out.data_ptr()), None)
     assert rc == 0, lib.hmv_last_error(None)
+    gd.check()
     got = out.cpu().double()
     assert torch.isfinite(got).all()
     err = (got - ref).abs().max().item() / ref.abs().max().item()
@@ -1328,8 +1341,9 @@ def test_attention_kernel_vs_torch(shape, kernel):
     qkv = torch.randn(B, T, 3, 8, 128, generator=g)
     qkv[:, :, 0] *= 3.0                                   # logits of std ~3 * sqrt(128) / sqrt(128): sharp rows
     dev = torch.device("cuda:0")
-    qd = qkv.reshape(B, T, 3072).contiguous().to(dev)
-    out = torch.full((B, Tq, 1024), float("nan"), device=dev)
+    gd = Guards(dev)                        # 0xFF bands around qkv and the outputs (which start as NaN)
+    qd = gd.inp(qkv.reshape(B, T, 3072))
+    out = gd.out((B, Tq, 1024))
     rc = op(0, qd.data_ptr(), B, T, Tq, koff, Tk, out.data_ptr(), None)
     assert rc == 0, lib.hmv_last_error(None)
     torch.cuda.synchronize()
@@ -1345,9 +1359,11 @@ def test_attention_kernel_vs_torch(shape, kernel):
     print(kernel, shape, err)
     assert err < 4e-6, err       # (measured: f32 0.8 .. 2.1e-6, x3 0.6 .. 1.5e-6)
     # sample 0 alone gives the same bits
-    out1 = torch.full((1, Tq, 1024), float("nan"), device=dev)
-    rc = op(0, qd[:1].contiguous().data_ptr(), 1, T, Tq, koff, Tk, out1.data_ptr(), None)
+    out1 = gd.out((1, Tq, 1024))
+    rc = op(0, gd.inp(qkv[:1].reshape(1, T, 3072)).data_ptr(), 1, T, Tq, koff, Tk, out1.data_ptr(), None)
     assert rc == 0
+    torch.cuda.synchronize()
+    gd.check()
     assert torch.equal(out1[0], out[0])
 
 
@@ -1366,27 +1382,29 @@ def test_lq_attention_kernel_vs_torch(shape):
     B, T, Tq, probe = shape
     g = torch.Generator().manual_seed(B * 1000 + T)
     dev = torch.device("cuda:0")
+    gd = Guards(dev)                        # 0xFF bands around the probe, the qkv / kv rows and the outputs (which start as NaN)
     if probe:
         q = torch.randn(Tq, 8, 256, generator=g) * 3.0
         kv = torch.randn(B, T, 2, 8, 256, generator=g)
-        qd, kvd = q.reshape(Tq, 2048).contiguous().to(dev), kv.reshape(B, T, 4096).contiguous().to(dev)
+        qd, kvd = gd.inp(q.reshape(Tq, 2048)), gd.inp(kv.reshape(B, T, 4096))
         args = (qd.data_ptr(), 2048, 0, kvd.data_ptr(), kvd.data_ptr() + 2048 * 4, 4096)
         q64 = q.double().permute(1, 0, 2)[None].expand(B, -1, -1, -1)
         k64, v64 = kv[:, :, 0].double().permute(0, 2, 1, 3), kv[:, :, 1].double().permute(0, 2, 1, 3)
     else:
         qkv = torch.randn(B, T, 3, 8, 256, generator=g)
         qkv[:, :, 0] *= 3.0
-        qd = qkv.reshape(B, T, 6144).contiguous().to(dev)
+        qd = gd.inp(qkv.reshape(B, T, 6144))
         args = (qd.data_ptr(), 6144, T, qd.data_ptr() + 2048 * 4, qd.data_ptr() + 4096 * 4, 6144)
         q64 = qkv[:, :Tq, 0].double().permute(0, 2, 1, 3)
         k64, v64 = qkv[:, :, 1].double().permute(0, 2, 1, 3), qkv[:, :, 2].double().permute(0, 2, 1, 3)
     ref = (torch.softmax(q64 @ k64.transpose(-1, -2) * 256 ** -0.5, dim=-1) @ v64).permute(0, 2, 1, 3).reshape(B, Tq, 2048)
 
     def run(nb):
-        out = torch.full((nb, Tq, 2048), float("nan"), device=dev)
+        out = gd.out((nb, Tq, 2048))
         rc = lib.hmv_op_attention_lq(0, *args, nb, T, Tq, out.data_ptr(), None)
         assert rc == 0, lib.hmv_last_error(None)
         torch.cuda.synchronize()
+        gd.check()
         return out
     got = run(B)
     assert torch.isfinite(got).all()

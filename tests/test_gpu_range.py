@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from guards import Guards, bands_intact, guarded
 from helpers import load_case, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -71,18 +72,27 @@ def _case(shape, k, which):
 
 
 def _call(fn, shape, x, w, b, res, out, *extra):
+    """One op-level conv call on guarded device buffers (tests/guards.py): whatever the return code, the bands around the inputs and the
+    output (an _nhwc_out) are intact afterwards and the inputs hold their bits."""
     N, H, W, Cin, Cout, ks, stride, pad, use_res, relu = shape
-    dev = torch.device("cuda:0")
-    xin = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    rdev = res.permute(0, 2, 3, 1).contiguous().to(dev) if use_res else None
+    gd = Guards(torch.device("cuda:0"))
+    xin = gd.inp(x.permute(0, 2, 3, 1))
+    rdev = gd.inp(res.permute(0, 2, 3, 1)) if use_res else None
     wc, bc = w.contiguous().numpy(), b.contiguous().numpy()
-    return fn(xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(vp), bc.ctypes.data_as(vp), Cout, ks, ks, stride, pad,
-              rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), *extra)
+    rc = fn(xin.data_ptr(), N, H, W, Cin, wc.ctypes.data_as(vp), bc.ctypes.data_as(vp), Cout, ks, ks, stride, pad,
+            rdev.data_ptr() if use_res else None, int(relu), out.data_ptr(), *extra)
+    torch.cuda.synchronize()
+    gd.check()
+    assert bands_intact(out.guard_buf, out), "a guard band around the output was written"
+    return rc
 
 
 def _nhwc_out(shape, ref, dtype=torch.float32):
+    """The output rows as a guarded payload: every byte 0xFF (NaN), its whole buffer kept at .guard_buf for _call's band check."""
     N, Cout = shape[0], shape[4]
-    return torch.full((N, ref.shape[2], ref.shape[3], Cout), float("nan"), device="cuda:0", dtype=dtype)
+    buf, out = guarded((N, ref.shape[2], ref.shape[3], Cout), dtype, torch.device("cuda:0"))
+    out.guard_buf = buf
+    return out
 
 
 def _conv_f32(shape, dtype, x, w, b, res, ref):
@@ -228,15 +238,17 @@ def test_attention_across_the_fp16_range(shape):
     dev = torch.device("cuda:0")
     for k in (-14, -6, -3, 0, 4, 15, 16, 18):
         qkv = base * 2.0 ** k
-        qd = qkv.reshape(B, T, 3072).contiguous().to(dev)
+        gd = Guards(dev)
+        qd = gd.inp(qkv.reshape(B, T, 3072))
         q = qkv[:, :Tq, 0].double().permute(0, 2, 1, 3)
         kk = qkv[:, koff:koff + Tk, 1].double().permute(0, 2, 1, 3)
         v = qkv[:, koff:koff + Tk, 2].double().permute(0, 2, 1, 3)
         ref = (torch.softmax(q @ kk.transpose(-1, -2) * 128 ** -0.5, dim=-1) @ v).permute(0, 2, 1, 3).reshape(B, Tq, 1024)
         for kernel, op in (("f32", lib.hmv_op_attention), ("x3", lib.hmv_op_attention_x3)):
-            out = torch.full((B, Tq, 1024), float("nan"), device=dev)
+            out = gd.out((B, Tq, 1024))
             rc = op(0, qd.data_ptr(), B, T, Tq, koff, Tk, out.data_ptr(), None)
             torch.cuda.synchronize()
+            gd.check()
             if kernel == "x3" and qkv.abs().max().item() > F16_MAX:
                 assert rc == HMV_ERR_RANGE and b"hmv_op_attention_x3" in lib.hmv_last_error(None), (k, rc)
                 continue
@@ -270,9 +282,10 @@ def test_hr_fuse_up_fp16_across_the_range(shape):
             ref = ref + gq.repeat_interleave(1 << sh, dim=1).repeat_interleave(1 << sh, dim=2)
         if relu:
             ref = ref.clamp_min(0)
-        dbase = base.to(dev)
-        dxs = [x.contiguous().to(dev) for x in xs]
-        out = torch.full((N, H, W, C), float("nan"), device=dev, dtype=torch.float16)
+        gd = Guards(dev)
+        dbase = gd.inp(base)
+        dxs = [gd.inp(x) for x in xs]
+        out = gd.out((N, H, W, C), torch.float16)
         n = len(srcs)
         wn = [w.contiguous().numpy() for w in ws]
         bn = [b.contiguous().numpy() for b in bs]
@@ -281,6 +294,7 @@ def test_hr_fuse_up_fp16_across_the_range(shape):
                                    (vp * n)(*[a.ctypes.data_as(vp) for a in wn]), (vp * n)(*[a.ctypes.data_as(vp) for a in bn]), int(relu),
                                    vp(out.data_ptr()), None)
         assert rc == 0, lib.hmv_last_error(None)
+        gd.check()
         got = out.cpu().double()
         big = ref.abs() >= F16_INF_EDGE * (1 + 1e-3)
         fin = ref.abs() < F16_MAX * (1 - 1e-3)

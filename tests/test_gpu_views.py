@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from guards import Guards
 from helpers import check_against_fixture, rel_l2
 from views_cases import VIEWS_CASES
 from views_helpers import OUT_KEYS, load_views_case, oracle_per_sample, per_sample, sample_inputs
@@ -197,14 +198,16 @@ def test_attention_views_kernels_vs_torch(kind, cross):
         mat = torch.randn(rows, 3, 8, D, generator=g)
         mat[:, 0] *= 3.0
         kcol, vcol = 1, 2
-    md = mat.reshape(rows, -1).contiguous().to(DEV)
-    pd = probe.reshape(21, 8 * D).contiguous().to(DEV) if probe is not None else None
+    gd = Guards(DEV)                        # 0xFF bands around the rows, the probe and the output (which starts as NaN)
+    md = gd.inp(mat.reshape(rows, -1))
+    pd = gd.inp(probe.reshape(21, 8 * D)) if probe is not None else None
     out_rows = B * 21 if cross else rows
-    out = torch.full((out_rows, 8 * D), float("nan"), device=DEV)
+    out = gd.out((out_rows, 8 * D))
     rc = lib.hmv_op_attention_views(0, {"f32": 0, "x3": 1, "lq": 2}[kind], md.data_ptr(), pd.data_ptr() if pd is not None else None, B, seg,
                                     cross, out.data_ptr(), None)
     assert rc == 0, lib.hmv_last_error(None)
     torch.cuda.synchronize()
+    gd.check()
     got = out.cpu().double()
     assert torch.isfinite(got).all()
     worst = 0.0

@@ -16,17 +16,14 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/handmv.h"
 #include "kernels.h"
 #include "pose_rows.h"
 
 namespace {
 
-constexpr int NJ = 21;
-constexpr int kLanes = 256;    // lanes of a workgroup and samples of a staged chunk.  256 and not pose_rows.h's 1024: the alignment lane
-                               // then has 512 registers to itself (eval_epoch_body.inc explains what 1024 lanes leave it)
+constexpr int kLanes = 256;    // lanes of a workgroup and samples of a staged chunk.  256 and not the epoch kernels' 1024: the alignment lane
+                               // then has 512 registers to itself (eval_epoch.hip explains what 1024 lanes leave it)
 constexpr int kHeader = 4;     // state[0 .. 4): samples, steps added, V, S
 constexpr int kRecordHead = 4; // record row: mpjpe, pa_mpjpe, mpjpe2d, views, then one value per camera
 
@@ -44,62 +41,13 @@ __device__ __forceinline__ float *record_row(const BreakdownParams &a, long samp
     return a.records + (a.record_base + sample) * (long)(kRecordHead + a.V);
 }
 
-// |p - g| in fp32 with the roundings of the pooled kernels.  row_distance (pose_rows.h) leaves the fusing of its multiply-adds to the
-// compiler, which picks by context: eval_epoch_body.inc's 3D loop compiles to fma(d1, d1, d0 * d0) + d2 * d2 and its 2D loop to
-// d0 * d0 + d1 * d1 (both squares rounded), this file's loops came out as two nested fmas.  A last-bit difference in a distance is
-// 1e-9 of a sum, so the breakdown would add up to the pooled state only to fp32 accuracy -- and a distance on a threshold would fall
-// into another bin.  Spelled out under contract(off), the distances here have the pooled kernels' bits, whatever the compiler
-// would choose (tests/test_gpu_breakdown.py compares the column sums with the pooled state at 1e-12 and the bins exactly).
-__device__ __forceinline__ float distance_3(const float *p, const float *g) {
-#pragma clang fp contract(off)
-    const float d0 = p[0] - g[0], d1 = p[1] - g[1], d2 = p[2] - g[2];
-    return sqrtf(fmaf(d1, d1, d0 * d0) + d2 * d2);
-}
-
-__device__ __forceinline__ float distance_2(const float *p, const float *g) {
-#pragma clang fp contract(off)
-    const float d0 = p[0] - g[0], d1 = p[1] - g[1];
-    return sqrtf(d0 * d0 + d1 * d1);
-}
-
-// the masked 2D distance of row r = (sample * V + view) * 21 + joint: a masked joint is zeroed on both sides (eval_epoch_body.inc)
+// the masked 2D distance of row r = (sample * V + view) * 21 + joint: a masked joint is zeroed on both sides (eval_epoch.hip)
 __device__ __forceinline__ float distance_2d(const BreakdownParams &a, long r, bool *visible) {
     const float keep = (a.mask && a.mask[r]) ? 0.f : 1.f;
     const float p[2] = {a.pred_2d[r * 2] * keep, a.pred_2d[r * 2 + 1] * keep};
     const float g[2] = {a.gt_2d[r * 2] * keep, a.gt_2d[r * 2 + 1] * keep};
     *visible = keep != 0.f;
     return distance_2(p, g);
-}
-
-// The 21 distances that remain after the similarity transform of pose p onto g (metrics.py:128-176): the statements of
-// POSE_ADD_ALIGNED_ERROR (pose_rows.h) with the distance of point j stored to out[j] where that macro adds it to one sum.
-__device__ void aligned_distances(const float *__restrict__ p, const float *__restrict__ g, double *out) {
-    POSE_MOMENTS(p, g, NJ, mu1, mu2, var1, K)
-    double U[3][3], S[3], V[3][3];
-    svd3(K, U, S, V);
-    double UVt[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) UVt[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + U[a][2] * V[b][2];
-    const double dd = det3(UVt);
-    const double z = dd > 0 ? 1.0 : (dd < 0 ? -1.0 : 0.0);
-    double R[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) R[a][b] = V[a][0] * U[b][0] + V[a][1] * U[b][1] + z * V[a][2] * U[b][2];
-    double trace = 0.0;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) trace += R[a][b] * K[b][a];
-    const double scale = trace / var1;
-    double tr[3];
-    for (int a = 0; a < 3; ++a) tr[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);
-    for (int j = 0; j < NJ; ++j) {
-        double e2 = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const double y = scale * (R[a][0] * p[j * 3] + R[a][1] * p[j * 3 + 1] + R[a][2] * p[j * 3 + 2]) + tr[a];
-            const double e = y - (double)g[j * 3 + a];
-            e2 += e * e;
-        }
-        out[j] = sqrt(e2);
-    }
 }
 
 // ---- workgroup 0: the 3D distance per joint, its PCK bins per joint, the header
@@ -149,11 +97,16 @@ __device__ __forceinline__ void joints_aligned(const BreakdownParams &a) {
     __shared__ double dist[kLanes * NJ];
     const int t = threadIdx.x;
     double col = 0.0;
-    for (int first = 0; first < a.B; first += kLanes) {   // a uniform counter, as in eval_epoch_body.inc
+    for (int first = 0; first < a.B; first += kLanes) {   // a uniform counter, as in eval_epoch.hip
         const int n = min(kLanes, a.B - first);
         if (t < n) {
-            const long at = (long)(first + t) * NJ * 3;
-            aligned_distances(a.pred_cam + at, a.gt_cam + at, dist + t * NJ);
+            const float *p = a.pred_cam + (long)(first + t) * NJ * 3, *g = a.gt_cam + (long)(first + t) * NJ * 3;
+            PoseMoments m;
+            pose_moments(p, g, NJ, m);
+            double U[3][3], S[3], V[3][3];
+            svd3(m.K, U, S, V);
+            double *out = dist + t * NJ;
+            pose_aligned_points(p, g, NJ, m, U, V, [&](int j, const double *, double d) { out[j] = d; });
         }
         __syncthreads();
         if (t < NJ)
@@ -241,10 +194,8 @@ __global__ __launch_bounds__(kLanes) void eval_breakdown_kernel(BreakdownParams 
         sample_2d(a);
 }
 
-int bad_arg(const char *what) {
-    hmv::set_thread_error(std::string("hmv_eval_breakdown_add: ") + what);
-    return HMV_ERR_ARG;
-}
+using hmv::bad_arg;
+using hmv::hip_fail;
 
 }  // namespace
 
@@ -256,32 +207,17 @@ extern "C" size_t hmv_eval_breakdown_doubles(int32_t V, int32_t steps) {
 extern "C" size_t hmv_eval_record_floats(int32_t V) { return V >= 1 ? (size_t)kRecordHead + V : 0; }
 
 extern "C" int hmv_eval_breakdown_add(int32_t device, const hmv_eval_breakdown_args *a, void *stream) {
-    // the rules of check_eval_args (eval_epoch.hip), in its order and wording; then the record table's
-    if (!a) return bad_arg("args is NULL");
-    if (a->struct_size != (int32_t)sizeof(hmv_eval_breakdown_args))
-        return bad_arg("struct_size does not match this library's hmv_eval_breakdown_args");
-    if (a->B < 1) return bad_arg("B must be >= 1");
-    if (a->V < 1) return bad_arg("V must be >= 1");
-    if ((int64_t)a->B * a->V > (1 << 24)) return bad_arg("B * V must not exceed 2^24 frames");
-    if (a->steps < 1 || a->steps > kMaxSteps) return bad_arg("steps must be in 1 .. 256");
-    if (!(a->thr_max >= a->thr_min)) return bad_arg("thr_max must not be below thr_min");
-    if (!a->pred_joints_cam) return bad_arg("pred_joints_cam is NULL");
-    if (!a->gt_joints_cam) return bad_arg("gt_joints_cam is NULL");
-    if (!a->pred_joints_2d) return bad_arg("pred_joints_2d is NULL");
-    if (!a->gt_joints_2d) return bad_arg("gt_joints_2d is NULL");
-    if (!a->state || ((uintptr_t)a->state & 7)) return bad_arg("state is NULL or not 8-byte aligned");
-    if (a->state_doubles < hmv_eval_breakdown_doubles(a->V, a->steps))
-        return bad_arg("state_doubles is smaller than hmv_eval_breakdown_doubles gives for V and steps");
+    const char *who = "hmv_eval_breakdown_add";
+    if (const int rc = hmv::check_eval_args(who, a, "hmv_eval_breakdown_args", a ? hmv_eval_breakdown_doubles(a->V, a->steps) : 0,
+                                            "state_doubles is smaller than hmv_eval_breakdown_doubles gives for V and steps"))
+        return rc;
     if (a->records) {
-        if ((uintptr_t)a->records & 3) return bad_arg("records is not 4-byte aligned");
-        if (a->record_capacity < 1) return bad_arg("record_capacity must be >= 1 with records");
-        if (a->record_base < 0) return bad_arg("record_base must be >= 0");
-        if (a->record_base > a->record_capacity - a->B) return bad_arg("record_base + B exceeds record_capacity");
+        if ((uintptr_t)a->records & 3) return bad_arg(who, "records is not 4-byte aligned");
+        if (a->record_capacity < 1) return bad_arg(who, "record_capacity must be >= 1 with records");
+        if (a->record_base < 0) return bad_arg(who, "record_base must be >= 0");
+        if (a->record_base > a->record_capacity - a->B) return bad_arg(who, "record_base + B exceeds record_capacity");
     }
-    if (hipSetDevice(device) != hipSuccess) {
-        hmv::set_thread_error(std::string("hmv_eval_breakdown_add: ") + hipGetErrorString(hipGetLastError()));
-        return HMV_ERR_HIP;
-    }
+    if (hipSetDevice(device) != hipSuccess) return hip_fail(who, hipGetLastError());
     BreakdownParams k;
     k.pred_cam = a->pred_joints_cam; k.gt_cam = a->gt_joints_cam; k.pred_2d = a->pred_joints_2d; k.gt_2d = a->gt_joints_2d;
     k.mask = a->joints_mask; k.present = a->view_present; k.state = a->state;
@@ -291,7 +227,5 @@ extern "C" int hmv_eval_breakdown_add(int32_t device, const hmv_eval_breakdown_a
     const int groups = 2 + a->V + (a->records ? 1 : 0);
     hipLaunchKernelGGL(eval_breakdown_kernel, dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, k);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return HMV_OK;
-    hmv::set_thread_error(std::string("hmv_eval_breakdown_add: ") + hipGetErrorString(e));
-    return HMV_ERR_HIP;
+    return e == hipSuccess ? HMV_OK : hip_fail(who, e);
 }

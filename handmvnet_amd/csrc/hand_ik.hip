@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int NJ = 21;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;
 constexpr int kUnapplyThreads = 256;
@@ -242,15 +241,8 @@ __global__ __launch_bounds__(kUnapplyThreads) void rigid_unapply_kernel(const fl
     for (int c = 0; c < 3; ++c) out[i * 3 + c] = r[c];
 }
 
-int bad_arg(const char *who, const char *what) {
-    hmv::set_thread_error(std::string(who) + ": " + what);
-    return HMV_ERR_ARG;
-}
-
-int hip_fail(const char *who, hipError_t e) {
-    hmv::set_thread_error(std::string(who) + ": " + hipGetErrorString(e));
-    return HMV_ERR_HIP;
-}
+using hmv::bad_arg;
+using hmv::hip_fail;
 
 }  // namespace
 

@@ -8,6 +8,8 @@
 #include <mutex>
 #include <string>
 
+#include "../../include/handmv.h"
+
 // Development knobs (A/B switches, probes: DESIGN.md section 9) exist only in a -DHMV_DEV_KNOBS build
 // (`python -m handmvnet_amd.build --variant dev HMV_DEV_KNOBS` -> build/libhandmv_dev.so, loaded with HMV_LIB=...).  The product
 // library reads ONE environment variable, HMV_GRAPHS; tests/test_abi_cpu.py holds its strings to that.
@@ -417,5 +419,40 @@ hipError_t launch_rigid_unapply(const float *points, const double *align, long n
 
 // Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
 void set_thread_error(const std::string &msg);
+
+// How an entry refuses a call: "<entry>: <what>" becomes the calling thread's error text, the code is returned.
+inline int bad_arg(const char *who, const char *what) {
+    set_thread_error(std::string(who) + ": " + what);
+    return HMV_ERR_ARG;
+}
+
+inline int hip_fail(const char *who, hipError_t e) {
+    set_thread_error(std::string(who) + ": " + hipGetErrorString(e));
+    return HMV_ERR_HIP;
+}
+
+// The argument rules of hmv_eval_add, hmv_eval_add_views and hmv_eval_breakdown_add over the leading fields hmv_eval_args and
+// hmv_eval_breakdown_args share, in front of every HIP call; 0 or the HMV_ERR_ARG of the first broken one.  struct_name: the
+// struct as the message names it; state_need / state_msg: the doubles the entry's state takes for these args (0 for a bad V or
+// steps, which an earlier rule refuses) and the message for a smaller one.
+constexpr int kMaxEvalSteps = 256;
+template <typename Args>
+int check_eval_args(const char *who, const Args *a, const char *struct_name, size_t state_need, const char *state_msg) {
+    if (!a) return bad_arg(who, "args is NULL");
+    if (a->struct_size != (int32_t)sizeof(Args))
+        return bad_arg(who, (std::string("struct_size does not match this library's ") + struct_name).c_str());
+    if (a->B < 1) return bad_arg(who, "B must be >= 1");
+    if (a->V < 1) return bad_arg(who, "V must be >= 1");
+    if ((int64_t)a->B * a->V > (1 << 24)) return bad_arg(who, "B * V must not exceed 2^24 frames");
+    if (a->steps < 1 || a->steps > kMaxEvalSteps) return bad_arg(who, "steps must be in 1 .. 256");
+    if (!(a->thr_max >= a->thr_min)) return bad_arg(who, "thr_max must not be below thr_min");
+    if (!a->pred_joints_cam) return bad_arg(who, "pred_joints_cam is NULL");
+    if (!a->gt_joints_cam) return bad_arg(who, "gt_joints_cam is NULL");
+    if (!a->pred_joints_2d) return bad_arg(who, "pred_joints_2d is NULL");
+    if (!a->gt_joints_2d) return bad_arg(who, "gt_joints_2d is NULL");
+    if (!a->state || ((uintptr_t)a->state & 7)) return bad_arg(who, "state is NULL or not 8-byte aligned");
+    if (a->state_doubles < state_need) return bad_arg(who, state_msg);
+    return HMV_OK;
+}
 
 }  // namespace hmv

@@ -20,30 +20,15 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/handmv.h"
 #include "kernels.h"
+#include "pose_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int NJ = 21;
 constexpr int kMaxProfile = 256;   // hm_h + hm_w: 21 * 256 fp64 profile values + the reduction buffer fit the 64 KB of LDS
 constexpr int kMaxSigma = 8;
-
-// Fixed-order tree reduction over the workgroup; every lane gets the total.
-__device__ double block_sum(double v, double *red) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // Output pixel i (of n) of one axis of the target map: the cropped 1-D Gaussian around trunc(p) on S source pixels through
 // the antialiased bilinear filter of torch's _upsample_bilinear2d_aa (scale = S / n; support = scale when down-sampling, else 1;
@@ -164,14 +149,69 @@ __global__ __launch_bounds__(kThreads) void project_joints_kernel(const float *_
 // the targets are rebuilt from the frame's label joints through the same target_at as (a), so both forms see the same fp32
 // values.  The elements are walked in groups of four (16-byte loads where both frame bases allow, scalar loads otherwise) and
 // added in the same order either way, so neither alignment nor the target form changes the bits.
+// Frame slot f by its workgroup.  lds: the reduction buffer (kThreads doubles) with the profile area behind it.
+__device__ __forceinline__ void frame_partial(const float *__restrict__ pred, const float *__restrict__ target,
+                                              const float *__restrict__ labels, int S, int h, int w, int sigma,
+                                              double *__restrict__ partial, long f, double *lds) {
+    const int t = threadIdx.x;
+    double *prof = lds + kThreads;
+    if (!target) fill_profiles(labels + f * NJ * 2, S, h, w, sigma, prof);
+    const int len = NJ * h * w;
+    const float *p = pred + f * len;
+    const float *g = target ? target + f * len : nullptr;
+    const bool vec = ((uintptr_t)p & 15) == 0 && (!g || ((uintptr_t)g & 15) == 0);
+    const int groups = (len + 3) / 4;
+    double acc = 0.0;
+    for (int q = t; q < groups; q += kThreads) {
+        const int e0 = q * 4;
+        const int cnt = min(4, len - e0);
+        float pv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec && cnt == 4) {
+            const float4 a = *reinterpret_cast<const float4 *>(p + e0);
+            pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w;
+            if (g) {
+                const float4 b = *reinterpret_cast<const float4 *>(g + e0);
+                gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < cnt) {
+                    pv[k] = p[e0 + k];
+                    if (g) gv[k] = g[e0 + k];
+                }
+        }
+        if (!g) {   // target_at(prof, e0 + k, h, w) for the group, with the (joint, row, column) split done once
+            const int hw = h * w;
+            int j = e0 / hw;
+            const int rem = e0 - j * hw;
+            int y = rem / w, x = rem - y * w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < cnt) {
+                    const double *pj = prof + j * (h + w);
+                    gv[k] = (float)(pj[w + y] * pj[x]);
+                    if (++x == w) {
+                        x = 0;
+                        if (++y == h) { y = 0; ++j; }
+                    }
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {   // lanes past the end hold 0 - 0
+            const double d = (double)pv[k] - (double)gv[k];
+            acc = fma(d, d, acc);
+        }
+    }
+    const double s = block_sum<kThreads>(acc, lds);
+    if (t == 0) partial[f] = s;
+}
+
 __global__ __launch_bounds__(kThreads) void pose_losses_kernel(const float *__restrict__ pred, const float *__restrict__ target,
                                                               const float *__restrict__ labels, int S, int h, int w, int sigma,
                                                               double *__restrict__ partial) {
     extern __shared__ double lds[];
-    double *prof = lds + kThreads;   // lds[0 .. kThreads): the reduction buffer
-    const long f = blockIdx.x;
-    const int t = threadIdx.x;
-#include "pose_losses_body.inc"
+    frame_partial(pred, target, labels, S, h, w, sigma, partial, blockIdx.x, lds);
 }
 
 // (c) for a ragged view set, first launch: the same per frame slot; the workgroup of an ABSENT slot writes partial 0 and leaves before
@@ -182,13 +222,11 @@ __global__ __launch_bounds__(kThreads) void pose_losses_views_kernel(const float
                                                                     const uint8_t *__restrict__ present, double *__restrict__ partial) {
     extern __shared__ double lds[];
     const long f = blockIdx.x;
-    const int t = threadIdx.x;
     if (!present[f]) {
-        if (t == 0) partial[f] = 0.0;
+        if (threadIdx.x == 0) partial[f] = 0.0;
         return;
     }
-    double *prof = lds + kThreads;
-#include "pose_losses_body.inc"
+    frame_partial(pred, target, labels, S, h, w, sigma, partial, f, lds);
 }
 
 struct FinishParams {
@@ -201,27 +239,51 @@ struct FinishParams {
 };
 
 // (c), second launch (one workgroup): the frame partials in index order, the L1 terms, the reprojection terms, the total.
-__global__ __launch_bounds__(kThreads) void pose_losses_finish_kernel(FinishParams a) {
+//
+// kRagged, a ragged view set (present: [B][V]): the value of a view-dependent term is the mean over samples of the sample's own mean
+// over its v_b present views: sum_b sum_{v in P_b} x / (v_b * n) / B.  Written as
+//     sum over ALL slots, in the uniform order, of (present ? x : 0) * (V / v_b),  divided by the uniform divisor B * V * n,
+// so that a full mask (V / v_b == 1.0 exactly) walks through the uniform instantiation's additions and gives its bits.  An absent
+// slot's rows are not read.  A sample WITHOUT a present view (a broken precondition) has V / 0 = inf, its slots add 0 * inf: the
+// view-dependent terms come out NaN, and nothing is indexed by a count.
+// The uniform instantiation is the same statements with every slot there and the weight the literal 1.0 (x * 1.0 is x): it tests no
+// `present` and has no count array.
+template <bool kRagged>
+__device__ __forceinline__ void losses_finish(const FinishParams &a, const uint8_t *__restrict__ present, const int *cnt) {
     __shared__ double red[kThreads];
     const int t = threadIdx.x;
+    auto there = [&](long slot) {
+        if constexpr (kRagged) return present[slot] != 0;
+        else return true;
+    };
+    auto weight = [&](long b) {
+        if constexpr (kRagged) return view_weight(present, cnt, b, a.V);
+        else return 1.0;
+    };
+
     const long frames = (long)a.B * a.V;
     double s = 0.0;
-    for (long i = t; i < frames; i += kThreads) s += a.partial[i];
-    const double hm = block_sum(s, red);
+    for (long i = t; i < frames; i += kThreads) s += a.partial[i] * weight(i / a.V);   // an absent slot's partial is the first launch's 0
+    const double hm = block_sum<kThreads>(s, red);
 
     // joints_2d: masked joints are zeroed on both sides, the divisor stays the full count (models/utils.py:123-131)
     const long n2 = frames * NJ * 2;
     s = 0.0;
     for (long e = t; e < n2; e += kThreads) {
-        const double keep = (a.use_mask && a.mask[e >> 1]) ? 0.0 : 1.0;
-        s += fabs((double)a.pred_2d[e] * keep - (double)a.gt_2d[e] * keep);
+        const long bv = e / (NJ * 2);
+        double d = 0.0;
+        if (there(bv)) {
+            const double keep = (a.use_mask && a.mask[e >> 1]) ? 0.0 : 1.0;
+            d = fabs((double)a.pred_2d[e] * keep - (double)a.gt_2d[e] * keep);
+        }
+        s += d * weight(bv / a.V);
     }
-    const double l2d = block_sum(s, red);
+    const double l2d = block_sum<kThreads>(s, red);
 
     const long n3 = (long)a.B * NJ * 3;
     s = 0.0;
     for (long e = t; e < n3; e += kThreads) s += fabs((double)a.pred_cam[e] - (double)a.gt_cam[e]);
-    const double l3d = block_sum(s, red);
+    const double l3d = block_sum<kThreads>(s, red);
 
     double g2d = 0.0, p2d = 0.0;
     if (a.with_projection) {
@@ -230,18 +292,23 @@ __global__ __launch_bounds__(kThreads) void pose_losses_finish_kernel(FinishPara
             const long bv = i / NJ;
             const int j = (int)(i - bv * NJ);
             const long b = bv / a.V;
-            double u, v;
-            project_joint(a.pred_cam + (b * NJ + j) * 3, a.root_joint ? a.root_joint + b * 3 : nullptr,
-                          a.extrinsic + (b * a.V + a.root_idx) * 16, a.extrinsic + bv * 16, a.intrinsic + bv * 4, a.bbox + bv * 4, u, v);
-            if (a.projected) {
+            double u = 0.0, v = 0.0, dg = 0.0, dp = 0.0;
+            if (there(bv)) {   // the camera tables are full [B][V]: the root camera's row is read whether or not its frame is present
+                project_joint(a.pred_cam + (b * NJ + j) * 3, a.root_joint ? a.root_joint + b * 3 : nullptr,
+                              a.extrinsic + (b * a.V + a.root_idx) * 16, a.extrinsic + bv * 16, a.intrinsic + bv * 4, a.bbox + bv * 4, u, v);
+                dg = fabs(u - (double)a.gt_2d[i * 2]) + fabs(v - (double)a.gt_2d[i * 2 + 1]);
+                dp = fabs(u - (double)a.pred_2d[i * 2]) + fabs(v - (double)a.pred_2d[i * 2 + 1]);
+            }
+            if (a.projected) {   // zeros for an absent slot
                 a.projected[i * 2] = (float)u;
                 a.projected[i * 2 + 1] = (float)v;
             }
-            sg += fabs(u - (double)a.gt_2d[i * 2]) + fabs(v - (double)a.gt_2d[i * 2 + 1]);
-            sp += fabs(u - (double)a.pred_2d[i * 2]) + fabs(v - (double)a.pred_2d[i * 2 + 1]);
+            const double wgt = weight(b);
+            sg += dg * wgt;
+            sp += dp * wgt;
         }
-        g2d = block_sum(sg, red);
-        p2d = block_sum(sp, red);
+        g2d = block_sum<kThreads>(sg, red);
+        p2d = block_sum<kThreads>(sp, red);
     }
     if (t == 0) {
         const double t_hm = (double)a.w_hm * hm / ((double)frames * NJ * a.hm_h * a.hm_w);
@@ -258,101 +325,18 @@ __global__ __launch_bounds__(kThreads) void pose_losses_finish_kernel(FinishPara
     }
 }
 
-// Present views of one sample: its row of the view mask, counted.
-__device__ __forceinline__ int count_views(const uint8_t *__restrict__ row, int V) {
-    int n = 0;
-    for (int v = 0; v < V; ++v) n += row[v] != 0;
-    return n;
-}
+// Two kernels and not one with a nullable mask: the uniform one is the reference the tests hold the ragged one to under a full mask.
+__global__ __launch_bounds__(kThreads) void pose_losses_finish_kernel(FinishParams a) { losses_finish<false>(a, nullptr, nullptr); }
 
-constexpr int kCountSlots = 1024;   // samples whose count is kept in LDS; a sample beyond them has its mask row counted when asked
-
-// (c) for a ragged view set, second launch (one workgroup).  The value of a view-dependent term is the mean over samples of the
-// sample's own mean over its v_b present views: sum_b sum_{v in P_b} x / (v_b * n) / B.  Written as
-//     sum over ALL slots, in the uniform kernel's order, of (present ? x : 0) * (V / v_b),  divided by the uniform divisor B * V * n,
-// so that a full mask (V / v_b == 1.0 exactly) walks through the uniform kernel's additions and gives its bits.  An absent slot's
-// rows are not read.  A sample WITHOUT a present view (a broken precondition) has V / 0 = inf, its slots add 0 * inf: the
-// view-dependent terms come out NaN, and nothing is indexed by a count.
 __global__ __launch_bounds__(kThreads) void pose_losses_views_finish_kernel(FinishParams a, const uint8_t *__restrict__ present) {
-    __shared__ double red[kThreads];
     __shared__ int cnt[kCountSlots];
-    const int t = threadIdx.x;
-    for (int b = t; b < a.B && b < kCountSlots; b += kThreads) cnt[b] = count_views(present + (long)b * a.V, a.V);
+    fill_view_counts<kThreads>(cnt, present, a.B, a.V);
     __syncthreads();
-    auto weight = [&](long b) { return (double)a.V / (double)(b < kCountSlots ? cnt[b] : count_views(present + b * a.V, a.V)); };
-
-    const long frames = (long)a.B * a.V;
-    double s = 0.0;
-    for (long i = t; i < frames; i += kThreads) s += a.partial[i] * weight(i / a.V);   // an absent slot's partial is the first launch's 0
-    const double hm = block_sum(s, red);
-
-    const long n2 = frames * NJ * 2;
-    s = 0.0;
-    for (long e = t; e < n2; e += kThreads) {
-        const long bv = e / (NJ * 2);
-        double d = 0.0;
-        if (present[bv]) {
-            const double keep = (a.use_mask && a.mask[e >> 1]) ? 0.0 : 1.0;
-            d = fabs((double)a.pred_2d[e] * keep - (double)a.gt_2d[e] * keep);
-        }
-        s += d * weight(bv / a.V);
-    }
-    const double l2d = block_sum(s, red);
-
-    const long n3 = (long)a.B * NJ * 3;
-    s = 0.0;
-    for (long e = t; e < n3; e += kThreads) s += fabs((double)a.pred_cam[e] - (double)a.gt_cam[e]);
-    const double l3d = block_sum(s, red);
-
-    double g2d = 0.0, p2d = 0.0;
-    if (a.with_projection) {
-        double sg = 0.0, sp = 0.0;
-        for (long i = t; i < frames * NJ; i += kThreads) {
-            const long bv = i / NJ;
-            const int j = (int)(i - bv * NJ);
-            const long b = bv / a.V;
-            double u = 0.0, v = 0.0, dg = 0.0, dp = 0.0;
-            if (present[bv]) {   // the camera tables are full [B][V]: the root camera's row is read whether or not its frame is present
-                project_joint(a.pred_cam + (b * NJ + j) * 3, a.root_joint ? a.root_joint + b * 3 : nullptr,
-                              a.extrinsic + (b * a.V + a.root_idx) * 16, a.extrinsic + bv * 16, a.intrinsic + bv * 4, a.bbox + bv * 4, u, v);
-                dg = fabs(u - (double)a.gt_2d[i * 2]) + fabs(v - (double)a.gt_2d[i * 2 + 1]);
-                dp = fabs(u - (double)a.pred_2d[i * 2]) + fabs(v - (double)a.pred_2d[i * 2 + 1]);
-            }
-            if (a.projected) {   // zeros for an absent slot
-                a.projected[i * 2] = (float)u;
-                a.projected[i * 2 + 1] = (float)v;
-            }
-            const double wgt = weight(b);
-            sg += dg * wgt;
-            sp += dp * wgt;
-        }
-        g2d = block_sum(sg, red);
-        p2d = block_sum(sp, red);
-    }
-    if (t == 0) {
-        const double t_hm = (double)a.w_hm * hm / ((double)frames * NJ * a.hm_h * a.hm_w);
-        const double t_2d = (double)a.w_2d * l2d / (double)n2;
-        const double t_3d = (double)a.w_3d * l3d / (double)n3;
-        const double t_g = a.with_projection ? (double)a.w_g2d * g2d / (double)n2 : 0.0;
-        const double t_p = a.with_projection ? (double)a.w_p2d * p2d / (double)n2 : 0.0;
-        a.result[0] = (float)t_hm;
-        a.result[1] = (float)t_2d;
-        a.result[2] = (float)t_3d;
-        a.result[3] = (float)t_g;
-        a.result[4] = (float)t_p;
-        a.result[5] = (float)(t_hm + t_2d + t_3d + t_g + t_p);
-    }
+    losses_finish<true>(a, present, cnt);
 }
 
-int bad_arg(const char *entry, const char *what) {
-    hmv::set_thread_error(std::string(entry) + ": " + what);
-    return HMV_ERR_ARG;
-}
-
-int hip_fail(const char *entry, hipError_t e) {
-    hmv::set_thread_error(std::string(entry) + ": " + hipGetErrorString(e));
-    return HMV_ERR_HIP;
-}
+using hmv::bad_arg;
+using hmv::hip_fail;
 
 // shape rules shared by the entries that build target maps
 const char *check_map_shape(int32_t image_size, int32_t hm_h, int32_t hm_w, int32_t sigma) {

@@ -14,6 +14,8 @@
 
 namespace {
 
+constexpr int kThreads = 1024;   // the one workgroup of the launch
+
 // result: [0] mean distance, [1] mean distance after similarity alignment (NaN when not requested),
 //         [2] auc, [3] norm_auc, [4 .. 4+steps) pck values, [4+steps .. 4+2*steps) thresholds.
 __global__ __launch_bounds__(kThreads) void pose_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -32,11 +34,11 @@ __global__ __launch_bounds__(kThreads) void pose_metrics_kernel(const float* __r
     const long rows = (long)n_sets * n_pts;
     double dsum = 0.0;
     for (long r = t; r < rows; r += kThreads) {
-        const float dist = row_distance(pred + r * dim, gt + r * dim, dim);
+        const float dist = distance_n(pred + r * dim, gt + r * dim, dim);
         dsum += (double)dist;
         atomicAdd(&hist[threshold_bin(dist, thr, steps)], 1);
     }
-    const double mean_dist = block_sum(dsum, red) / (double)rows;
+    const double mean_dist = block_sum<kThreads>(dsum, red) / (double)rows;
 
     // ---- PA-MPJPE: similarity transform of each predicted pose onto its target (metrics.py:128-176)
     double pasum = 0.0;
@@ -44,13 +46,19 @@ __global__ __launch_bounds__(kThreads) void pose_metrics_kernel(const float* __r
         for (int sidx = t; sidx < n_sets; sidx += kThreads) {
             const float* p = pred + (long)sidx * n_pts * 3;
             const float* g = gt + (long)sidx * n_pts * 3;
-            POSE_MOMENTS(p, g, n_pts, mu1, mu2, var1, K)
+            PoseMoments m;
+            pose_moments(p, g, n_pts, m);
             double U[3][3], S[3], V[3][3];
-            svd3(K, U, S, V);
-            POSE_ADD_ALIGNED_ERROR(p, g, n_pts, mu1, mu2, var1, K, U, V, aligned, (long)sidx * n_pts, pasum)
+            svd3(m.K, U, S, V);
+            float* out = aligned ? aligned + (long)sidx * n_pts * 3 : nullptr;
+            pose_aligned_points(p, g, n_pts, m, U, V, [&](int j, const double* y, double dist) {
+                if (out)
+                    for (int c = 0; c < 3; ++c) out[j * 3 + c] = (float)y[c];
+                pasum += dist;
+            });
         }
     }
-    const double pa_mean = block_sum(pasum, red) / (double)rows;
+    const double pa_mean = block_sum<kThreads>(pasum, red) / (double)rows;
 
     if (t == 0) {
         result[0] = (float)mean_dist;

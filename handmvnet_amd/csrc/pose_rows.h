@@ -1,24 +1,29 @@
-// Device code shared by the evaluation kernels (metrics.hip: one step's metrics; eval_epoch.hip: an epoch's running sums), so
-// that the two cannot drift apart: the workgroup reduction, the 3x3 SVD, and the per-row arithmetic of models/metrics.py --
-// thresholds as torch.linspace builds them, the fp32 joint distance, its PCK bin, the similarity alignment of one pose (two macros, below).
-// The arithmetic that decides a comparison (joint distance vs threshold) is fp32 like the reference's; sums and the 3x3 Procrustes
-// problem run in fp64.  Both kernels are single-workgroup launches of kThreads lanes.
+// Device code shared by the evaluation kernels (metrics.hip: one step's metrics; eval_epoch.hip: an epoch's running sums;
+// eval_breakdown.hip: the same by joint, camera and sample; losses.hip: the step's losses; hand_ik.hip uses svd3), as functions, so
+// that they cannot drift apart: the workgroup reduction, the 3x3 SVD, the present-view count of a ragged sample, and the per-row
+// arithmetic of models/metrics.py -- thresholds as torch.linspace builds them, the fp32 joint distance, its PCK bin, the similarity
+// alignment of one pose.  The arithmetic that decides a comparison (joint distance vs threshold) is fp32 like the reference's and
+// written out under contract(off): its roundings are the source's, not the optimiser's.  Sums and the 3x3 Procrustes problem run
+// in fp64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int NJ = 21;
 constexpr int kMaxSteps = 256;
+constexpr int kCountSlots = 1024;   // samples whose present-view count is kept in LDS; a sample beyond them has its mask row counted when asked
 
-// Fixed-order tree reduction over the workgroup; every lane gets the total.
+// Fixed-order tree reduction over a workgroup of N lanes (red: N doubles of LDS); every lane gets the total.
+template <int N>
 __device__ double block_sum(double v, double* red) {
     const int t = threadIdx.x;
     __syncthreads();
     red[t] = v;
     __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
+    for (int s = N / 2; s > 0; s >>= 1) {
         if (t < s) red[t] += red[t + s];
         __syncthreads();
     }
@@ -27,7 +32,7 @@ __device__ double block_sum(double v, double* red) {
 
 // One-sided Jacobi (Hestenes) SVD of a 3x3 matrix: a = u * diag(s) * v^T, s descending.
 // A column of u that belongs to a zero singular value is completed with the cross product of the others.
-__device__ void svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3]) {
+[[maybe_unused]] __device__ void svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3]) {
     double w[3][3];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
@@ -109,7 +114,7 @@ __device__ void svd3(const double a[3][3], double u[3][3], double s[3], double v
     }
 }
 
-__device__ double det3(const double m[3][3]) {
+[[maybe_unused]] __device__ double det3(const double m[3][3]) {
     return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
            m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
 }
@@ -125,12 +130,31 @@ __device__ __forceinline__ void fill_thresholds(float* thr, float tmin, float tm
     }
 }
 
-// |p - g| of one row of `dim` coordinates, in fp32 (metrics.py:12, 77)
-__device__ __forceinline__ float row_distance(const float* p, const float* g, int dim) {
+// |p - g| in fp32 (metrics.py:12, 77).  A distance is compared with a threshold, and a last-bit difference moves it into another PCK
+// bin, so every multiply-add below is spelled out under contract(off): which squares are rounded on their own and which are fused is
+// stated here and no longer picked by the optimiser from what surrounds a call.  The forms are the ones this library has always
+// computed (what the kernels compiled to before they were pinned); they differ in the last bit, so they stay apart:
+//   distance_3, distance_2   the epoch kernels and the breakdown, whose sums and bins must agree with each other
+//   distance_n               pose_metrics_kernel, whose `dim` (1 .. 4) is a run-time value: a chain of fmas from 0, so at dim 3 its
+//                            last square is fused where distance_3 rounds it
+__device__ __forceinline__ float distance_3(const float* p, const float* g) {
+#pragma clang fp contract(off)
+    const float d0 = p[0] - g[0], d1 = p[1] - g[1], d2 = p[2] - g[2];
+    return sqrtf(fmaf(d1, d1, d0 * d0) + d2 * d2);
+}
+
+__device__ __forceinline__ float distance_2(const float* p, const float* g) {
+#pragma clang fp contract(off)
+    const float d0 = p[0] - g[0], d1 = p[1] - g[1];
+    return sqrtf(d0 * d0 + d1 * d1);
+}
+
+__device__ __forceinline__ float distance_n(const float* p, const float* g, int dim) {
+#pragma clang fp contract(off)
     float acc = 0.f;
     for (int c = 0; c < dim; ++c) {
         const float d = p[c] - g[c];
-        acc += d * d;
+        acc = fmaf(d, d, acc);
     }
     return sqrtf(acc);
 }
@@ -142,63 +166,89 @@ __device__ __forceinline__ int threshold_bin(float dist, const float* thr, int s
     return b;
 }
 
+// Present views of one sample of a ragged view set: its row of the view mask [B][V] (non-zero = the view is there), counted.
+__device__ __forceinline__ int count_views(const uint8_t* __restrict__ row, int V) {
+    int n = 0;
+    for (int v = 0; v < V; ++v) n += row[v] != 0;
+    return n;
+}
+
+// cnt[b] = the present views of sample b, for the first kCountSlots samples, by a workgroup of N lanes; the caller synchronises.
+template <int N>
+__device__ __forceinline__ void fill_view_counts(int* cnt, const uint8_t* __restrict__ present, int B, int V) {
+    for (int b = threadIdx.x; b < B && b < kCountSlots; b += N) cnt[b] = count_views(present + (long)b * V, V);
+}
+
+// V / v_b, what a present row of sample b adds its value times so that the sum over all slots, divided by the uniform divisor, is the
+// mean over samples of each sample's own mean over its v_b present views.  Exactly 1.0 for a full sample.  A sample without a present
+// view (a broken precondition) gives V / 0 = inf; nothing is indexed by a count.
+__device__ __forceinline__ double view_weight(const uint8_t* __restrict__ present, const int* cnt, long b, int V) {
+    return (double)V / (double)(b < kCountSlots ? cnt[b] : count_views(present + b * V, V));
+}
+
+// The similarity transform of one predicted pose p [n_pts][3] onto its target g (metrics.py:128-176), in two pieces around
+// svd3(m.K, U, S, V): the moments, and the transformed points.
+struct PoseMoments {
+    double mu1[3], mu2[3];   // the means of p and g
+    double var1;             // the variance of p
+    double K[3][3];          // the cross-covariance
+};
+
+__device__ __forceinline__ void pose_moments(const float* p, const float* g, int n_pts, PoseMoments& m) {
+    for (int c = 0; c < 3; ++c) m.mu1[c] = m.mu2[c] = 0.0;
+    for (int j = 0; j < n_pts; ++j)
+        for (int c = 0; c < 3; ++c) {
+            m.mu1[c] += p[j * 3 + c];
+            m.mu2[c] += g[j * 3 + c];
+        }
+    for (int c = 0; c < 3; ++c) {
+        m.mu1[c] /= n_pts;
+        m.mu2[c] /= n_pts;
+    }
+    m.var1 = 0.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) m.K[a][b] = 0.0;
+    for (int j = 0; j < n_pts; ++j) {
+        double x1[3], x2[3];
+        for (int c = 0; c < 3; ++c) {
+            x1[c] = p[j * 3 + c] - m.mu1[c];
+            x2[c] = g[j * 3 + c] - m.mu2[c];
+            m.var1 += x1[c] * x1[c];
+        }
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) m.K[a][b] += x1[a] * x2[b];
+    }
+}
+
+// From the moments and the U, V of svd3(m.K, ...): point(j, y, dist) for every point j, with its transformed coordinates y[3] and the
+// distance to g's point that remains.
+template <typename F>
+__device__ __forceinline__ void pose_aligned_points(const float* p, const float* g, int n_pts, const PoseMoments& m, const double U[3][3],
+                                                    const double V[3][3], F&& point) {
+    // Z = diag(1, 1, sign(det(U V^T)));  R = V Z U^T
+    double UVt[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) UVt[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + U[a][2] * V[b][2];
+    const double dd = det3(UVt);
+    const double z = dd > 0 ? 1.0 : (dd < 0 ? -1.0 : 0.0);
+    double R[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[a][b] = V[a][0] * U[b][0] + V[a][1] * U[b][1] + z * V[a][2] * U[b][2];
+    double trace = 0.0;   // trace(R K)
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) trace += R[a][b] * m.K[b][a];
+    const double scale = trace / m.var1;
+    double tr[3];
+    for (int a = 0; a < 3; ++a) tr[a] = m.mu2[a] - scale * (R[a][0] * m.mu1[0] + R[a][1] * m.mu1[1] + R[a][2] * m.mu1[2]);
+    for (int j = 0; j < n_pts; ++j) {
+        double y[3], e2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            y[a] = scale * (R[a][0] * p[j * 3] + R[a][1] * p[j * 3 + 1] + R[a][2] * p[j * 3 + 2]) + tr[a];
+            const double e = y[a] - (double)g[j * 3 + a];
+            e2 += e * e;
+        }
+        point(j, y, sqrt(e2));
+    }
+}
+
 }  // namespace
-
-// The similarity transform of one predicted pose p [n_pts][3] (const float*) onto its target g (metrics.py:128-176), in two pieces.
-// Macros on purpose.  As inlined functions the same statements reach the optimiser in another order, svd3's arrays are promoted
-// differently and pose_metrics_kernel's code changes; shared as text, that kernel's device assembly stays what it was before the
-// epoch kernel existed (tools/isa_diff.py), and both kernels still have one copy of the arithmetic.
-
-// Declares, in the enclosing scope, the means mu1 / mu2 (double[3]), the variance var1 of p and the cross-covariance K (double[3][3]).
-#define POSE_MOMENTS(p, g, n_pts, mu1, mu2, var1, K)                                                                              \
-    double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};                                                                                \
-    for (int j = 0; j < (n_pts); ++j)                                                                                             \
-        for (int c = 0; c < 3; ++c) {                                                                                             \
-            mu1[c] += (p)[j * 3 + c];                                                                                             \
-            mu2[c] += (g)[j * 3 + c];                                                                                             \
-        }                                                                                                                         \
-    for (int c = 0; c < 3; ++c) {                                                                                                 \
-        mu1[c] /= (n_pts);                                                                                                        \
-        mu2[c] /= (n_pts);                                                                                                        \
-    }                                                                                                                             \
-    double var1 = 0.0, K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};                                                               \
-    for (int j = 0; j < (n_pts); ++j) {                                                                                           \
-        double x1[3], x2[3];                                                                                                      \
-        for (int c = 0; c < 3; ++c) {                                                                                             \
-            x1[c] = (p)[j * 3 + c] - mu1[c];                                                                                      \
-            x2[c] = (g)[j * 3 + c] - mu2[c];                                                                                      \
-            var1 += x1[c] * x1[c];                                                                                                \
-        }                                                                                                                         \
-        for (int a = 0; a < 3; ++a)                                                                                               \
-            for (int b = 0; b < 3; ++b) K[a][b] += x1[a] * x2[b];                                                                 \
-    }
-
-// From the moments and svd3(K, U, S, V): adds to the double `sum`, point by point, the distance that remains after the transform.
-// aligned (float*, may be null): the base of a [poses][n_pts][3] output whose rows row0 .. row0 + n_pts - 1 receive the transformed points.
-#define POSE_ADD_ALIGNED_ERROR(p, g, n_pts, mu1, mu2, var1, K, U, V, aligned, row0, sum)                                          \
-    /* Z = diag(1, 1, sign(det(U V^T)));  R = V Z U^T */                                                                          \
-    double UVt[3][3];                                                                                                             \
-    for (int a = 0; a < 3; ++a)                                                                                                   \
-        for (int b = 0; b < 3; ++b) UVt[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + U[a][2] * V[b][2];                        \
-    const double dd = det3(UVt);                                                                                                  \
-    const double z = dd > 0 ? 1.0 : (dd < 0 ? -1.0 : 0.0);                                                                        \
-    double R[3][3];                                                                                                               \
-    for (int a = 0; a < 3; ++a)                                                                                                   \
-        for (int b = 0; b < 3; ++b) R[a][b] = V[a][0] * U[b][0] + V[a][1] * U[b][1] + z * V[a][2] * U[b][2];                      \
-    double trace = 0.0; /* trace(R K) */                                                                                          \
-    for (int a = 0; a < 3; ++a)                                                                                                   \
-        for (int b = 0; b < 3; ++b) trace += R[a][b] * K[b][a];                                                                   \
-    const double scale = trace / var1;                                                                                            \
-    double tr[3];                                                                                                                 \
-    for (int a = 0; a < 3; ++a)                                                                                                   \
-        tr[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);                                        \
-    for (int j = 0; j < (n_pts); ++j) {                                                                                           \
-        double e2 = 0.0;                                                                                                          \
-        for (int a = 0; a < 3; ++a) {                                                                                             \
-            const double y = scale * (R[a][0] * (p)[j * 3] + R[a][1] * (p)[j * 3 + 1] + R[a][2] * (p)[j * 3 + 2]) + tr[a];        \
-            if (aligned) (aligned)[((row0) + j) * 3 + a] = (float)y;                                                              \
-            const double e = y - (double)(g)[j * 3 + a];                                                                          \
-            e2 += e * e;                                                                                                          \
-        }                                                                                                                         \
-        (sum) += sqrt(e2);                                                                                                        \
-    }

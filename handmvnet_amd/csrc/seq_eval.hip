@@ -183,15 +183,8 @@ __global__ __launch_bounds__(kWave) void seq_eval_add_kernel(SeqParams a) {
     }
 }
 
-int bad_arg(const char *who, const char *what) {
-    hmv::set_thread_error(std::string(who) + ": " + what);
-    return HMV_ERR_ARG;
-}
-
-int hip_fail(const char *who, hipError_t e) {
-    hmv::set_thread_error(std::string(who) + ": " + hipGetErrorString(e));
-    return HMV_ERR_HIP;
-}
+using hmv::bad_arg;
+using hmv::hip_fail;
 
 }  // namespace
 

@@ -100,10 +100,8 @@ __global__ __launch_bounds__(kWave * kRowsPerBlock) void next_crop_boxes_kernel(
     if (a.status && lane == 0) a.status[slot] = st;
 }
 
-int bad_arg(const char *who, const char *what) {
-    hmv::set_thread_error(std::string(who) + ": " + what);
-    return HMV_ERR_ARG;
-}
+using hmv::bad_arg;
+using hmv::hip_fail;
 
 }  // namespace
 
@@ -129,6 +127,5 @@ extern "C" int hmv_op_next_crop_boxes(int32_t device, int32_t n_slots, const flo
     hmv::TrackParams p{n_slots, n_slots, joints_crop_img, crop_boxes_in, present, nullptr, image_size, margin, square != 0,
                        crop_boxes_out, bbox_out, joints_img, status};
     const hipError_t e = hmv::launch_next_crop_boxes(p, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { hmv::set_thread_error(std::string(who) + ": " + hipGetErrorString(e)); return HMV_ERR_HIP; }
-    return HMV_OK;
+    return e == hipSuccess ? HMV_OK : hip_fail(who, e);
 }

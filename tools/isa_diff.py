@@ -12,7 +12,7 @@ import hashlib, json, re, sys
 def kernels(path):
     t = open(path).read()
     out = {}
-    for m in re.finditer(r'\t\.globl\t(\S+)\n(?:(?!\t\.globl\t).)*?\.end_amdhsa_kernel', t, re.S):
+    for m in re.finditer(r'\t\.globl\t(\S+)[^\n]*\n(?:(?!\t\.globl\t).)*?\.end_amdhsa_kernel', t, re.S):   # (the line may end in a comment)
         body = re.sub(r'[ \t]*;.*', '', m.group(0))      # comments: they carry function indices and are column-aligned
         body = re.sub(r'BB\d+_', 'BB_', body)            # .LBB<function index>_<block>
         body = re.sub(r'\.Lfunc_end\d+', '.Lfunc_end', body).replace(m.group(1), '@SELF@')

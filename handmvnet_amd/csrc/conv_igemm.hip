@@ -961,6 +961,93 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
     float *sC = smem;
     const int n0 = nt * BN;
     const bool vec = ((p.ldc & 3) == 0) && (p.res == nullptr || (p.ldr & 3) == 0);
+    // ---- fp32 fast drain: fp32 rows written in place, residual absent or fp32 (every fp32 launch of the backbone).  The format
+    // decisions are wave-uniform, so they are taken once, around the whole pass loop, and a pass is straight-line code.  What that
+    // buys is the order of the vector-memory queue, which retires in issue order and counts stores like loads:
+    //   * no residual: nothing is loaded (the bias vector is fetched once per tile, before the first pass), so no wait stands
+    //     between the row stores of a pass, nor between those of one pass and the next;
+    //   * fp32 residual: the rows of the next group (the next pass's first group after a pass's last) are requested BEFORE the
+    //     stores of this group, into the registers this group's residual has just left, so the counted wait for them never has
+    //     a store ahead of it.  A request in flight must not meet a join of the control flow, where the compiler waits for
+    //     everything: hence one copy of the loop per case, and no branch in it.
+    // Rows past M and columns past the row's end store to the 1 KiB behind the zero page (16 bytes per lane, never read) and read
+    // the zero page.  (v + bias) + 0.f keeps the bits that the load of a zero-page residual gave.
+    // Measured (profiles/r06_drain_*.json): before, every row store of the general drain below sat behind an
+    // `s_waitcnt vmcnt(0)` (the joins of its format branches), one store round trip per row; the epilogue of a 256x256 tile fell
+    // from 12.8 to 6.8 us (1x1, K = 1024) and from 10.8 to 5.3 us (3x3, K = 2304), the cfg-3 fp32 step from 42.23 to 41.78 ms.
+    bool fast = false;
+    if constexpr (!F16 && !GENERIC && !RD && !PARTN) {   // (skipN: its 128x128 kernels would give up a wave per SIMD for the second copy)
+        fast = vec && !(p.out_split | p.out_f16 | p.res_f16 | p.res_split);
+        if (fast) {
+            constexpr int TPR = BN / 4, RPP = NT / TPR, NPASS = SR / RPP;
+            static_assert(SR % RPP == 0 && (NPASS < HMV_UB || NPASS % HMV_UB == 0) && (NPASS < 2 || NPASS % 2 == 0), "staging pass shape");
+            const int c4 = tid % TPR, r0 = tid / TPR;
+            const int col = n0 + 4 * c4;
+            const bool cok = col < ((p.fill || p.Cout + 3 >= p.ldc) ? p.ldc : ((p.Cout + 3) & ~3));   // (the column rule of the drain below)
+            const float *resp = reinterpret_cast<const float *>(p.res) + col;
+            float *outp = reinterpret_cast<float *>(outv) + col;
+            float *trash = const_cast<float *>(p.zero) + 64 + 4 * lane;
+            const float lo = (p.act == ACT_RELU) ? 0.f : -INFINITY;
+            auto row = [&](int ps, int q) {   // the output row that this thread drains as its q-th of pass ps
+                const int sr = r0 + q * RPP;
+                return mt * BM + (sr / (AS * 32)) * WM + (ps * AS + (sr / 32) % AS) * 32 + (sr & 31);
+            };
+            auto drain = [&](auto rtag) {
+                constexpr bool RES = decltype(rtag)::value;
+                // rows per group.  With a residual: 2, since the rows of two groups are in registers at a time (4 cost the
+                // 256x128 / 256x64 / 128x64 kernels a wave per SIMD, and the 4-wave k16 kernel spilled)
+                constexpr int UB = RES ? (NPASS < 2 ? NPASS : 2) : (NPASS < HMV_UB ? NPASS : HMV_UB);
+                f32x4 rv[UB];
+                auto load_res = [&](int ps, int g) {
+#pragma unroll
+                    for (int u = 0; u < UB; ++u) {
+                        const int m = row(ps, g + u);
+                        rv[u] = *reinterpret_cast<const f32x4 *>((cok && m < p.M) ? resp + (size_t)m * p.ldr : p.zero);
+                    }
+                };
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(cok ? p.bias + col : p.zero);
+                if constexpr (RES) load_res(0, 0);
+#pragma unroll
+                for (int pass = 0; pass < TM / AS; ++pass) {
+                    if (pass > 0) __syncthreads();   // the previous pass has been read
+#pragma unroll
+                    for (int aa = 0; aa < AS; ++aa)
+#pragma unroll
+                        for (int b = 0; b < TN; ++b)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) {
+                                const int srow = (wm * AS + aa) * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+                                sC[srow * LDC + wn * WN + b * 32 + l31] = acc[pass * AS + aa][b][e];
+                            }
+                    __syncthreads();
+#pragma unroll
+                    for (int g = 0; g < NPASS; g += UB) {
+                        f32x4 t[UB];
+#pragma unroll
+                        for (int u = 0; u < UB; ++u) t[u] = *reinterpret_cast<const f32x4 *>(&sC[(r0 + (g + u) * RPP) * LDC + 4 * c4]);
+#pragma unroll
+                        for (int u = 0; u < UB; ++u) {
+                            t[u] = t[u] + bv + (RES ? rv[u] : f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) t[u][j] = fmaxf(t[u][j], lo);
+                        }
+                        if constexpr (RES) {
+                            if (g + UB < NPASS) load_res(pass, g + UB);
+                            else if (pass + 1 < TM / AS) load_res(pass + 1, 0);
+                        }
+#pragma unroll
+                        for (int u = 0; u < UB; ++u) {
+                            const int m = row(pass, g + u);
+                            *reinterpret_cast<f32x4 *>((cok && m < p.M) ? outp + (size_t)m * p.ldc : trash) = t[u];
+                        }
+                    }
+                }
+            };
+            if (p.res) drain(std::true_type{});
+            else drain(std::false_type{});
+        }
+    }
+    if (!fast) {
 #pragma unroll
     for (int pass = 0; pass < TM / AS; ++pass) {
         if (pass > 0) __syncthreads();   // the previous pass has been drained
@@ -1012,7 +1099,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                     *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(outv) + (size_t)m * p.ldc + 4 * c4) = t;
             }
         } else if (vec) {
-            if constexpr (!F16) {   // the fp32 kernels keep their hand-tuned 4-wide drain (any restructuring here costs ~3 %)
+            if constexpr (!F16) {   // fp32 kernels: 4-wide drain (the fast drain above takes the formats of the fp32 backbone)
             constexpr int TPR = BN / 4, RPP = NT / TPR, NPASS = SR / RPP, UB = NPASS < HMV_UB ? NPASS : HMV_UB;
             static_assert(TOUT || (SR % RPP == 0 && NPASS % UB == 0), "staging pass shape");   // (the register-epilogue kernels never get here)
             const int c4 = tid % TPR, r0 = tid / TPR;
@@ -1235,6 +1322,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, min_waves(BM, BN, 64 * WGM * WGN, s
                 else reinterpret_cast<float *>(outv)[orow * p.ldc + col] = v;
             }
         }
+    }
     }
     // diagnostic stamps (tools/timeline.py): main-loop shader cycles / 100 MHz ticks, block timeline, CU id
     if (p.dbg && tid == 0) {

@@ -19,6 +19,9 @@ def __getattr__(name):
     if name in ("SubsetSweepEvaluator", "k_of_n", "as_subset_table"):   # camera-subset sweeps (subsets.py)
         from . import subsets
         return getattr(subsets, name)
+    if name in ("OcclusionSweepEvaluator", "cell_rects", "grid_variants"):   # occlusion sweeps from raw frames (occlusion.py)
+        from . import occlusion
+        return getattr(occlusion, name)
     if name in ("JointsToVertices", "hand_ik", "rigid_unapply"):   # hand pose parameters and MANO vertices (ik.py)
         from . import ik
         return getattr(ik, name)

@@ -19,7 +19,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_forward_frames_views_track", "hmv_op_labels_to_windows", "hmv_op_mka", "hmv_seq_eval_sums_doubles",
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
-           "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply"]
+           "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply", "hmv_op_prepare_frames_occluded",
+           "hmv_forward_frames_occlusions"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -210,6 +211,13 @@ def load() -> ctypes.CDLL:
     lib.hmv_op_prepare_frames.argtypes = [ci, fp, ci, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                           ci, ci, fp, vp]
     lib.hmv_op_prepare_frames.restype = ctypes.c_int
+    lib.hmv_op_prepare_frames_occluded.argtypes = [ci, fp, ci, ci, ci, fp, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                                   ci, ci, fp, vp]
+    lib.hmv_op_prepare_frames_occluded.restype = ctypes.c_int
+    # (occ_view: host int32 [n_occ]; occ_rects: device int32 [n_occ][batch][4])
+    lib.hmv_forward_frames_occlusions.argtypes = [vp, ci, fp, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                                  fp, fp, ci, ctypes.POINTER(ci), fp, fp, fp, fp, fp, fp, vp]
+    lib.hmv_forward_frames_occlusions.restype = ctypes.c_int
     lib.hmv_set_graphs.argtypes = [vp, ci]
     lib.hmv_set_graphs.restype = ctypes.c_int
     lib.hmv_graph_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]

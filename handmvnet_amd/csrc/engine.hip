@@ -1223,6 +1223,7 @@ struct FrameSrc {
     int n_src = 0;
     int fh = 0, fw = 0;
     float mean[3] = {0, 0, 0}, std[3] = {1, 1, 1};
+    const int *rects = nullptr;   // hmv_forward_frames_occlusions: packed frame n's occluder, window pixels (device, [n][4])
 };
 // The tracking tail (hmv_forward_frames_track / hmv_forward_frames_views_track): behind the forward, on its stream, the windows
 // (src.boxes) and bbox are moved in place to the box around the joints just found (track.hip)
@@ -1249,6 +1250,7 @@ struct Runner {
     const ViewSet *vs = nullptr;   // not null: a ragged forward (hmv_forward_views); stages are not captured then
     bool sweep = false;            // a camera-subset sweep (hmv_forward_subsets): the token rows leave tokens_stage without PE and pair copy; no stages
     const FrameSrc *src = nullptr;   // the call's frame source (null in the op-level entries): the backbones prepare their input from it
+    float *tokens_dst = nullptr;     // an occlusion sweep: tokens_stage writes its rows here (the caller's, kept) instead of rows of its own
 
     float *alloc(size_t n) {
         float *ptr = A.alloc(n);
@@ -1666,7 +1668,7 @@ struct Runner {
         const HrNet &hr = h->hr;
         const int H = h->cfg.height, W = h->cfg.width;
         Map in4 = act(N, H, W, 3, h16 ? 8 : 4);   // 4 fp32 / 8 fp16 / [hi8 | lo8] per pixel
-        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, split ? 2 : (h16 ? 1 : 0), in4.p, s, /*s2d=*/false, src->index, src->n_src));
+        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, split ? 2 : (h16 ? 1 : 0), in4.p, s, /*s2d=*/false, src->index, src->n_src, src->rects));
         else if (split) LAUNCH(launch_nchw_to_nhwc_split(x, in4.p, N, H, W, s, h->sat));
         else if (h16) LAUNCH(launch_nchw_to_nhwc8_f16(x, in4.p, N, H, W, s));
         else LAUNCH(launch_nchw_to_nhwc4(x, in4.p, N, H, W, s));
@@ -1787,7 +1789,7 @@ struct Runner {
         // as a 4x4 stride-1 conv over the 2x2 space-to-depth frames: 12 fp32 / 16 fp16 (12 + 4 zeros) / [hi16 | lo16] per s2d pixel
         const int Hs = (H + 1) / 2, Ws = (W + 1) / 2, smode = split ? 2 : (h16 ? 1 : 0);
         Map in4 = act(N, Hs, Ws, 12, h16 ? 16 : 12);
-        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, smode, in4.p, s, /*s2d=*/true, src->index, src->n_src));
+        if (src && src->frames) LAUNCH(launch_frames_to_input(src->frames, src->boxes, N, src->fh, src->fw, H, W, src->mean, src->std, smode, in4.p, s, /*s2d=*/true, src->index, src->n_src, src->rects));
         else LAUNCH(launch_nchw_to_s2d(x, in4.p, N, H, W, smode, s, h->sat));
         const int H1 = conv_out(H, 7, 2, 3), W1 = conv_out(W, 7, 2, 3);   // == Hs, Ws
         const int hp = conv_out(H1, 3, 2, 1), wp = conv_out(W1, 3, 2, 1);
@@ -1873,7 +1875,7 @@ struct Runner {
             LAUNCH(hipMemcpyAsync(h->cap_coords, coords, (size_t)N * NJ * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
 
         // ---- sample nets as gather -> conv1x1+BN+ReLU -> bilinear blend (nets.py:46-63; handmvnet.py:185-187)
-        float *tokens = alloc((size_t)N * NJ * ldt);
+        float *tokens = tokens_dst ? tokens_dst : alloc((size_t)N * NJ * ldt);
         int col0 = 0;
         for (int i = 0; i < c.n_levels; ++i) {
             const Map &lv = f.lv[i];
@@ -2168,6 +2170,95 @@ int run_forward_subsets(hmv_engine *h, const ForwardCall &fc, const std::vector<
         R.decoder(ck.nv, X, joints_cam ? joints_cam + (size_t)ck.q0 * NJ * 3 : nullptr);
         R.vs = nullptr;
         bracket_end(br, "subsets_tail");
+    }
+    R.release(rows);
+    return R.rc;
+}
+
+// An occlusion sweep (hmv_forward_frames_occlusions), planned on the host.  Occluded frame q = o * B + b is frame b * V + occ_view[o] under
+// the rectangle rects[q]; the frame stage takes them in `passes` (frames q0 .. q0 + n), the tail runs in `chunks` of virtual samples
+// (1 + n_occ) * B in all: sample b clean, then sample b under variant o).  The call's device table is [index: n_occ * B | the chunks' tables as
+// a subset sweep's], index[q] = the slot b * V + occ_view[o].
+struct OccPass { int q0, n; };
+struct OccPlan {
+    int n_occ = 0;
+    std::vector<OccPass> passes;
+    std::vector<SubsetChunk> chunks;
+    const int32_t *rects = nullptr;                // device [n_occ * B][4]
+    float *crop_occ = nullptr, *hm_occ = nullptr;  // the occluded camera's own 2D output, [n_occ * B][21][2] and [n_occ * B][21][H/8][W/8], or null
+};
+
+// The sweep: the per-frame stage in sweep form (rows without PE and pair copy) on the B * V clean frames, then on the occluded frames pass by
+// pass, all into ONE retained block of token rows [(B * V + n_occ * B) * 21][ldt]; then, as in run_forward_subsets, per chunk the packed rows
+// of its virtual samples and the unchanged ragged fusion and decoder.  Every virtual sample has all V views, so its bits are those of a
+// uniform forward on the frames it stands for.  While profiling, bracketing records "occlusions_frames" (the clean stage, every occluded
+// pass) and "occlusions_tail" (every tail pass).
+int run_forward_occlusions(hmv_engine *h, const ForwardCall &fc, const OccPlan &op, const int32_t *tab, bool dry, Arena &A) {
+    Runner R{h, fc.stream, dry, HMV_OK, A, nullptr, true, &fc.src};
+    const hmv_config &c = h->cfg;
+    const hipStream_t s = fc.stream;
+    if (!dry)
+        if (const int rc = ensure_aux_stream(h)) return rc;
+    auto bracket_begin = [&](const char *label) {   // (an index: nested records may move the list)
+        if (!h->profiling || dry) return (size_t)-1;
+        R.prof_begin(label);
+        return h->prof_used - 1;
+    };
+    auto bracket_end = [&](size_t i, const char *name) {
+        if (i == (size_t)-1) return;
+        h->prof[i].flops = h->prof[i].bytes = 0;
+        R.prof_end(&h->prof[i], name);
+    };
+    const int B = fc.batch, V = c.num_views, N = B * V, M = op.n_occ * B, ldt = h->ldt;
+    size_t hm_frame = 0;   // floats of one frame's heat-maps
+    float *rows = R.alloc((size_t)(N + M) * NJ * ldt);
+    float *no_pairs = nullptr;
+    size_t br = bracket_begin("frames");
+    {
+        R.tokens_dst = rows;
+        const Features f = h->hrnet ? R.hrnet_backbone(N, nullptr) : R.resnet_backbone(N, nullptr);
+        hm_frame = (size_t)NJ * f.hm.H * f.hm.W;
+        R.tokens_stage(f, fc.bbox, fc.intrinsic, fc.joints_crop_img, fc.heatmap, no_pairs);
+    }
+    bracket_end(br, "occlusions_frames");
+    const bool crop_pe = (c.pos_enc & HMV_POS_CROP) != 0;
+    for (const OccPass &ps : op.passes) {
+        br = bracket_begin("occluded");
+        FrameSrc src = fc.src;
+        src.index = tab ? tab + ps.q0 : nullptr;
+        src.n_src = N;
+        src.rects = op.rects ? op.rects + (size_t)ps.q0 * 4 : nullptr;
+        R.src = &src;
+        R.tokens_dst = rows + (size_t)(N + ps.q0) * NJ * ldt;
+        // the slot's bbox and intrinsic rows (the crop-FoV columns of the token rows)
+        float *bb = crop_pe ? R.alloc((size_t)ps.n * 4) : nullptr, *in = crop_pe ? R.alloc((size_t)ps.n * 4) : nullptr;
+        if (crop_pe) R.launch("gather_rows4", [&] { return launch_gather_rows4(fc.bbox, fc.intrinsic, src.index, ps.n, N, bb, in, s); });
+        float *crop = op.crop_occ ? op.crop_occ + (size_t)ps.q0 * NJ * 2 : R.alloc((size_t)ps.n * NJ * 2);
+        const Features f = h->hrnet ? R.hrnet_backbone(ps.n, nullptr) : R.resnet_backbone(ps.n, nullptr);
+        R.tokens_stage(f, bb, in, crop, op.hm_occ ? op.hm_occ + (size_t)ps.q0 * hm_frame : nullptr, no_pairs);
+        if (!op.crop_occ) R.release(crop);
+        R.release(in);
+        R.release(bb);
+        R.src = &fc.src;
+        bracket_end(br, "occlusions_frames");
+    }
+    R.tokens_dst = nullptr;
+    const bool want_pairs = !h->lq && c.fusion_layers > 0 && h->attn[0].qkv.plane;   // (as tokens_stage decides for a forward)
+    const float *pe = (h->lq || !(c.pos_enc & HMV_POS_SIN)) ? nullptr : h->pe;
+    for (const SubsetChunk &ck : op.chunks) {
+        br = bracket_begin("tail");
+        const int32_t *t = tab ? tab + ck.tab : nullptr;
+        const ViewSet vs{ck.n, t, t ? t + ck.nv + 1 : nullptr, NJ * ck.vmax};
+        const int32_t *src = t ? t + ck.nv + 1 + ck.n : nullptr;
+        float *X = R.alloc((size_t)ck.n * NJ * ldt);
+        float *Xpairs = want_pairs ? R.alloc((size_t)ck.n * NJ * ldt) : nullptr;
+        R.launch("tokens_expand_subsets", [&] { return launch_tokens_expand_subsets(rows, ldt, h->d, ck.n, src, vs.fpos, pe, X, Xpairs, s, h->sat); });
+        R.vs = &vs;
+        int Tcur = vs.Tmax;
+        X = h->lq ? R.fusion_learnable_query(ck.nv, X, Tcur) : R.fusion_cross_attn(ck.nv, X, Xpairs, Tcur);
+        R.decoder(ck.nv, X, fc.joints_cam ? fc.joints_cam + (size_t)ck.q0 * NJ * 3 : nullptr);
+        R.vs = nullptr;
+        bracket_end(br, "occlusions_tail");
     }
     R.release(rows);
     return R.rc;
@@ -2620,6 +2711,77 @@ int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const ui
     if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
     h->forget_attention();   // (no attention maps either: a sweep ignores the mask)
     return run_checked(h, fc, 1, run);
+}
+
+/* An occlusion sweep from raw frames (include/handmv.h): the per-frame stage once on the clean frames and once per occluded frame, the
+ * fusion tail per variant.  Everything that can be refused is refused, and the whole call is planned on the host -- passes, tables,
+ * workspace -- before the first launch.  Always eager. */
+int hmv_forward_frames_occlusions(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
+                                  const int32_t *crop_boxes, const float *mean, const float *std, const float *bbox, const float *intrinsic,
+                                  int32_t n_occ, const int32_t *occ_view, const int32_t *occ_rects, float *joints_crop_img, float *joints_cam,
+                                  float *heatmap, float *joints_crop_img_occ, float *heatmap_occ, void *stream) {
+    if (const int rc = check_handle(h)) return rc;
+    if (const int rc = check_frames(h, batch, frames, frame_h, frame_w, crop_boxes, mean, std, joints_crop_img, joints_cam)) return rc;
+    if (n_occ < 1) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_occlusions: n_occ must be at least 1 (got %d)", (int)n_occ);
+    if (!occ_view) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_occlusions: occ_view is null (host int32 [n_occ])");
+    if (!occ_rects) return h->fail(HMV_ERR_ARG, "hmv_forward_frames_occlusions: occ_rects is null (device int32 [n_occ][batch][4])");
+    const int V = h->cfg.num_views;
+    if (((long long)n_occ + 1) * batch > INT32_MAX / (NJ * 3) / std::max(V, 1))   // (before occ_view's n_occ entries are read)
+        return h->fail(HMV_ERR_ARG, "hmv_forward_frames_occlusions: (1 + n_occ) x batch is too large");
+    for (int o = 0; o < n_occ; ++o)
+        if (occ_view[o] < 0 || occ_view[o] >= V)
+            return h->fail(HMV_ERR_ARG, "hmv_forward_frames_occlusions: occ_view[%d] = %d is no camera in [0, %d)", o, (int)occ_view[o], V);
+    if (const int rc = check_crop_pe(h, bbox, intrinsic)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (batch > h->reserved_batch)
+        if (const int rc = hmv_reserve(h, batch)) return rc;
+    // the passes: at most max(batch, reserved batch) * V occluded frames, then at most that many virtual samples each, so that every buffer
+    // of a pass stays within the reservation
+    const int cmax = std::max<int>(batch, h->reserved_batch), M = n_occ * batch, total = M + batch;
+    OccPlan op;
+    op.n_occ = n_occ;
+    op.rects = occ_rects;
+    op.crop_occ = joints_crop_img_occ;
+    op.hm_occ = heatmap_occ;
+    for (int q0 = 0; q0 < M; q0 += cmax * V) op.passes.push_back(OccPass{q0, std::min(cmax * V, M - q0)});
+    ViewsUpload up{nullptr, (size_t)M};
+    for (int q0 = 0; q0 < total; q0 += cmax) {
+        const int nv = std::min(cmax, total - q0);
+        op.chunks.push_back(SubsetChunk{q0, nv, nv * V, V, up.tab_n});
+        up.tab_n += (size_t)nv + 1 + 2 * (size_t)nv * V;
+    }
+    if (const int rc = views_slot(h, up.tab_n, up.slot)) return rc;
+    int32_t *index = up.slot->host;
+    for (int q = 0; q < M; ++q) index[q] = (q % batch) * V + occ_view[q / batch];
+    for (const SubsetChunk &ck : op.chunks) {
+        int32_t *seg = up.slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
+        seg[0] = 0;
+        for (int i = 0, m = 0; i < ck.nv; ++i) {
+            const int q = ck.q0 + i, o = q / batch - 1, b = q % batch;   // o == -1: the clean batch
+            seg[i + 1] = seg[i] + NJ * V;
+            for (int v = 0; v < V; ++v, ++m) {
+                fpos[m] = NJ * v;
+                src[m] = (o >= 0 && v == occ_view[o]) ? batch * V + o * batch + b : b * V + v;
+            }
+        }
+    }
+    const ForwardCall fc{batch, nullptr, frame_src(frames, frame_h, frame_w, crop_boxes, nullptr, 0, mean, std), bbox, intrinsic,
+                         joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
+    auto run = [&](const ForwardCall &c, bool dry, Arena &A) { return run_forward_occlusions(h, c, op, dry ? nullptr : h->views_dev, dry, A); };
+    if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
+    h->forget_attention();   // (no attention maps: a sweep ignores the mask)
+    return run_checked(h, fc, 1, run);
+}
+
+int hmv_op_prepare_frames_occluded(int32_t device, const uint8_t *frames, int32_t n_frames, int32_t frame_h, int32_t frame_w,
+                                   const int32_t *crop_boxes, const int32_t *occ_rects, const float *mean, const float *std, int32_t out_h,
+                                   int32_t out_w, float *out_nhwc4, void *stream) {
+    if (!frames || !crop_boxes || !occ_rects || !mean || !std || !out_nhwc4 || n_frames <= 0 || frame_h <= 0 || frame_w <= 0 || out_h <= 0 ||
+        out_w <= 0)
+        return HMV_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return HMV_ERR_HIP;
+    return launch_frames_to_input(frames, crop_boxes, n_frames, frame_h, frame_w, out_h, out_w, mean, std, 0, out_nhwc4,
+                                  static_cast<hipStream_t>(stream), /*s2d=*/false, nullptr, 0, occ_rects) == hipSuccess ? HMV_OK : HMV_ERR_HIP;
 }
 
 int hmv_forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts, const uint8_t *frames, int32_t frame_h, int32_t frame_w,

@@ -203,7 +203,10 @@ hipError_t launch_nchw_to_nhwc8_f16(const float *x, void *out, int N, int H, int
 // out_mode: 0 = NHWC4 fp32, 1 = NHWC8 fp16, 2 = split [hi8 | lo8] fp16 pairs (HMV_F32X3)
 hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N, int Hf, int Wf, int S_h, int S_w, const float *mean,
                                   const float *std, int out_mode, void *out, hipStream_t s, bool s2d = false, const int *index = nullptr,
-                                  int n_src = 0);   // index (device, N entries): output frame n comes from frames / boxes [index[n]], n_src of them
+                                  int n_src = 0,    // index (device, N entries): output frame n comes from frames / boxes [index[n]], n_src of them
+                                  const int *rects = nullptr);   // rects (device, N x 4): output frame n's occluder in window pixels (index may be null then)
+// out rows i = rows index[i] of a / b (4 floats each; zeros for an index outside [0, n_src)); a or b may be null
+hipError_t launch_gather_rows4(const float *a, const float *b, const int *index, int n, int n_src, float *a_out, float *b_out, hipStream_t s);
 // HMV_F32X3 helpers: tensors whose rows are [hi plane | lo plane] fp16 pairs
 // space-to-depth stem input (misc_kernels.hip): mode 0 fp32 [12], 1 fp16 [16], 2 split [hi16 | lo16] per 2x2 pixel block
 hipError_t launch_nchw_to_s2d(const float *x, void *out, int N, int H, int W, int mode, hipStream_t s, int *sat = nullptr);

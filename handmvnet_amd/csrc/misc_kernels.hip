@@ -1132,6 +1132,25 @@ hipError_t launch_copy_rows(const float *in, int ldi, float *out, int ldo, int r
     return hipGetLastError();
 }
 
+// rows of 4 floats through an index (hmv_forward_frames_occlusions: the bbox and intrinsic rows of the occluded frames); either pair may be null
+__global__ void gather_rows4_kernel(const f32x4 *__restrict__ a, const f32x4 *__restrict__ b, const int *__restrict__ index, int n, int n_src,
+                                    f32x4 *__restrict__ a_out, f32x4 *__restrict__ b_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int src = index[i];
+    const bool ok = src >= 0 && src < n_src;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if (a) a_out[i] = ok ? a[src] : zero;
+    if (b) b_out[i] = ok ? b[src] : zero;
+}
+hipError_t launch_gather_rows4(const float *a, const float *b, const int *index, int n, int n_src, float *a_out, float *b_out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!index || (a && !a_out) || (b && !b_out)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows4_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4 *>(a),
+                       reinterpret_cast<const f32x4 *>(b), index, n, n_src, reinterpret_cast<f32x4 *>(a_out), reinterpret_cast<f32x4 *>(b_out));
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ camera frames: uint8 HWC -> model input
 // The reference prepares every view on the host (datasets/ho3d.py:35-40, 136-149; datasets/utils.py:40-77):
 //   crop_and_pad_image(frame, box) -> ToTensor (/255) -> Resize((S, S), antialias=True) -> Normalize(mean, std).
@@ -1151,8 +1170,15 @@ __device__ __forceinline__ void aa_span(int o, int in_size, float scale, float &
 }
 
 // one output pixel of the antialiased crop-resize + normalisation (datasets' transform, see hmv_forward_frames in handmv.h)
-__device__ __forceinline__ void frame_pixel(const uint8_t *__restrict__ frames, const int *__restrict__ boxes, size_t n, int oy, int ox,
-                                            int Hf, int Wf, int S_h, int S_w, const FrameNorm &nm, float &pr, float &pg, float &pb) {
+// OCC (a compile-time switch: the plain and indexed kernels' code stays what it is): `rect` = x1, y1, x2, y2 of an occluder in WINDOW
+// pixels (origin at the window's top-left corner, half-open), the reference's OcclusionAugmentation patch (datasets/augment.py:102-129).
+// It is clipped to the window; window pixels under it read as 0, like those outside the frame, and the weight sums still run over all
+// taps.  A row under the rectangle walks the taps left of it, then those right of it: the skipped taps would add +0 to a sum that is
+// never negative, so the bits are those of the same frame with these pixels zeroed.
+template <bool OCC>
+__device__ __forceinline__ void frame_pixel(const uint8_t *__restrict__ frames, const int *__restrict__ boxes, const int *__restrict__ rect,
+                                            size_t n, int oy, int ox, int Hf, int Wf, int S_h, int S_w, const FrameNorm &nm, float &pr,
+                                            float &pg, float &pb) {
         const int x1 = boxes[n * 4], y1 = boxes[n * 4 + 1], x2 = boxes[n * 4 + 2], y2 = boxes[n * 4 + 3];
         float acc[3] = {0.f, 0.f, 0.f};
         // windows wider than kMaxWindow px are treated like empty ones: a garbage box must not turn into an unbounded loop
@@ -1172,16 +1198,40 @@ __device__ __forceinline__ void frame_pixel(const uint8_t *__restrict__ frames, 
             const long long ox0 = (long long)fx + x1, oy0 = (long long)fy + y1;   // frame coordinates of tap 0
             const int a_lo = (int)(ox0 < 0 ? (-ox0 < nx ? -ox0 : nx) : 0), a_hi = (int)(ox0 + nx > Wf ? (Wf - ox0 > 0 ? Wf - ox0 : 0) : nx);
             const int b_lo = (int)(oy0 < 0 ? (-oy0 < ny ? -oy0 : ny) : 0), b_hi = (int)(oy0 + ny > Hf ? (Hf - oy0 > 0 ? Hf - oy0 : 0) : ny);
+            // the occluder in taps: rows b in [rb_lo, rb_hi) skip the taps [ra_lo, ra_hi), a_lo <= ra_lo <= ra_hi <= a_hi.  Its values are
+            // untrusted: clamped to the window first (saturating compares), everything behind that is at most kMaxWindow
+            int ra_lo = 0, ra_hi = 0, rb_lo = 0, rb_hi = 0;
+            if (OCC) {
+                const int rx1 = min(max(rect[0], 0), cw), ry1 = min(max(rect[1], 0), ch);
+                const int rx2 = min(max(rect[2], 0), cw), ry2 = min(max(rect[3], 0), ch);
+                if (rx2 > rx1 && ry2 > ry1) {
+                    ra_lo = min(max(rx1 - fx, a_lo), a_hi);
+                    ra_hi = min(max(rx2 - fx, ra_lo), a_hi);
+                    rb_lo = ry1 - fy;
+                    rb_hi = ry2 - fy;
+                }
+            }
             for (int b = b_lo; b < b_hi; ++b) {
                 const float wy = fmaxf(0.f, 1.f - fabsf((float)(b + fy) - cy + 0.5f) * iy);
                 if (wy == 0.f) continue;
                 const uint8_t *line = img + ((size_t)(oy0 + b) * Wf + (size_t)(ox0 + a_lo)) * 3;
                 float row[3] = {0.f, 0.f, 0.f};
-                for (int a = a_lo; a < a_hi; ++a, line += 3) {
+                const bool hidden = OCC && b >= rb_lo && b < rb_hi;
+                const int a_end = hidden ? ra_lo : a_hi;
+                for (int a = a_lo; a < a_end; ++a, line += 3) {
                     const float wx = fmaxf(0.f, 1.f - fabsf((float)(a + fx) - cx + 0.5f) * ix);
                     row[0] += wx * (float)line[0];
                     row[1] += wx * (float)line[1];
                     row[2] += wx * (float)line[2];
+                }
+                if (hidden) {
+                    line += (size_t)(ra_hi - ra_lo) * 3;
+                    for (int a = ra_hi; a < a_hi; ++a, line += 3) {
+                        const float wx = fmaxf(0.f, 1.f - fabsf((float)(a + fx) - cx + 0.5f) * ix);
+                        row[0] += wx * (float)line[0];
+                        row[1] += wx * (float)line[1];
+                        row[2] += wx * (float)line[2];
+                    }
                 }
                 acc[0] += wy * row[0];
                 acc[1] += wy * row[1];
@@ -1198,7 +1248,7 @@ __device__ __forceinline__ void frame_pixel(const uint8_t *__restrict__ frames, 
 #define FRAMES_TO_INPUT_KERNEL frames_to_input_kernel
 #define FRAMES_TO_S2D_KERNEL frames_to_s2d_kernel
 #define FRAMES_EXTRA_PARAMS
-#define FRAME_PIXEL(n, oy, ox, r, g, b) frame_pixel(frames, boxes, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b)
+#define FRAME_PIXEL(n, oy, ox, r, g, b) frame_pixel<false>(frames, boxes, nullptr, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b)
 #include "frames_to_input_body.inc"
 #undef FRAMES_TO_INPUT_KERNEL
 #undef FRAMES_TO_S2D_KERNEL
@@ -1213,7 +1263,7 @@ __device__ __forceinline__ void frame_pixel_indexed(const uint8_t *__restrict__ 
                                                     int S_h, int S_w, const FrameNorm &nm, float &pr, float &pg, float &pb) {
     const int src = index[n];
     if (src >= 0 && src < n_src) {
-        frame_pixel(frames, boxes, (size_t)src, oy, ox, Hf, Wf, S_h, S_w, nm, pr, pg, pb);
+        frame_pixel<false>(frames, boxes, nullptr, (size_t)src, oy, ox, Hf, Wf, S_h, S_w, nm, pr, pg, pb);
     } else {
         pr = -nm.mean[0] * nm.inv_std[0];
         pg = -nm.mean[1] * nm.inv_std[1];
@@ -1230,14 +1280,46 @@ __device__ __forceinline__ void frame_pixel_indexed(const uint8_t *__restrict__ 
 #undef FRAMES_EXTRA_PARAMS
 #undef FRAME_PIXEL
 
+// The same with an occluder per OUTPUT frame (hmv_forward_frames_occlusions, hmv_op_prepare_frames_occluded): output frame n is prepared
+// from frames[index[n]] with the window boxes[index[n]] and the occluder rects[n] (frame_pixel<true>).  index == nullptr: the identity.
+__device__ __forceinline__ void frame_pixel_occluded(const uint8_t *__restrict__ frames, const int *__restrict__ boxes,
+                                                     const int *__restrict__ index, int n_src, const int *__restrict__ rects, size_t n, int oy,
+                                                     int ox, int Hf, int Wf, int S_h, int S_w, const FrameNorm &nm, float &pr, float &pg,
+                                                     float &pb) {
+    const long long src = index ? (long long)index[n] : (long long)n;
+    if (!index || (src >= 0 && src < n_src)) {
+        frame_pixel<true>(frames, boxes, rects + n * 4, (size_t)src, oy, ox, Hf, Wf, S_h, S_w, nm, pr, pg, pb);
+    } else {
+        pr = -nm.mean[0] * nm.inv_std[0];
+        pg = -nm.mean[1] * nm.inv_std[1];
+        pb = -nm.mean[2] * nm.inv_std[2];
+    }
+}
+#define FRAMES_TO_INPUT_KERNEL frames_to_input_occluded_kernel
+#define FRAMES_TO_S2D_KERNEL frames_to_s2d_occluded_kernel
+#define FRAMES_EXTRA_PARAMS const int *__restrict__ index, int n_src, const int *__restrict__ rects,
+#define FRAME_PIXEL(n, oy, ox, r, g, b) frame_pixel_occluded(frames, boxes, index, n_src, rects, n, oy, ox, Hf, Wf, S_h, S_w, nm, r, g, b)
+#include "frames_to_input_body.inc"
+#undef FRAMES_TO_INPUT_KERNEL
+#undef FRAMES_TO_S2D_KERNEL
+#undef FRAMES_EXTRA_PARAMS
+#undef FRAME_PIXEL
+
 hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N, int Hf, int Wf, int S_h, int S_w, const float *mean,
-                                  const float *std, int out_mode, void *out, hipStream_t s, bool s2d, const int *index, int n_src) {
+                                  const float *std, int out_mode, void *out, hipStream_t s, bool s2d, const int *index, int n_src,
+                                  const int *rects) {
     FrameNorm nm;
     for (int c = 0; c < 3; ++c) { nm.mean[c] = mean[c]; nm.inv_std[c] = 1.f / std[c]; }
     if (s2d) {
         const int Hs = (S_h + 1) / 2, Ws = (S_w + 1) / 2;
         const size_t total = (size_t)N * Hs * Ws;
         const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+        if (rects) {
+            if (out_mode == 2) hipLaunchKernelGGL(frames_to_s2d_occluded_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            else if (out_mode == 1) hipLaunchKernelGGL(frames_to_s2d_occluded_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            else hipLaunchKernelGGL(frames_to_s2d_occluded_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
+            return hipGetLastError();
+        }
         if (index) {
             if (out_mode == 2) hipLaunchKernelGGL(frames_to_s2d_indexed_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
             else if (out_mode == 1) hipLaunchKernelGGL(frames_to_s2d_indexed_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, Hs, Ws, nm, out, total);
@@ -1251,6 +1333,12 @@ hipError_t launch_frames_to_input(const uint8_t *frames, const int *boxes, int N
     }
     const size_t total = (size_t)N * S_h * S_w;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    if (rects) {
+        if (out_mode == 2) hipLaunchKernelGGL(frames_to_input_occluded_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, nm, out, total);
+        else if (out_mode == 1) hipLaunchKernelGGL(frames_to_input_occluded_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, nm, out, total);
+        else hipLaunchKernelGGL(frames_to_input_occluded_kernel<0>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, rects, Hf, Wf, S_h, S_w, nm, out, total);
+        return hipGetLastError();
+    }
     if (index) {
         if (out_mode == 2) hipLaunchKernelGGL(frames_to_input_indexed_kernel<2>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, nm, out, total);
         else if (out_mode == 1) hipLaunchKernelGGL(frames_to_input_indexed_kernel<1>, dim3(grid), dim3(256), 0, s, frames, boxes, index, n_src, Hf, Wf, S_h, S_w, nm, out, total);

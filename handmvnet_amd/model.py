@@ -405,6 +405,48 @@ class HandMvNet(torch.nn.Module):
         self._call("hmv_forward_frames", size, size, dev, batch, frames, fh, fw, boxes, m3, s3, bb, it, crop, cam, hm)
         return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
 
+    def forward_frames_occlusions(self, frames, crop_boxes, occ_view, occ_rects, cam_params=None, mean=(0.485, 0.456, 0.406),
+                                  std=(0.229, 0.224, 0.225), image_size=None):
+        """forward_frames() for the clean batch and for n occluded variants of it in one call (hmv_forward_frames_occlusions): variant
+        o hides the rectangle occ_rects[o, b] of camera occ_view[o]'s window in every sample b -- the reference's OcclusionAugmentation
+        patch (handmvnet_amd.occlusion.cell_rects builds grid cells).  The per-frame stage runs once on the b * v clean frames and once
+        per occluded frame; only the fusion blocks and the decoder run per variant.
+        occ_view: n camera indices in [0, v) (list, array or tensor; read on the host).  occ_rects: int tensor [n, b, 4] =
+        (rx1, ry1, rx2, ry2) in window pixels from the window's top-left corner, half-open, clipped to the window; an empty one hides
+        nothing.  Returns forward_frames()' dict for the clean batch with `joints_cam` of shape [1 + n, b, 21, 3] (row 0 clean, row
+        1 + o variant o), plus `joints_crop_img_occ` [n, b, 21, 2] and `heatmap_occ` [n, b, 21, h, w]: the occluded camera's own 2D
+        output under variant o.  Every variant's values are the bits forward_frames() returns on a copy of `frames` with the frame
+        pixels under the rectangle zeroed."""
+        self._check_frames(frames)
+        b, v, fh, fw, _ = frames.shape
+        self._check_all_views(v, "frames", "an occlusion sweep takes the full view set")
+        if b == 0:
+            raise ValueError("frames hold no sample")
+        view = occ_view.detach().cpu().numpy() if isinstance(occ_view, torch.Tensor) else np.asarray(occ_view)
+        if view.ndim != 1 or view.size == 0 or view.dtype.kind not in "iu":
+            raise ValueError("occ_view must hold at least one integer camera index")
+        bad = np.flatnonzero((view < 0) | (view >= v))
+        if bad.size:
+            raise ValueError(f"occ_view[{int(bad[0])}] = {int(view[bad[0]])} is outside [0, {v})")
+        n = int(view.size)
+        if not isinstance(occ_rects, torch.Tensor) or occ_rects.is_floating_point() or tuple(occ_rects.shape) != (n, b, 4):
+            raise ValueError(f"occ_rects must be an int tensor [{n}, {b}, 4]")
+        self._need_cuda(frames, "frames")
+        dev = frames.device
+        size = int(image_size or self.cfg.image_size)
+        frames = frames.contiguous()
+        boxes = self._window_rows(crop_boxes, dev, b * v)
+        rects = occ_rects.to(dev).to(torch.int32).contiguous()
+        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        bb, it = self._camera_rows(dev, b * v, cam_params, boxes=boxes)
+        hs = heatmap_size_of(self.cfg, size, size)
+        crop, cam, hm = self._outputs(dev, (b, v), (1 + n, b), hs)
+        crop_occ, _, hm_occ = self._outputs(dev, (n, b), (0,), hs)
+        views = (ctypes.c_int32 * n)(*[int(c) for c in view])
+        self._call("hmv_forward_frames_occlusions", size, size, dev, b, frames, fh, fw, boxes, m3, s3, bb, it, n, views, rects, crop, cam,
+                   hm, crop_occ, hm_occ)
+        return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm, "joints_crop_img_occ": crop_occ, "heatmap_occ": hm_occ}
+
     # ------------------------------------------------------------------ evaluation (handmvnet.py:352-383, 493-517)
     def _get_metrics(self, pred_pts, target_pts):
         """handmvnet.py:352-368: (mpjpe mm, pa_mpjpe mm, auc, norm_auc, pck_values, thresholds) for [b, n, 3]
@@ -543,6 +585,21 @@ class HandMvNet(torch.nn.Module):
         (handmvnet_amd/subsets.py).  Like evaluate(), converts each batch's joints_cam / root_joint from mm to metres in place."""
         from .subsets import SubsetSweepEvaluator
         ev = SubsetSweepEvaluator(self, subsets, mode)
+        for batch in batches:
+            ev.step(batch)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            ev.reduce(group)
+        return ev.compute()
+
+    def evaluate_occlusions(self, batches, grid: int = 4, cameras=None, mode: str = "test", group=None) -> dict:
+        """evaluate() for the clean batches and for every cell of a grid x grid occluder layout on every camera of `cameras` (None:
+        all) in one pass over `batches` (frames and windows: batch["data"]["frames"] / ["crop_boxes"]): per step one
+        forward_frames_occlusions call, then per variant the loss and accumulation evaluate() runs; one all-reduce of the whole
+        [1 + n][state] tensor under torch.distributed, one readback.  Returns {"variants": the (camera, row, col) list, "clean",
+        "per_variant": the dicts evaluate() returns on the clean / occluded frames, "sensitivity": per scalar key a [V, grid, grid]
+        array of value(variant) - value(clean), NaN for a camera not swept} (handmvnet_amd/occlusion.py)."""
+        from .occlusion import OcclusionSweepEvaluator
+        ev = OcclusionSweepEvaluator(self, grid=grid, cameras=cameras, mode=mode)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():

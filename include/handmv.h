@@ -443,6 +443,49 @@ int hmv_op_prepare_frames(int32_t device, const uint8_t *frames, int32_t n_frame
                           const int32_t *crop_boxes, const float *mean, const float *std, int32_t out_h, int32_t out_w, float *out_nhwc4,
                           void *stream);
 
+/* ---- occlusion: one patch of one camera's window hidden (the reference's OcclusionAugmentation, datasets/augment.py:102-129) ----
+ * The occluder is a rectangle (rx1, ry1, rx2, ry2), int32, in WINDOW pixels: the origin is the window's top-left corner (x1, y1) of the
+ * frame's crop box, before the resize; half-open; clipped to [0, cw] x [0, ch] (cw = x2 - x1, ch = y2 - y1).  Window pixels inside it read
+ * as 0, exactly like window pixels that fall outside the frame; the filter's weight sums still run over all taps of the window.  The
+ * result is, bit for bit, the preparation of the same frame with the frame pixels under the rectangle zeroed.  A rectangle that is empty
+ * after clipping (rx2 <= rx1 or ry2 <= ry1) occludes nothing; one that covers the whole window gives the black view of an empty window.
+ * The values are untrusted: whatever they are, nothing outside `frames` is read and the work per pixel stays that of the window.
+ * The reference's patch (patch_size p, row r, column c; r < ch / p, c < cw / p) is the rectangle (c p, r p, (c + 1) p, (r + 1) p).
+ *
+ * hmv_op_prepare_frames with one occluder per frame: occ_rects device int32 [n_frames][4]. */
+int hmv_op_prepare_frames_occluded(int32_t device, const uint8_t *frames, int32_t n_frames, int32_t frame_h, int32_t frame_w,
+                                   const int32_t *crop_boxes, const int32_t *occ_rects, const float *mean, const float *std, int32_t out_h,
+                                   int32_t out_w, float *out_nhwc4, void *stream);
+
+/* An occlusion sweep ("which patch of which camera does the prediction rest on"): hmv_forward_frames for the clean batch and for n_occ
+ * variants of it, each with one rectangle hidden in ONE camera, at the cost of one per-frame pass over the batch * V clean frames and one
+ * occluded frame per (variant, sample) instead of (1 + n_occ) * batch * V frames.  Everything up to the per-frame token rows does not depend
+ * on the other views, so a variant reuses the clean rows of its V - 1 untouched cameras; the fusion blocks and the decoder run per variant.
+ *   frames, crop_boxes, bbox, intrinsic, joints_crop_img, heatmap: the full clean batch, exactly as for hmv_forward_frames; written once
+ *   occ_view             HOST int32 [n_occ], the camera in [0, cfg.num_views) that variant o occludes; read before the call returns
+ *   occ_rects            DEVICE int32 [n_occ][batch][4], variant o's rectangle in sample b's window of that camera (see above)
+ *   joints_cam           [1 + n_occ][batch][21][3]  out: row 0 the clean batch, row 1 + o variant o
+ *   joints_crop_img_occ  [n_occ][batch][21][2]            out, may be NULL: the occluded camera's own 2D output under variant o
+ *   heatmap_occ          [n_occ][batch][21][H/8][W/8]     out, may be NULL
+ * The rule that defines every number: variant o's joints_cam, joints_crop_img_occ and heatmap_occ hold the bits hmv_forward_frames writes
+ * for this batch when, in camera occ_view[o]'s frames, the frame pixels under the rectangle are zeroed; row 0 and the clean outputs hold
+ * the bits of hmv_forward_frames on the untouched frames.  A variant's bits depend neither on the passes nor on the other variants;
+ * duplicates are allowed.
+ * Occluded frame (o, b) is frames[b * V + occ_view[o]] with that slot's window, bbox and intrinsic rows.  The occluded frames go through the
+ * per-frame stage in passes of at most max(batch, reserved batch) * V frames, the tail in passes of at most max(batch, reserved batch)
+ * virtual samples (one sample under one variant, or clean), so that every buffer of a pass stays within the reservation; the token rows of
+ * all batch * V + n_occ * batch frames are retained on top, and the workspace grows before the first launch where that takes it past the
+ * reservation.
+ * Asynchronous on `stream` and without a device synchronisation (one small table upload).  Always eager, records no stages (reading one
+ * afterwards returns HMV_ERR_STATE), ignores attention capture; the range report covers it.  With profiling on, the record list also holds
+ * bracketing records "occlusions_frames" (one around the clean stage, one per occluded pass) and "occlusions_tail" (one per tail pass).
+ * HMV_ERR_ARG, before anything is launched, for: whatever hmv_forward_frames refuses, n_occ < 1, a NULL occ_view or occ_rects, a camera
+ * outside [0, V), (1 + n_occ) * batch beyond the index arithmetic. */
+int hmv_forward_frames_occlusions(hmv_handle h, int32_t batch, const uint8_t *frames, int32_t frame_h, int32_t frame_w,
+                                  const int32_t *crop_boxes, const float *mean, const float *std, const float *bbox, const float *intrinsic,
+                                  int32_t n_occ, const int32_t *occ_view, const int32_t *occ_rects, float *joints_crop_img, float *joints_cam,
+                                  float *heatmap, float *joints_crop_img_occ, float *heatmap_occ, void *stream);
+
 /* ---- sequences: the crop window of frame t + 1 is the box around the hand found in frame t ----
  * A recorded or live sequence has no dataset boxes (datasets/ho3d.py:103); its windows follow the hand.  One launch (track.hip) turns a
  * step's joints_crop_img into the next step's windows, per frame slot n (sample, view) with S = float(image_size):

@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("OcclusionSweepEvaluator", "cell_rects", "grid_variants"):   # occlusion sweeps from raw frames (occlusion.py)
         from . import occlusion
         return getattr(occlusion, name)
+    if name in ("ReferenceSweepEvaluator", "each_reference", "rotations", "as_order_table", "pose_consensus"):   # reference-view sweeps (orders.py)
+        from . import orders
+        return getattr(orders, name)
     if name in ("JointsToVertices", "hand_ik", "rigid_unapply"):   # hand pose parameters and MANO vertices (ik.py)
         from . import ik
         return getattr(ik, name)

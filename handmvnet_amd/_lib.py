@@ -20,7 +20,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
            "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply", "hmv_op_prepare_frames_occluded",
-           "hmv_forward_frames_occlusions"]
+           "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -77,6 +77,14 @@ class HmvSeqEvalArgs(ctypes.Structure):
                 ("sums_doubles", ctypes.c_size_t), ("history_floats", ctypes.c_size_t)]
 
 
+class HmvConsensusArgs(ctypes.Structure):
+    """hmv_consensus_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("S", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32),
+                ("target_cam", ctypes.c_int32), ("mode", ctypes.c_int32), ("iterations", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("poses", ctypes.c_void_p), ("ref_cam", ctypes.c_void_p), ("extrinsic", ctypes.c_void_p), ("aligned", ctypes.c_void_p),
+                ("consensus", ctypes.c_void_p), ("spread", ctypes.c_void_p), ("deviation", ctypes.c_void_p)]
+
+
 class HandMvError(RuntimeError):
     pass
 
@@ -112,6 +120,10 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_views.restype = ctypes.c_int
     lib.hmv_forward_subsets.argtypes = [vp, ci, ci, fp, fp, fp, fp, fp, fp, fp, vp]   # (subset_mask: host uint8 [S][V])
     lib.hmv_forward_subsets.restype = ctypes.c_int
+    lib.hmv_forward_orders.argtypes = [vp, ci, ci, fp, fp, fp, fp, fp, fp, fp, vp]   # (orders: host int32 [S][V], padded with -1)
+    lib.hmv_forward_orders.restype = ctypes.c_int
+    lib.hmv_op_pose_consensus.argtypes = [ci, ctypes.POINTER(HmvConsensusArgs), vp]
+    lib.hmv_op_pose_consensus.restype = ctypes.c_int
     lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
     lib.hmv_op_attention_views.restype = ctypes.c_int
     lib.hmv_set_attention_capture.argtypes = [vp, ctypes.c_uint32]

@@ -2600,6 +2600,58 @@ int forward_frames_views(hmv_handle h, int32_t batch, const int32_t *view_counts
     return forward_ragged(h, fc, view_counts);
 }
 
+// S ordered camera lists over one full batch, what a sweep's fusion tails run on: list i is cams[sum count[0 .. i)) ...], count[i] distinct
+// cameras in feed order (the first one is the reference view).  A subset's list is its cameras ascending (hmv_forward_subsets), an
+// order's the cameras as the caller named them (hmv_forward_orders).
+struct CameraLists {
+    int S;
+    const std::vector<int> &count, &cams;
+};
+
+// The host plan of a sweep over camera lists: the passes -- at most max(batch, reserved batch) virtual samples each, so that every
+// buffer of a pass stays within the reservation -- and every pass's table [seg | fpos | src] in the slot `up` names.  Virtual sample
+// q = list q / batch on sample q % batch; its frame of rank r is src = b * V + (the list's r-th camera) at position fpos = 21 r.
+int plan_camera_lists(hmv_engine *h, int batch, const CameraLists &L, std::vector<SubsetChunk> &chunks, ViewsUpload &up) {
+    const int V = h->cfg.num_views, total = L.S * batch, cmax = std::max<int>(batch, h->reserved_batch);
+    std::vector<size_t> first(L.S + 1, 0);   // list i starts at cams[first[i]]
+    for (int i = 0; i < L.S; ++i) first[i + 1] = first[i] + (size_t)L.count[i];
+    for (int q0 = 0; q0 < total; q0 += cmax) {
+        SubsetChunk ck{q0, std::min(cmax, total - q0), 0, 0, up.tab_n};
+        for (int q = q0; q < q0 + ck.nv; ++q) {
+            ck.n += L.count[q / batch];
+            ck.vmax = std::max(ck.vmax, L.count[q / batch]);
+        }
+        up.tab_n += (size_t)ck.nv + 1 + 2 * (size_t)ck.n;
+        chunks.push_back(ck);
+    }
+    if (const int rc = views_slot(h, up.tab_n, up.slot)) return rc;
+    for (const SubsetChunk &ck : chunks) {
+        int32_t *seg = up.slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
+        seg[0] = 0;
+        for (int i = 0, m = 0; i < ck.nv; ++i) {
+            const int q = ck.q0 + i, list = q / batch, b = q % batch;
+            seg[i + 1] = seg[i] + NJ * L.count[list];
+            for (int r = 0; r < L.count[list]; ++r) { fpos[m] = NJ * r; src[m++] = b * V + L.cams[first[list] + r]; }
+        }
+    }
+    return HMV_OK;
+}
+
+// What hmv_forward_subsets and hmv_forward_orders share behind their own argument checks: reservation, plan, upload, the eager run.
+int forward_camera_lists(hmv_engine *h, const ForwardCall &fc, const CameraLists &L) {
+    if (const int rc = check_crop_pe(h, fc.bbox, fc.intrinsic)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (fc.batch > h->reserved_batch)
+        if (const int rc = hmv_reserve(h, fc.batch)) return rc;
+    std::vector<SubsetChunk> chunks;
+    ViewsUpload up{nullptr, 0};
+    if (const int rc = plan_camera_lists(h, fc.batch, L, chunks, up)) return rc;
+    auto run = [&](const ForwardCall &c, bool dry, Arena &A) { return run_forward_subsets(h, c, chunks, dry ? nullptr : h->views_dev, dry, A); };
+    if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
+    h->forget_attention();   // (no attention maps either: a sweep ignores the mask)
+    return run_checked(h, fc, 1, run);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2678,39 +2730,50 @@ int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const ui
         for (int v = 0; v < V; ++v) count[i] += subset_mask[(size_t)i * V + v] != 0;
         if (!count[i]) return h->fail(HMV_ERR_ARG, "hmv_forward_subsets: subset %d has no camera", i);
     }
-    if (const int rc = check_crop_pe(h, bbox, intrinsic)) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (batch > h->reserved_batch)
-        if (const int rc = hmv_reserve(h, batch)) return rc;
-    // the passes: at most max(batch, reserved batch) virtual samples each, so that every buffer of a pass stays within the reservation
-    const int total = S * batch, cmax = std::max<int>(batch, h->reserved_batch);
-    std::vector<SubsetChunk> chunks;
-    ViewsUpload up{nullptr, 0};
-    for (int q0 = 0; q0 < total; q0 += cmax) {
-        SubsetChunk ck{q0, std::min(cmax, total - q0), 0, 0, up.tab_n};
-        for (int q = q0; q < q0 + ck.nv; ++q) {
-            ck.n += count[q / batch];
-            ck.vmax = std::max(ck.vmax, count[q / batch]);
+    const ForwardCall fc{batch, x, FrameSrc{}, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
+    // a subset's list is its cameras ascending
+    std::vector<int> cams;
+    cams.reserve((size_t)S * V);
+    for (int i = 0; i < S; ++i)
+        for (int v = 0; v < V; ++v)
+            if (subset_mask[(size_t)i * V + v]) cams.push_back(v);
+    return forward_camera_lists(h, fc, CameraLists{S, count, cams});
+}
+
+/* A reference-view sweep (include/handmv.h): hmv_forward_subsets with the cameras of every row fed in the order the row names them.
+ * Everything that can be refused is refused before the first launch; the rest is hmv_forward_subsets' (one planner, one runner). */
+int hmv_forward_orders(hmv_handle h, int32_t batch, int32_t n_orders, const int32_t *orders, const float *x, const float *bbox,
+                       const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream) {
+    if (const int rc = check_handle(h)) return rc;
+    if (batch <= 0) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: batch must be positive (got %d)", (int)batch);
+    if (n_orders < 1) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: n_orders must be at least 1 (got %d)", (int)n_orders);
+    if (!orders) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: orders is null (host int32 [n_orders][num_views], padded with -1)");
+    if (!x || !joints_crop_img || !joints_cam) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: null or empty input/output");
+    const int V = h->cfg.num_views, S = n_orders;
+    if ((long long)S * batch > INT32_MAX / (NJ * 3)) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: n_orders x batch is too large");
+    std::vector<int> count(S, 0), cams;
+    cams.reserve((size_t)S * V);
+    std::vector<char> seen(V);
+    for (int i = 0; i < S; ++i) {
+        const int32_t *row = orders + (size_t)i * V;
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int v = 0; v < V; ++v) {
+            const int c = row[v];
+            if (c < 0) {
+                if (c != -1) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: order %d, entry %d = %d is no camera in [0, %d) (padding is -1)", i, v, c, V);
+                continue;
+            }
+            if (count[i] != v) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: order %d names camera %d after a -1", i, c);
+            if (c >= V) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: order %d, entry %d = %d is no camera in [0, %d)", i, v, c, V);
+            if (seen[c]) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: order %d names camera %d twice", i, c);
+            seen[c] = 1;
+            cams.push_back(c);
+            ++count[i];
         }
-        up.tab_n += (size_t)ck.nv + 1 + 2 * (size_t)ck.n;
-        chunks.push_back(ck);
-    }
-    if (const int rc = views_slot(h, up.tab_n, up.slot)) return rc;
-    for (const SubsetChunk &ck : chunks) {
-        int32_t *seg = up.slot->host + ck.tab, *fpos = seg + ck.nv + 1, *src = fpos + ck.n;
-        seg[0] = 0;
-        for (int i = 0, m = 0; i < ck.nv; ++i) {
-            const int q = ck.q0 + i, sub = q / batch, b = q % batch;
-            seg[i + 1] = seg[i] + NJ * count[sub];
-            for (int v = 0, r = 0; v < V; ++v)
-                if (subset_mask[(size_t)sub * V + v]) { fpos[m] = NJ * r++; src[m++] = b * V + v; }
-        }
+        if (!count[i]) return h->fail(HMV_ERR_ARG, "hmv_forward_orders: order %d has no camera", i);
     }
     const ForwardCall fc{batch, x, FrameSrc{}, bbox, intrinsic, joints_crop_img, joints_cam, heatmap, TrackTail{}, static_cast<hipStream_t>(stream)};
-    auto run = [&](const ForwardCall &c, bool dry, Arena &A) { return run_forward_subsets(h, c, chunks, dry ? nullptr : h->views_dev, dry, A); };
-    if (const int rc = plan_and_upload(h, fc, up, run)) return rc;
-    h->forget_attention();   // (no attention maps either: a sweep ignores the mask)
-    return run_checked(h, fc, 1, run);
+    return forward_camera_lists(h, fc, CameraLists{S, count, cams});
 }
 
 /* An occlusion sweep from raw frames (include/handmv.h): the per-frame stage once on the clean frames and once per occluded frame, the

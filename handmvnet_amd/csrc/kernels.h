@@ -420,6 +420,20 @@ hipError_t launch_hand_ik(const HandIkParams &p, hipStream_t s);
 // out[i] = R_i^T (points[i] - t_i) over [n][n_pts][3]; out may be points
 hipError_t launch_rigid_unapply(const float *points, const double *align, long n, int n_pts, float *out, hipStream_t s);
 
+// Pose consensus over reference views (pose_consensus.hip; hmv_op_pose_consensus in handmv.h): one wave64 per sample.  Each output
+// may be null.
+struct PoseConsensusParams {
+    const float *poses;      // [S][B][21][3]
+    const int *ref_cam;      // [S], device
+    const float *extrinsic;  // [B][V][4][4]
+    int S, B, V, target, mode, iterations;
+    float *aligned;          // [S][B][21][3]
+    float *consensus;        // [B][21][3]
+    float *spread;           // [B][21]
+    float *deviation;        // [S][B]
+};
+hipError_t launch_pose_consensus(const PoseConsensusParams &p, hipStream_t s);
+
 // Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
 void set_thread_error(const std::string &msg);
 

@@ -88,25 +88,6 @@ __global__ __launch_bounds__(kThreads) void target_heatmaps_kernel(const float *
     for (int e = threadIdx.x; e < len; e += kThreads) o[e] = target_at(lds, e, h, w);
 }
 
-// Rows 0..2 of inverse(a) * b for a general 4x4 `a` (row-major): cofactor expansion over 2x2 minors, no pivoting needed and no
-// dynamic indexing.  det == 0 gives inf / NaN.
-__device__ void solve4_xyz(const double a[16], const double b[4], double y[3]) {
-    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
-    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
-    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
-    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
-    const double det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    const double i00 = a[5] * c5 - a[6] * c4 + a[7] * c3, i01 = -a[1] * c5 + a[2] * c4 - a[3] * c3;
-    const double i02 = a[13] * s5 - a[14] * s4 + a[15] * s3, i03 = -a[9] * s5 + a[10] * s4 - a[11] * s3;
-    const double i10 = -a[4] * c5 + a[6] * c2 - a[7] * c1, i11 = a[0] * c5 - a[2] * c2 + a[3] * c1;
-    const double i12 = -a[12] * s5 + a[14] * s2 - a[15] * s1, i13 = a[8] * s5 - a[10] * s2 + a[11] * s1;
-    const double i20 = a[4] * c4 - a[5] * c2 + a[7] * c0, i21 = -a[0] * c4 + a[1] * c2 - a[3] * c0;
-    const double i22 = a[12] * s4 - a[13] * s2 + a[15] * s0, i23 = -a[8] * s4 + a[9] * s2 - a[11] * s0;
-    y[0] = (i00 * b[0] + i01 * b[1] + i02 * b[2] + i03 * b[3]) / det;
-    y[1] = (i10 * b[0] + i11 * b[1] + i12 * b[2] + i13 * b[3]) / det;
-    y[2] = (i20 * b[0] + i21 * b[1] + i22 * b[2] + i23 * b[3]) / det;
-}
-
 // get_2d_joints_from_3d_joints for one joint of one view (camera.py:4-60), then optionally the crop mapping
 // (datasets/utils.py:124-143 with its default image_size of 256).  x3: the joint in camera `root` (metres), root3: added to it
 // first when given.  e_root / e_view: [4][4] extrinsics, k: fx, fy, cx, cy, box: x1, y1, x2, y2 or null.

@@ -373,6 +373,52 @@ class HandMvNet(torch.nn.Module):
         self._call("hmv_forward_subsets", hh, ww, dev, b, S, table.ctypes.data_as(ctypes.c_void_p), x, bb, it, crop, cam, hm)
         return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
 
+    def forward_orders(self, x, orders, bbox=None, cam_params=None):
+        """forward_subsets() with the cameras of every row fed in the ORDER the row names them (hmv_forward_orders): `orders` is a
+        sequence of camera-index lists (handmvnet_amd.orders.each_reference / rotations build the usual ones) or an int table
+        [S, <= v] padded with -1; the first camera of an order is the reference view.  Returns forward()'s dict with `joints_cam` of
+        shape [S, b, 21, 3]: joints_cam[s] holds the bits forward_views() returns for x[:, order s] (bbox and intrinsic alike) in the
+        first k view slots under a mask of k leading True -- root-relative in the frame of the order's FIRST camera for the
+        cross-attention fusion; for the learnable-query fusion the frame of the output is a property of that model's training, not
+        of the engine.  `joints_crop_img` and `heatmap` are forward()'s, written once for all v views in camera order.  The table
+        is read on the host; the backbone runs once."""
+        from .orders import as_order_table
+        self._check_x(x)
+        self._check_channels(x)
+        b, v, _, hh, ww = x.shape
+        self._check_all_views(v, "x", "the orders name the cameras to feed")
+        if b == 0:
+            raise ValueError("x holds no sample")
+        table = as_order_table(orders, v)
+        self._need_cuda(x, "x")
+        dev = x.device
+        x = x.contiguous().float()
+        bb, it = self._camera_rows(dev, b * v, cam_params, bbox=bbox)
+        S = table.shape[0]
+        crop, cam, hm = self._outputs(dev, (b, v), (S, b), heatmap_size_of(self.cfg, hh, ww))
+        self._call("hmv_forward_orders", hh, ww, dev, b, S, table.ctypes.data_as(ctypes.c_void_p), x, bb, it, crop, cam, hm)
+        return {"joints_crop_img": crop, "joints_cam": cam, "heatmap": hm}
+
+    def forward_consensus(self, x, bbox, cam_params, orders=None, target: int = 0, mode: str = "mean"):
+        """Every order's estimate of the hand in ONE camera's frame and their consensus: one forward_orders call (one backbone pass)
+        and one pose_consensus launch (handmvnet_amd/orders.py).  orders=None: each_reference(v), every camera as the reference view
+        once.  Needs cam_params["extrinsic"] [b, v, 4, 4].  Returns forward()'s dict with `joints_cam` [b, 21, 3] set to the
+        consensus ("mean" or "median", the geometric median) in camera `target`'s frame, plus `joints_cam_orders` [S, b, 21, 3] (the
+        estimates rotated into that frame), `joints_cam_spread` [b, 21] (the root mean square over the orders of each joint's
+        distance from the consensus, in metres: the disagreement of the reference views) and `order_deviation` [S, b] (each
+        order's mean joint distance from the consensus).  Each estimate is taken to be in the frame of its order's first camera."""
+        from .orders import as_order_table, each_reference, pose_consensus
+        if cam_params is None or "extrinsic" not in cam_params:
+            raise ValueError("forward_consensus needs cam_params['extrinsic']")
+        if not 0 <= int(target) < self.num_views:
+            raise ValueError(f"target = {target} is outside [0, {self.num_views})")
+        table = as_order_table(each_reference(self.num_views) if orders is None else orders, self.num_views)
+        out = self.forward_orders(x, table, bbox, cam_params)
+        res = pose_consensus(out["joints_cam"], table[:, 0], cam_params["extrinsic"], target=int(target), mode=mode)
+        out.update(joints_cam=res["consensus"], joints_cam_orders=res["aligned"], joints_cam_spread=res["spread"],
+                   order_deviation=res["deviation"])
+        return out
+
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                        image_size=None, view_mask=None):
         """forward() from raw camera frames: `frames` uint8 [b, v, Hf, Wf, 3] and integer crop windows `crop_boxes`
@@ -585,6 +631,23 @@ class HandMvNet(torch.nn.Module):
         (handmvnet_amd/subsets.py).  Like evaluate(), converts each batch's joints_cam / root_joint from mm to metres in place."""
         from .subsets import SubsetSweepEvaluator
         ev = SubsetSweepEvaluator(self, subsets, mode)
+        for batch in batches:
+            ev.step(batch)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            ev.reduce(group)
+        return ev.compute()
+
+    def evaluate_orders(self, batches, orders=None, mode: str = "test", group=None, consensus: str = "mean") -> dict:
+        """evaluate() for S reference-view orders (None: every camera as the reference view once) and for their consensus in one pass
+        over `batches` (full-view batches with cam_params["extrinsic"], no view_mask): per step one forward_orders call -- one
+        backbone pass, S fusion tails -- one pose_consensus launch into the frame of camera inputs["root_idx"], then per order and
+        for the consensus the loss and accumulation evaluate() runs; one all-reduce of the whole [S + 1][state] tensor under
+        torch.distributed, one readback.  Returns {"orders": the camera-index lists, "per_order": per order evaluate()'s dict for
+        its rotated estimate, "consensus": that dict for the consensus pose, "best_reference": the order with the lowest
+        {mode}_mpjpe} (handmvnet_amd/orders.py).  Like evaluate(), converts each batch's joints_cam / root_joint from mm to metres in
+        place."""
+        from .orders import ReferenceSweepEvaluator
+        ev = ReferenceSweepEvaluator(self, orders, mode, consensus=consensus)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():

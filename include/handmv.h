@@ -191,6 +191,25 @@ int hmv_forward_views(hmv_handle h, int32_t batch, const int32_t *view_counts, c
 int hmv_forward_subsets(hmv_handle h, int32_t batch, int32_t n_subsets, const uint8_t *subset_mask, const float *x, const float *bbox,
                         const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
 
+/* A reference-view sweep ("what is the pose in camera c's frame", "which camera should be the reference view"): hmv_forward_subsets
+ * with the cameras of every row fed in the ORDER the row names them.  The first camera of an order is the reference view: the cross
+ * block takes its queries from it, joints_cam comes out root-relative in its frame, and the sinusoidal positions count the others in
+ * feed order.  joints_cam[s] holds the bits hmv_forward_views writes for this batch with its views permuted by order s: x, bbox and
+ * intrinsic rows [order s] in the first k view slots and k present views per sample.  A sorted order is a subset (hmv_forward_subsets'
+ * bits); the identity order over all cameras has hmv_forward's.
+ *   orders          HOST int32 [n_orders][cfg.num_views]: each row lists k distinct cameras, 1 <= k <= num_views, from the left and is
+ *                   padded with -1; one table for the whole batch; read before the call returns.  Duplicate orders are allowed
+ *   x, bbox, intrinsic, joints_crop_img, heatmap: the FULL batch in camera order, exactly as for hmv_forward; both outputs are written once
+ *   joints_cam      [n_orders][batch][21][3]  out
+ * Passes, workspace, stream behaviour, eager execution, stages, the range report and the two bracketing profile records
+ * ("subsets_frames", "subsets_tail") are hmv_forward_subsets': both entries share one host planner and one runner, and a sweep captures
+ * no attention maps.  For the learnable-query fusion the sweep is defined by the same rule; which frame that model's output is in is a
+ * property of its training, not of the engine.
+ * HMV_ERR_ARG, before anything is launched, for: batch <= 0, n_orders < 1, a NULL table, an order without a camera, a camera outside
+ * [0, num_views), a camera named twice in one order, a camera behind a -1. */
+int hmv_forward_orders(hmv_handle h, int32_t batch, int32_t n_orders, const int32_t *orders, const float *x, const float *bbox,
+                       const float *intrinsic, float *joints_crop_img, float *joints_cam, float *heatmap, void *stream);
+
 /* Human-readable description of the last failure on this handle, or with h == NULL of the calling thread's last failed call
  * without a handle (hmv_create, the hmv_op_* entries ...): per thread, like errno. */
 const char *hmv_last_error(hmv_handle h);
@@ -901,6 +920,54 @@ int hmv_op_hand_ik(int32_t device, const float *joints, const float *template_jo
  *   points, out  [n][n_pts][3] fp32, may be the same buffer;   align [n][12] fp64 as hmv_op_hand_ik wrote it
  * HMV_ERR_ARG before any HIP call for n <= 0, n_pts <= 0, a NULL points / out, a NULL or misaligned align. */
 int hmv_op_rigid_unapply(int32_t device, const float *points, const double *align, int32_t n, int32_t n_pts, float *out, void *stream);
+
+/* ---- pose consensus: the S estimates of a reference-view sweep in one camera's frame, their consensus and their disagreement ----
+ * Every camera of a rig can serve as reference view (hmv_forward_orders), which gives S root-relative estimates of the same hand, estimate
+ * s in the frame of camera ref_cam[s].  One stateless launch (pose_consensus.hip) rotates them into camera target_cam's frame by the
+ * extrinsics and reduces them per joint.
+ *   poses      [S][B][21][3] fp32, root-relative (hmv_forward_orders' joints_cam)
+ *   ref_cam    DEVICE int32 [S]: the camera whose frame estimate s is in
+ *   extrinsic  [B][V][4][4] fp32, the reference's convention: world = E [x; 1] (utils/camera.py:4-22)
+ *   mode       0 = mean, 1 = geometric median (Weiszfeld);   iterations: Weiszfeld steps (the Python layer passes 16), unused by mode 0
+ *   aligned    [S][B][21][3]  estimate s in target_cam's frame
+ *   consensus  [B][21][3]
+ *   spread     [B][21]   sqrt(sum_s |aligned_s - consensus|^2 / S) per joint, in the poses' unit (metres)
+ *   deviation  [S][B]    the mean over the 21 joints of |aligned_s - consensus|
+ * Each output may be NULL, not all four.  Outputs must not alias inputs.
+ * fp64 arithmetic from the fp32 inputs, no fused multiply-add, in this order (tests/consensus_oracle.py repeats it); outputs rounded once:
+ *   T = rows 0..2 of inverse(E[b][target_cam]): cofactors over 2x2 minors divided by the determinant (the routine of hmv_project_joints)
+ *   M[r][c] = ((T[r][0] E[0][c] + T[r][1] E[1][c]) + T[r][2] E[2][c]) + T[r][3] E[3][c]  with E = E[b][ref_cam[s]], c < 3
+ *   aligned[r] = (M[r][0] x[0] + M[r][1] x[1]) + M[r][2] x[2]: the poses are root-relative, so no translation applies -- this is
+ *     transform_joints_between_cameras(x) - transform_joints_between_cameras(0)
+ *   mean: the sum over s ascending from 0.0, divided by S
+ *   median, per joint: y_0 = the mean; y_{k+1} = (sum_s x_s / m_s) / (sum_s 1 / m_s) with m_s = max(|x_s - y_k|, 1e-12), both sums over
+ *     s ascending from 0.0; exactly `iterations` steps, no early exit.  |v| = sqrt((v0 v0 + v1 v1) + v2 v2) everywhere
+ *   deviation: the 21 distances summed in joint order from 0.0, divided by 21
+ * A singular E[b][target_cam] gives non-finite outputs for sample b, as in hmv_project_joints.  ref_cam is device data and cannot be
+ * refused: a value outside [0, V) is clamped for the load and makes that estimate's aligned row and deviation NaN -- and through them the
+ * consensus and the spread.
+ * One wave64 per sample, four samples per workgroup, lanes 0..20 one joint each; no LDS, no atomics.  Row b of a B-row call has the bits
+ * of a one-row call.  Takes no handle; asynchronous on `stream`.
+ * HMV_ERR_ARG before any HIP call (hmv_last_error(NULL) names the argument) for: a NULL args, a struct_size other than
+ * sizeof(hmv_consensus_args), S, B or V below 1, target_cam outside [0, V), a mode other than 0 or 1, iterations < 0, a NULL poses /
+ * ref_cam / extrinsic, all four outputs NULL. */
+typedef struct hmv_consensus_args {
+    int32_t struct_size;   /* sizeof(hmv_consensus_args) */
+    int32_t S, B, V;
+    int32_t target_cam;
+    int32_t mode;
+    int32_t iterations;
+    int32_t reserved;      /* 0 */
+    const float *poses;
+    const int32_t *ref_cam;
+    const float *extrinsic;
+    float *aligned;
+    float *consensus;
+    float *spread;
+    float *deviation;
+} hmv_consensus_args;
+
+int hmv_op_pose_consensus(int32_t device, const hmv_consensus_args *args, void *stream);
 
 const char *hmv_version(void);
 

@@ -20,7 +20,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
            "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply", "hmv_op_prepare_frames_occluded",
-           "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus"]
+           "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -85,6 +85,17 @@ class HmvConsensusArgs(ctypes.Structure):
                 ("consensus", ctypes.c_void_p), ("spread", ctypes.c_void_p), ("deviation", ctypes.c_void_p)]
 
 
+class HmvTriangulateArgs(ctypes.Structure):
+    """hmv_triangulate_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("J", ctypes.c_int32),
+                ("S", ctypes.c_int32), ("n_cams", ctypes.c_int32), ("image_size", ctypes.c_int32), ("extrinsic_kind", ctypes.c_int32),
+                ("refit", ctypes.c_int32), ("threshold", ctypes.c_float),
+                ("points", ctypes.c_void_p), ("bbox", ctypes.c_void_p), ("intrinsic", ctypes.c_void_p), ("extrinsic", ctypes.c_void_p),
+                ("present", ctypes.c_void_p), ("joint_mask", ctypes.c_void_p), ("subsets", ctypes.c_void_p), ("frame_cam", ctypes.c_void_p),
+                ("points3d", ctypes.c_void_p), ("reproj_err", ctypes.c_void_p), ("inliers", ctypes.c_void_p), ("winner", ctypes.c_void_p),
+                ("status", ctypes.c_void_p)]
+
+
 class HandMvError(RuntimeError):
     pass
 
@@ -124,6 +135,8 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_orders.restype = ctypes.c_int
     lib.hmv_op_pose_consensus.argtypes = [ci, ctypes.POINTER(HmvConsensusArgs), vp]
     lib.hmv_op_pose_consensus.restype = ctypes.c_int
+    lib.hmv_op_triangulate.argtypes = [ci, ctypes.POINTER(HmvTriangulateArgs), vp]
+    lib.hmv_op_triangulate.restype = ctypes.c_int
     lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
     lib.hmv_op_attention_views.restype = ctypes.c_int
     lib.hmv_set_attention_capture.argtypes = [vp, ctypes.c_uint32]

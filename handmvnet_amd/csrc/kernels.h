@@ -434,6 +434,25 @@ struct PoseConsensusParams {
 };
 hipError_t launch_pose_consensus(const PoseConsensusParams &p, hipStream_t s);
 
+// Triangulation of the per-view 2D joints (triangulate.hip; hmv_op_triangulate in handmv.h): one wave64 per (sample, joint).  bbox,
+// present, joint_mask, subsets, frame_cam, reproj_err, inliers and winner may be null.
+struct TriangulateParams {
+    const float *points;        // [B][V][J][2]
+    const float *bbox;          // [B][V][4]
+    const float *intrinsic;     // [B][V][4]
+    const float *extrinsic;     // [B][V][4][4]
+    const uint8_t *present;     // [B][V]
+    const uint8_t *joint_mask;  // [B][V][J]
+    const int *subsets;         // [S][n_cams], device
+    const int *frame_cam;       // [B], device
+    int B, V, J, S, n_cams, image_size, kind, refit;
+    double threshold;
+    float *points3d;            // [B][J][3]
+    float *reproj_err;          // [B][V][J]
+    int *inliers, *winner, *status;   // [B][J]
+};
+hipError_t launch_triangulate(const TriangulateParams &p, hipStream_t s);
+
 // Sets what hmv_last_error(NULL) returns on the calling thread (engine.hip owns the text).
 void set_thread_error(const std::string &msg);
 

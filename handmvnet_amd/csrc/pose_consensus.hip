@@ -29,19 +29,6 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;
 
-// Rows 0..2 of inverse(e) for a row-major 4x4: solve4_xyz on the four unit vectors, so T[r][k] is cofactor / det exactly (the products
-// with 1 and the sums with 0 round nothing).  A singular e gives inf / NaN.
-__device__ __forceinline__ void inverse_rows(const float *__restrict__ e, double T[3][4]) {
-    double a[16];
-    for (int i = 0; i < 16; ++i) a[i] = (double)e[i];
-    for (int k = 0; k < 4; ++k) {
-        const double unit[4] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0, k == 3 ? 1.0 : 0.0};
-        double col[3];
-        solve4_xyz(a, unit, col);
-        for (int r = 0; r < 3; ++r) T[r][k] = col[r];
-    }
-}
-
 // y = M[:3, :3] x with M = inverse(E_tgt) E_src: M[r][c] = ((T[r][0] E[0][c] + T[r][1] E[1][c]) + T[r][2] E[2][c]) + T[r][3] E[3][c],
 // y[r] = (M[r][0] x[0] + M[r][1] x[1]) + M[r][2] x[2].  bad: the estimate's ref_cam was out of range -- NaN.
 __device__ __forceinline__ void align_point(const double T[3][4], const float *__restrict__ e_src, const float *__restrict__ x, bool bad,

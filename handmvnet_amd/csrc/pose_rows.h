@@ -140,6 +140,19 @@ __device__ double block_sum(double v, double* red) {
     y[2] = (i20 * b[0] + i21 * b[1] + i22 * b[2] + i23 * b[3]) / det;
 }
 
+// Rows 0..2 of inverse(e) for a row-major 4x4: solve4_xyz on the four unit vectors, so T[r][k] is cofactor / det exactly (the products
+// with 1 and the sums with 0 round nothing).  A singular e gives inf / NaN.  (pose_consensus.hip, triangulate.hip.)
+[[maybe_unused]] __device__ __forceinline__ void inverse_rows(const float *__restrict__ e, double T[3][4]) {
+    double a[16];
+    for (int i = 0; i < 16; ++i) a[i] = (double)e[i];
+    for (int k = 0; k < 4; ++k) {
+        const double unit[4] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0, k == 3 ? 1.0 : 0.0};
+        double col[3];
+        solve4_xyz(a, unit, col);
+        for (int r = 0; r < 3; ++r) T[r][k] = col[r];
+    }
+}
+
 // thr[0 .. steps) = torch.linspace(tmin, tmax, steps) in fp32: symmetric fill from both ends, one fma per value (metrics.py:105).
 // Lanes 0 .. steps - 1 write one value each; the caller synchronises.
 __device__ __forceinline__ void fill_thresholds(float* thr, float tmin, float tmax, int steps) {

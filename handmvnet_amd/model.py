@@ -63,6 +63,9 @@ class HandMvNet(torch.nn.Module):
         # where the evaluation step's heat-map targets come from: "batch" = inputs["heatmap"] (the reference's DataLoader product),
         # "joints" = rebuilt inside the loss kernel from inputs["joints_crop_img"] (no target tensor has to exist)
         self.heatmap_targets = "batch"
+        # where the evaluation step's absolute position comes from: None = nowhere (root-relative metrics only), "triangulate" = the
+        # predicted 2D joints triangulated on the device (forward_absolute), which adds {mode}_w_mpjpe and {mode}_root_err
+        self.absolute_root = None
         self.last_losses: Dict[str, object] = {}   # what the reference logs from _calculate_loss, by its log names
         self.last_loss_vector: Optional[torch.Tensor] = None   # the same call's device fp32 [6], in the order of losses.TERMS
 
@@ -419,6 +422,49 @@ class HandMvNet(torch.nn.Module):
                    order_deviation=res["deviation"])
         return out
 
+    def forward_absolute(self, x, bbox, cam_params, view_mask=None, ransac=None, refit=True):
+        """forward() -- or forward_views() when `view_mask` is given -- plus where the hand IS: one triangulation launch on the same
+        stream (handmvnet_amd/triangulation.py, hmv_op_triangulate) fed the call's own `joints_crop_img` and `bbox`; the crop-to-frame
+        mapping happens inside that launch.  Needs cam_params["intrinsic"] [b, v, 4] and cam_params["extrinsic"] [b, v, 4, 4], the
+        data set's camera-to-world matrices.  Returns the forward's dict, its values untouched, plus
+          joints_tri  [b, 21, 3]  the triangulated joints in the frame of each sample's reference camera -- view 0, or the first present
+                                  view of a ragged sample -- in the unit of the extrinsics' translation
+          root_joint  [b, 1, 3]   joints_tri[:, :1]
+          joints_abs  [b, 21, 3]  joints_cam + root_joint (joints_cam is in metres: so must the extrinsics be for this sum)
+          tri_status  [b, 21]     int32, triangulate()'s status per joint
+        ransac: None = one DLT over all present views; a candidate table [S, n_cams] (threshold 10 px), (n_cams, threshold) = every
+        combination of n_cams cameras in itertools order, or (table, threshold).  refit (with ransac only): the result is the DLT over
+        the winner's inlier views."""
+        from .triangulation import candidate_table, triangulate
+        if cam_params is None or "intrinsic" not in cam_params or "extrinsic" not in cam_params:
+            raise ValueError("forward_absolute needs cam_params['intrinsic'] and cam_params['extrinsic']")
+        if bbox is None:
+            raise ValueError("forward_absolute needs bbox: the windows joints_crop_img is in")
+        table, threshold = None, 10.0
+        if ransac is not None:
+            if isinstance(ransac, tuple) and len(ransac) == 2 and np.ndim(ransac[1]) == 0 and np.ndim(ransac[0]) in (0, 2):
+                table, threshold = ransac
+                if np.ndim(table) == 0:
+                    table = candidate_table(self.num_views, int(table), n_iterations=4096)
+            else:
+                table = ransac
+        b, v = int(x.shape[0]), int(x.shape[1])
+        if view_mask is None:
+            out = self.forward(x, bbox, cam_params)
+            present, frame_cam = None, 0
+        else:
+            out = self.forward_views(x, view_mask, bbox, cam_params)
+            mask, _ = self._host_view_mask(view_mask, b, v)
+            present = torch.from_numpy(mask.astype(np.uint8)).to(x.device)
+            frame_cam = mask.argmax(axis=1).astype(np.int32)   # the first present view of each sample
+        crop = out["joints_crop_img"]
+        tri, status = triangulate(crop, cam_params["intrinsic"].to(crop.device).reshape(b, v, 4), cam_params["extrinsic"],
+                                  bbox=bbox.to(crop.device).reshape(b, v, 4), image_size=self.data_params["image_size"], present=present,
+                                  subsets=table, threshold=threshold, refit=bool(refit) and table is not None, frame_cam=frame_cam)
+        root = tri[:, :1]
+        out.update(joints_tri=tri, root_joint=root, joints_abs=out["joints_cam"] + root, tri_status=status)
+        return out
+
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                        image_size=None, view_mask=None):
         """forward() from raw camera frames: `frames` uint8 [b, v, Hf, Wf, 3] and integer crop windows `crop_boxes`
@@ -576,10 +622,18 @@ class HandMvNet(torch.nn.Module):
     def _eval_step(self, batch, mode):
         """The body validation_step and test_step share in the reference (handmvnet.py:468-491 / 493-517): forward + loss +
         metrics.  "loss" is _calculate_loss(...) when the batch carries inputs["heatmap"] (or heatmap_targets == "joints"), and None
-        for a batch without loss labels.  Like the reference, converts inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE."""
+        for a batch without loss labels.  Like the reference, converts inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE.
+        absolute_root == "triangulate" and a batch with inputs["root_joint"]: the forward is forward_absolute (the same outputs plus one
+        triangulation launch; cam_params["extrinsic"] in metres) and the metrics gain {mode}_w_mpjpe (handmvnet.py:412-414) and
+        {mode}_root_err, the distance of the triangulated root from the label's, both in mm.  Unset, nothing changes."""
         inputs = batch["data"]
         view_mask = batch.get("view_mask")   # bool [B, V], True = present: a ragged view set (forward_views and the ragged loss / metrics)
-        if view_mask is None:
+        if self.absolute_root not in (None, "triangulate"):
+            raise ValueError('absolute_root must be None or "triangulate"')
+        absolute = self.absolute_root == "triangulate" and "root_joint" in inputs
+        if absolute:   # the same forward, plus one triangulation launch
+            out = self.forward_absolute(inputs["rgb"], inputs["bboxes"], batch["cam_params"], view_mask=view_mask)
+        elif view_mask is None:
             out = self.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
         else:   # raises ValueError for a sample without a present view, before anything is launched
             out = self.forward_views(inputs["rgb"], view_mask, inputs["bboxes"], batch["cam_params"])
@@ -590,7 +644,14 @@ class HandMvNet(torch.nn.Module):
         loss = None
         if "heatmap" in inputs or self.heatmap_targets == "joints":
             loss = self._calculate_loss(out, inputs, batch["cam_params"], mode=mode, **extra)
-        return {"loss": loss, "metrics": self._calculate_mpjpe(out, inputs, mode=mode, **extra)}
+        metrics = self._calculate_mpjpe(out, inputs, mode=mode, **extra)
+        if absolute:   # handmvnet.py:412-414 with the triangulated root in the place of the root-joint head's
+            from .metrics import PoseMetrics
+            dev = out["joints_cam"].device
+            gt_root = inputs["root_joint"].to(dev)
+            metrics[f"{mode}_w_mpjpe"] = PoseMetrics.mpjpe(out["joints_cam"] + out["root_joint"], inputs["joints_cam"].to(dev) + gt_root) * 1000
+            metrics[f"{mode}_root_err"] = PoseMetrics.mpjpe(out["root_joint"], gt_root) * 1000
+        return {"loss": loss, "metrics": metrics}
 
     def validation_step(self, batch, batch_idx=0):
         """handmvnet.py:468-491: metric keys carry the "val_" prefix (val_mpjpe is what ModelCheckpoint monitors, train.py:34)."""

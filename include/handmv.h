@@ -969,6 +969,76 @@ typedef struct hmv_consensus_args {
 
 int hmv_op_pose_consensus(int32_t device, const hmv_consensus_args *args, void *stream);
 
+/* ---- triangulation: the per-view 2D joints to one 3D point per joint, DLT or DLT + RANSAC over a caller-ordered candidate table ----
+ * The reference's utils/triangulation.py (batch_triangulate_dlt_torch :99-139, batch_triangulate_dlt_ransac_torch :5-58,
+ * calculate_reprojection_error :61-95) as one stateless launch (triangulate.hip), with two deliberate differences: the homogeneous
+ * coordinate is divided out WITHOUT the + 1e-7 of :137 (as triangulate_dlt_torch :170 and triangulate_one_point_dlt :201 do), and the
+ * candidates come as an ORDERED TABLE from the caller instead of random.shuffle on the process-global state (:26).
+ *   points      [B][V][J][2] fp32, 1 <= J <= 64: frame pixels; with `bbox`, crop pixels that are first mapped to the frame
+ *   bbox        NULL, or [B][V][4] fp32 (x1, y1, x2, y2): X = u * ((x2 - x1) / image_size) + x1, Y likewise, in fp32, every operation
+ *               rounded on its own -- batch_cropped_joints_to_joints_img (datasets/utils.py:146-162) in the operation order of
+ *               hmv_op_next_crop_boxes, whose joints_img has the same bits
+ *   intrinsic   [B][V][4] fp32 (fx, fy, cx, cy)
+ *   extrinsic   [B][V][4][4] fp32.  extrinsic_kind 0: camera-to-world, world = E [x; 1] (the data set's cam_params["extrinsic"],
+ *               utils/camera.py:17-20) -- inverted here by the cofactor routine of hmv_project_joints;  1: world-to-camera, what
+ *               triangulation.py takes
+ *   present     NULL, or [B][V] uint8, zero = the view is absent
+ *   joint_mask  NULL, or [B][V][J] uint8, NON-zero = do not use this view for this joint (the sense of joints_img_mask)
+ *               A view is USABLE for joint j when it is present and not masked.
+ *   subsets     NULL (one DLT over all usable views), or DEVICE int32 [S][n_cams]: candidate s names n_cams cameras
+ *   threshold   pixels, read with a table only;  refit: 0 or 1, read with a table only
+ *   frame_cam   NULL (world coordinates), or DEVICE int32 [B]: the result in that camera's frame, W [X; 1] with W the world-to-camera
+ *               rows of that camera (inverse(E) for kind 0)
+ *   points3d    [B][J][3] fp32
+ *   reproj_err  NULL, or [B][V][J] fp32: the written point's reprojection error in every view, NaN for a view that is not usable
+ *   inliers     NULL, or [B][J] int32: the winner's inlier count; without a table the number of usable views
+ *   winner      NULL, or [B][J] int32: the winner's index into `subsets`; -1 without a table and for status 1 and 2
+ *   status      [B][J] int32
+ * The rule, in fp64 from the fp32 inputs, no fused multiply-add, outputs rounded once:
+ *   W_v = rows 0..2 of the world-to-camera matrix;  M_v[r][c] = K_v W_v: rows (fx W0 + cx W2), (fy W1 + cy W2), W2
+ *   the DLT rows of view v: x M_v[2] - M_v[0], then y M_v[2] - M_v[1] (:128-134);  X = v[:3] / v[3] with v the right singular vector of
+ *   the smallest singular value: the rows are rotated one by one (Givens) into a 4x4 triangular factor, whose singular vectors a
+ *   one-sided Jacobi iteration of a fixed number of sweeps finds -- no normal equations
+ *   no table: one DLT over the usable views, ascending
+ *   a table:  candidate s is the DLT over its cameras in the order the row lists them; a candidate that names a camera outside [0, V) or
+ *             one that is not usable is SKIPPED; its inlier count is the number of usable views with |proj - point| < threshold,
+ *             proj = (M [X; 1])[:2] / (M [X; 1])[2], the error sqrt(dx dx + dy dy); the FIRST candidate with the most inliers wins
+ *   refit 1:  the output is the DLT over the winner's inlier views, ascending, when there are at least two of them (not in the reference)
+ * status: 0 ok;  1 no candidate had an inlier: the point is 0, 0, 0 as the reference leaves it;  2 fewer than two usable views, or every
+ * candidate was skipped: the point is NaN;  3 a written coordinate is not finite (a singular extrinsic, coincident cameras, a NaN input,
+ * a frame_cam outside [0, V)).  Device code reports, it does not repair.
+ * One wave64 per (sample, joint), four per workgroup; the V projection matrices sit in LDS, lanes stride over the candidates; no
+ * atomics.  The bits of (b, j) depend on neither B nor the row's place in the call; a masked call has the bits of the call on the
+ * reduced camera list.  Takes no handle; asynchronous on `stream`.  Outputs must not alias inputs.
+ * HMV_ERR_ARG before any HIP call (hmv_last_error(NULL) names the field) for: a NULL args, a struct_size other than
+ * sizeof(hmv_triangulate_args), B < 1 or B * J beyond 2^24, V outside [1, 16], J outside [1, 64], a NULL points / intrinsic / extrinsic /
+ * points3d / status, a table with S outside [1, 4096] or n_cams outside [2, V], a threshold that is not finite or <= 0 with a table, a bbox
+ * with image_size < 1, an extrinsic_kind or a refit other than 0 or 1. */
+typedef struct hmv_triangulate_args {
+    int32_t struct_size;   /* sizeof(hmv_triangulate_args) */
+    int32_t B, V, J;
+    int32_t S, n_cams;     /* the table's shape; ignored when subsets is NULL */
+    int32_t image_size;    /* read with bbox */
+    int32_t extrinsic_kind;
+    int32_t refit;
+    float threshold;
+    const float *points;
+    const float *bbox;
+    const float *intrinsic;
+    const float *extrinsic;
+    const uint8_t *present;
+    const uint8_t *joint_mask;
+    const int32_t *subsets;
+    const int32_t *frame_cam;
+    float *points3d;
+    float *reproj_err;
+    int32_t *inliers;
+    int32_t *winner;
+    int32_t *status;
+} hmv_triangulate_args;
+
+int hmv_op_triangulate(int32_t device, const hmv_triangulate_args *args, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

@@ -25,9 +25,12 @@ def __getattr__(name):
     if name in ("ReferenceSweepEvaluator", "each_reference", "rotations", "as_order_table", "pose_consensus"):   # reference-view sweeps (orders.py)
         from . import orders
         return getattr(orders, name)
-    if name in ("triangulate", "candidate_table", "batch_triangulate_dlt_torch", "batch_triangulate_dlt_ransac_torch"):   # absolute position (triangulation.py)
+    if name in ("triangulate", "candidate_table", "batch_triangulate_dlt_torch", "batch_triangulate_dlt_ransac_torch", "triangulate_dlt"):   # absolute position (triangulation.py)
         from . import triangulation
         return getattr(triangulation, name)
+    if name in ("heatmap_peaks", "heatmaps_to_coordinates", "confidence_mask"):   # heat-map confidences (confidence.py)
+        from . import confidence
+        return getattr(confidence, name)
     if name in ("JointsToVertices", "hand_ik", "rigid_unapply"):   # hand pose parameters and MANO vertices (ik.py)
         from . import ik
         return getattr(ik, name)

@@ -20,7 +20,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_seq_eval_history_floats", "hmv_seq_eval_add", "hmv_forward_subsets", "hmv_set_attention_capture", "hmv_attention_shape",
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
            "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply", "hmv_op_prepare_frames_occluded",
-           "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate"]
+           "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate",
+           "hmv_op_heatmap_peaks", "hmv_op_confidence_select"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -96,6 +97,20 @@ class HmvTriangulateArgs(ctypes.Structure):
                 ("status", ctypes.c_void_p)]
 
 
+class HmvPeaksArgs(ctypes.Structure):
+    """hmv_peaks_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("N", ctypes.c_int32), ("J", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("heatmap", ctypes.c_void_p), ("maxval", ctypes.c_void_p), ("index", ctypes.c_void_p), ("preds", ctypes.c_void_p)]
+
+
+class HmvConfidenceSelectArgs(ctypes.Structure):
+    """hmv_confidence_select_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("J", ctypes.c_int32),
+                ("carry", ctypes.c_int32), ("threshold", ctypes.c_double), ("step", ctypes.c_double),
+                ("conf", ctypes.c_void_p), ("present", ctypes.c_void_p), ("joint_mask", ctypes.c_void_p), ("mask_out", ctypes.c_void_p),
+                ("level", ctypes.c_void_p), ("lowered", ctypes.c_void_p), ("selected", ctypes.c_void_p)]
+
+
 class HandMvError(RuntimeError):
     pass
 
@@ -137,6 +152,10 @@ def load() -> ctypes.CDLL:
     lib.hmv_op_pose_consensus.restype = ctypes.c_int
     lib.hmv_op_triangulate.argtypes = [ci, ctypes.POINTER(HmvTriangulateArgs), vp]
     lib.hmv_op_triangulate.restype = ctypes.c_int
+    lib.hmv_op_heatmap_peaks.argtypes = [ci, ctypes.POINTER(HmvPeaksArgs), vp]
+    lib.hmv_op_heatmap_peaks.restype = ctypes.c_int
+    lib.hmv_op_confidence_select.argtypes = [ci, ctypes.POINTER(HmvConfidenceSelectArgs), vp]
+    lib.hmv_op_confidence_select.restype = ctypes.c_int
     lib.hmv_op_attention_views.argtypes = [ci, ci, fp, fp, ci, ctypes.POINTER(ci), ci, fp, vp]
     lib.hmv_op_attention_views.restype = ctypes.c_int
     lib.hmv_set_attention_capture.argtypes = [vp, ctypes.c_uint32]

@@ -66,6 +66,9 @@ class HandMvNet(torch.nn.Module):
         # where the evaluation step's absolute position comes from: None = nowhere (root-relative metrics only), "triangulate" = the
         # predicted 2D joints triangulated on the device (forward_absolute), which adds {mode}_w_mpjpe and {mode}_root_err
         self.absolute_root = None
+        # how that triangulation treats views whose heat-map peak is low: None = every view counts alike; a threshold, or
+        # (threshold, step, carry) = forward_absolute(confidence=...), which leaves such views out per joint
+        self.absolute_confidence = None
         self.last_losses: Dict[str, object] = {}   # what the reference logs from _calculate_loss, by its log names
         self.last_loss_vector: Optional[torch.Tensor] = None   # the same call's device fp32 [6], in the order of losses.TERMS
 
@@ -422,7 +425,7 @@ class HandMvNet(torch.nn.Module):
                    order_deviation=res["deviation"])
         return out
 
-    def forward_absolute(self, x, bbox, cam_params, view_mask=None, ransac=None, refit=True):
+    def forward_absolute(self, x, bbox, cam_params, view_mask=None, ransac=None, refit=True, confidence=None):
         """forward() -- or forward_views() when `view_mask` is given -- plus where the hand IS: one triangulation launch on the same
         stream (handmvnet_amd/triangulation.py, hmv_op_triangulate) fed the call's own `joints_crop_img` and `bbox`; the crop-to-frame
         mapping happens inside that launch.  Needs cam_params["intrinsic"] [b, v, 4] and cam_params["extrinsic"] [b, v, 4, 4], the
@@ -434,7 +437,18 @@ class HandMvNet(torch.nn.Module):
           tri_status  [b, 21]     int32, triangulate()'s status per joint
         ransac: None = one DLT over all present views; a candidate table [S, n_cams] (threshold 10 px), (n_cams, threshold) = every
         combination of n_cams cameras in itertools order, or (table, threshold).  refit (with ransac only): the result is the DLT over
-        the winner's inlier views."""
+        the winner's inlier views.
+        confidence: None = every present view counts alike.  A threshold, or (threshold, step, carry): two more launches on the same
+        stream -- the peak of every heat map (handmvnet_amd/confidence.py, hmv_op_heatmap_peaks on the call's own `heatmap`) and the
+        reference's triangulate_dlt selection on it (hmv_op_confidence_select: per joint the views whose peak exceeds the threshold,
+        lowered by `step`, default 0.05, until two remain; carry, default False, keeps what one joint lowered for the sample's later
+        ones) -- and the triangulation, DLT or RANSAC, uses the selected views only.  Adds
+          joints_conf [b, v, 21]     the peak of each joint's heat map (a view_mask's absent views: the peak of their zero maps, 0)
+          joints_peak [b, v, 21, 2]  where it lies, in crop pixels: (x, y) * image_size / heatmap_size, 0-based like joints_crop_img.
+                                     It is made from `index` by five elementwise torch ops on [b, v, 21] device tensors (remainder, floor
+                                     division, stack, multiply, divide) beside the two library launches: nothing is read back
+          tri_level   [b, 21]        the threshold that decided each joint
+          tri_views   [b, 21]        int32, the views kept; below two, tri_status is 2 and the joint NaN"""
         from .triangulation import candidate_table, triangulate
         if cam_params is None or "intrinsic" not in cam_params or "extrinsic" not in cam_params:
             raise ValueError("forward_absolute needs cam_params['intrinsic'] and cam_params['extrinsic']")
@@ -448,6 +462,15 @@ class HandMvNet(torch.nn.Module):
                     table = candidate_table(self.num_views, int(table), n_iterations=4096)
             else:
                 table = ransac
+        gate = None
+        if confidence is not None:
+            from .confidence import check_schedule, heatmap_peaks
+            if isinstance(confidence, (tuple, list)):
+                if len(confidence) != 3:
+                    raise ValueError("confidence must be None, a threshold or (threshold, step, carry)")
+                gate = check_schedule(confidence[0], confidence[1]) + (bool(confidence[2]),)
+            else:
+                gate = check_schedule(confidence, 0.05) + (False,)
         b, v = int(x.shape[0]), int(x.shape[1])
         if view_mask is None:
             out = self.forward(x, bbox, cam_params)
@@ -458,11 +481,22 @@ class HandMvNet(torch.nn.Module):
             present = torch.from_numpy(mask.astype(np.uint8)).to(x.device)
             frame_cam = mask.argmax(axis=1).astype(np.int32)   # the first present view of each sample
         crop = out["joints_crop_img"]
-        tri, status = triangulate(crop, cam_params["intrinsic"].to(crop.device).reshape(b, v, 4), cam_params["extrinsic"],
-                                  bbox=bbox.to(crop.device).reshape(b, v, 4), image_size=self.data_params["image_size"], present=present,
-                                  subsets=table, threshold=threshold, refit=bool(refit) and table is not None, frame_cam=frame_cam)
+        extra = {}
+        if gate is not None:   # the peaks launch on the forward's own heat map; the select launch runs inside triangulate()
+            hm = out["heatmap"]
+            conf, index, _ = heatmap_peaks(hm.reshape(b, v, 21, hm.shape[-2], hm.shape[-1]))
+            extra = dict(confidences=conf, confidence_threshold=gate[0], confidence_step=gate[1], carry=gate[2], return_details=True)
+        res = triangulate(crop, cam_params["intrinsic"].to(crop.device).reshape(b, v, 4), cam_params["extrinsic"],
+                          bbox=bbox.to(crop.device).reshape(b, v, 4), image_size=self.data_params["image_size"], present=present,
+                          subsets=table, threshold=threshold, refit=bool(refit) and table is not None, frame_cam=frame_cam, **extra)
+        tri, status = (res["points3d"], res["status"]) if gate is not None else res
         root = tri[:, :1]
         out.update(joints_tri=tri, root_joint=root, joints_abs=out["joints_cam"] + root, tri_status=status)
+        if gate is not None:
+            wmap = int(out["heatmap"].shape[-1])
+            xy = torch.stack([index % wmap, torch.div(index, wmap, rounding_mode="floor")], dim=-1).float()
+            peak = xy * self.data_params["image_size"] / self.data_params["heatmap_size"]   # handmvnet.py:252, on the hard peak
+            out.update(joints_conf=conf, joints_peak=peak, tri_level=res["level"], tri_views=res["selected"])
         return out
 
     def forward_frames(self, frames, crop_boxes, cam_params=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
@@ -625,14 +659,16 @@ class HandMvNet(torch.nn.Module):
         for a batch without loss labels.  Like the reference, converts inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE.
         absolute_root == "triangulate" and a batch with inputs["root_joint"]: the forward is forward_absolute (the same outputs plus one
         triangulation launch; cam_params["extrinsic"] in metres) and the metrics gain {mode}_w_mpjpe (handmvnet.py:412-414) and
-        {mode}_root_err, the distance of the triangulated root from the label's, both in mm.  Unset, nothing changes."""
+        {mode}_root_err, the distance of the triangulated root from the label's, both in mm.  Unset, nothing changes.
+        absolute_confidence (read with absolute_root only) is that forward_absolute's `confidence`; None, nothing changes."""
         inputs = batch["data"]
         view_mask = batch.get("view_mask")   # bool [B, V], True = present: a ragged view set (forward_views and the ragged loss / metrics)
         if self.absolute_root not in (None, "triangulate"):
             raise ValueError('absolute_root must be None or "triangulate"')
         absolute = self.absolute_root == "triangulate" and "root_joint" in inputs
         if absolute:   # the same forward, plus one triangulation launch
-            out = self.forward_absolute(inputs["rgb"], inputs["bboxes"], batch["cam_params"], view_mask=view_mask)
+            out = self.forward_absolute(inputs["rgb"], inputs["bboxes"], batch["cam_params"], view_mask=view_mask,
+                                        confidence=self.absolute_confidence)
         elif view_mask is None:
             out = self.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
         else:   # raises ValueError for a sample without a present view, before anything is launched

@@ -63,7 +63,8 @@ def _intrinsic_rows(intrinsics: torch.Tensor, B: int, V: int, what: str = "intri
 
 def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, present=None, joint_mask=None, subsets=None,
                 threshold: float = 10.0, refit: bool = False, frame_cam=None, extrinsic_kind: str = "cam_to_world",
-                return_details: bool = False):
+                return_details: bool = False, confidences=None, confidence_threshold: float = 0.5, confidence_step: float = 0.05,
+                carry: bool = False):
     """One 3D point per (sample, joint) from its 2D positions in V views (one launch; fp64 arithmetic from the fp32 inputs).
       points      [B, V, J, 2] device tensor, J <= 64: frame pixels -- or crop pixels when `bbox` [B, V, 4] (x1, y1, x2, y2) and
                   `image_size` are given (the model's joints_crop_img and the batch's bboxes; the mapping has joints_to_frame's bits)
@@ -76,10 +77,14 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
                   camera; its inliers are the usable views whose reprojection error is below `threshold` pixels; the FIRST candidate
                   with the most inliers wins.  refit=True: the result is the DLT over the winner's inlier views.
       frame_cam   None: world coordinates.  An int, or [B] indices (list, array, device tensor): the result in that camera's frame.
+      confidences None, or [B, V, J] (heatmap_peaks' maxval): one more launch first (confidence.confidence_mask with
+                  confidence_threshold, confidence_step, carry and this call's present and joint_mask) decides per joint which views
+                  are left out, and its mask is this call's joint_mask -- the reference's triangulate_dlt (:205-242).
     Returns points3d [B, J, 3] fp32 (in the unit of the extrinsics' translation) and status [B, J] int32 -- 0 ok; 1 no candidate had
     an inlier (the point is 0, 0, 0, as the reference leaves it); 2 fewer than two usable views or every candidate skipped (NaN);
     3 a coordinate is not finite.  return_details=True: a dict with those two and reproj_err [B, V, J] (the point's error in every
-    view, NaN where the view is not usable), inliers [B, J], winner [B, J] (index into the table; -1 without one)."""
+    view, NaN where the view is not usable), inliers [B, J], winner [B, J] (index into the table; -1 without one); with
+    `confidences` also level [B, J] (the confidence threshold that decided), lowered [B, J] and selected [B, J] (views kept)."""
     if extrinsic_kind not in KINDS:
         raise ValueError('extrinsic_kind must be "cam_to_world" or "world_to_cam"')
     if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[-1] != 2:
@@ -101,6 +106,13 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
     for name, t, shape in (("present", present, (B, V)), ("joint_mask", joint_mask, (B, V, J))):
         if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape):
             raise ValueError(f"{name} must be a {list(shape)} tensor")
+    if confidences is not None:
+        from .confidence import check_schedule
+        if not isinstance(confidences, torch.Tensor) or tuple(confidences.shape) != (B, V, J):
+            raise ValueError(f"confidences must be a [{B}, {V}, {J}] tensor")
+        if confidences.dtype != torch.float32:
+            raise ValueError(f"confidences must be float32, got {confidences.dtype}")
+        check_schedule(confidence_threshold, confidence_step)
     table = None
     if subsets is not None:
         if isinstance(subsets, torch.Tensor):
@@ -122,6 +134,12 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
     if not points.is_cuda:
         raise _lib.HandMvError("handmvnet_amd runs on MI355X only: points must be a CUDA(HIP) tensor (no CPU fallback)")
     dev = points.device
+    gate = None
+    if confidences is not None:   # the select launch first, on the same stream; its mask holds the caller's joint_mask and the absent views
+        from .confidence import confidence_mask
+        gate = confidence_mask(confidences.to(dev), confidence_threshold, confidence_step, carry, present=present, joint_mask=joint_mask,
+                               return_details=True)
+        joint_mask = gate["mask"]
     fc = None
     if frame_cam is not None:
         if isinstance(frame_cam, torch.Tensor) and frame_cam.is_cuda:
@@ -176,7 +194,10 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
         _lib.check(_lib.load().hmv_op_triangulate(idx, ctypes.byref(a), stream))
     del pts, it, ex, bb, pr, jm, tab, fc   # allocated on the stream the kernel runs on: the caching allocator reuses them in stream order
     if return_details:
-        return {"points3d": out3d, "status": status, "reproj_err": err, "inliers": inl, "winner": win}
+        res = {"points3d": out3d, "status": status, "reproj_err": err, "inliers": inl, "winner": win}
+        if gate is not None:
+            res.update(level=gate["level"], lowered=gate["lowered"], selected=gate["selected"])
+        return res
     return out3d, status
 
 
@@ -211,3 +232,21 @@ def batch_triangulate_dlt_ransac_torch(kp2ds, Ks, Extrs, n_cams=3, n_iterations=
         raise ValueError("kp2ds must be a [B, N, J, 2] tensor")
     table = candidate_table(int(kp2ds.shape[1]), n_cams, n_iterations, seed)
     return triangulate(kp2ds, Ks, Extrs, subsets=table, threshold=reprojection_threshold, extrinsic_kind="world_to_cam")[0]
+
+
+def triangulate_dlt(pts, confis, Ks, Extrs, confi_thres=0.5):
+    """utils/triangulation.py:205-242 on the device, same arguments, as device tensors: pts [N, J, 2], confis [N, J], Ks [N, 3, 3],
+    Extrs [N, 4, 4] WORLD-TO-CAMERA of ONE sample -> [J, 3].  Two launches: the camera selection with the reference's threshold walk
+    (steps of 0.05, carried from joint to joint as the reference does: carry=True), then the DLT over the selected views.
+    Deliberately different from the reference in one way: a joint for which the threshold reaches zero with fewer than two views
+    comes back as NaN; the reference triangulates it from one camera or raises.  Raises ValueError for a Ks with skew or a last row
+    other than 0, 0, 1."""
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or pts.shape[-1] != 2:
+        raise ValueError("pts must be a [N, J, 2] tensor")
+    if not isinstance(confis, torch.Tensor) or tuple(confis.shape) != tuple(pts.shape[:2]):
+        raise ValueError("confis must be a [N, J] tensor")
+    if not isinstance(Ks, torch.Tensor) or Ks.dim() != 3 or not isinstance(Extrs, torch.Tensor) or Extrs.dim() != 3:
+        raise ValueError("Ks must be [N, 3, 3] and Extrs [N, 4, 4]")
+    _check_ks(Ks[None])
+    return triangulate(pts[None], Ks[None], Extrs[None], extrinsic_kind="world_to_cam", confidences=confis[None],
+                       confidence_threshold=confi_thres, confidence_step=0.05, carry=True)[0][0]

@@ -1039,6 +1039,76 @@ typedef struct hmv_triangulate_args {
 
 int hmv_op_triangulate(int32_t device, const hmv_triangulate_args *args, void *stream);
 
+/* ---- heat-map confidences: the peak of every score map, and the views a confidence threshold keeps per joint ----
+ * Two stateless launches (confidence.hip) that put the reference's confidence-gated triangulation on the device:
+ * heatmaps_to_coordinates (models/utils.py:65-82) and the camera selection of triangulate_dlt (utils/triangulation.py:227-236).
+ * The selection's mask_out is hmv_op_triangulate's joint_mask; the triangulation itself is that entry, unchanged.
+ *
+ * hmv_op_heatmap_peaks
+ *   heatmap   [N][J][h][w] fp32, contiguous: the NCHW map every forward returns (N = frames)
+ *   maxval    NULL, or [N][J] fp32: the maximum of the map
+ *   index     NULL, or [N][J] int32: where it lies, flat y * w + x, 0-based
+ *   preds     NULL, or [N][J][2] fp32: the reference's 1-based (index % w + 1, index / w + 1), times (maxval > 0)
+ *   (not all three NULL)
+ * The rule is torch.max(scores.view(N, J, -1), 2): the largest value wins; among equal values the LOWEST flat index wins (+0 and -0 are
+ * equal); a NaN beats every number and the FIRST NaN wins -- the NaN in maxval is the report, its preds are 0; a map of -inf only gives
+ * -inf at index 0.  One wave64 per map, four per workgroup; 16-byte loads when h * w is a multiple of 4 and heatmap is 16-byte aligned,
+ * scalar loads otherwise: the same bits either way.  The bits of a map depend on neither N nor its place in the call.  No byte outside
+ * the maps is read.
+ * HMV_ERR_ARG before any HIP call for: a NULL args, a struct_size other than sizeof(hmv_peaks_args), N, J, h or w below 1, N * J beyond
+ * 2^24, h * w beyond 2^20, a NULL heatmap, all three outputs NULL.
+ *
+ * hmv_op_confidence_select
+ *   conf        [B][V][J] fp32: maxval of a [B * V] frame batch as it lies
+ *   present     NULL, or [B][V] uint8;  joint_mask  NULL, or [B][V][J] uint8: the senses of hmv_op_triangulate
+ *   threshold, step   doubles;  carry  0 or 1
+ *   mask_out    [B][V][J] uint8: 1 = leave this view out for this joint.  It includes the caller's joint_mask and absent views: feed it
+ *               to hmv_op_triangulate as joint_mask
+ *   level       NULL, or [B][J] fp32: the threshold that decided, (float)t
+ *   lowered     NULL, or [B][J] int32: the decrements spent on this joint
+ *   selected    NULL, or [B][J] int32: the views kept
+ * The rule, per sample (t is a double, lowered by repeated subtraction, never recomputed from a level count):
+ *   t = threshold                       -- once per sample when carry == 1: what joint j lowered, every later joint starts from, as in the
+ *                                          reference, which never resets it;  for every joint anew when carry == 0
+ *   for j:  loop { sel_v = usable(v, j) && conf[v][j] > (float)t;  n = count(sel)
+ *                  if (t <= 0) break;  if (n <= 1) { t -= step; ++lowered[j]; } else break; }
+ *           mask_out[v][j] = !sel_v;  level[j] = (float)t;  selected[j] = n
+ * The comparison is made in fp32 with t rounded to fp32 -- what numpy makes of float32_array > python_float -- so float32(0.4) > 0.4 is
+ * false.  A view that is not usable is neither selected nor counted: a gated call has the decisions of the call on the reduced camera
+ * list.  A NaN confidence is never selected.  Deliberately different from the reference in one way: where t reaches <= 0 with fewer than
+ * two views selected the reference triangulates from one camera or raises; here `selected` says so and hmv_op_triangulate reports status
+ * 2 and NaN for that joint.  One wave64 per sample, four per workgroup; at most threshold / step + 2 ballots per level walk.
+ * HMV_ERR_ARG before any HIP call for: a NULL args, a struct_size other than sizeof(hmv_confidence_select_args), B < 1, V outside
+ * [1, 16], J outside [1, 64], a carry other than 0 or 1, a threshold or a step that is not finite, step <= 0, threshold / step > 1024,
+ * a NULL conf or mask_out.
+ * Both take no handle, are asynchronous on `stream`, use no atomics; outputs must not alias inputs. */
+typedef struct hmv_peaks_args {
+    int32_t struct_size;   /* sizeof(hmv_peaks_args) */
+    int32_t N, J, h, w;
+    const float *heatmap;
+    float *maxval;
+    int32_t *index;
+    float *preds;
+} hmv_peaks_args;
+
+int hmv_op_heatmap_peaks(int32_t device, const hmv_peaks_args *args, void *stream);
+
+typedef struct hmv_confidence_select_args {
+    int32_t struct_size;   /* sizeof(hmv_confidence_select_args) */
+    int32_t B, V, J;
+    int32_t carry;
+    double threshold, step;
+    const float *conf;
+    const uint8_t *present;
+    const uint8_t *joint_mask;
+    uint8_t *mask_out;
+    float *level;
+    int32_t *lowered;
+    int32_t *selected;
+} hmv_confidence_select_args;
+
+int hmv_op_confidence_select(int32_t device, const hmv_confidence_select_args *args, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

@@ -21,7 +21,9 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_read_attention", "hmv_op_attention_probs", "hmv_eval_breakdown_doubles", "hmv_eval_record_floats",
            "hmv_eval_breakdown_add", "hmv_op_hand_ik", "hmv_op_rigid_unapply", "hmv_op_prepare_frames_occluded",
            "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate",
-           "hmv_op_heatmap_peaks", "hmv_op_confidence_select"]
+           "hmv_op_heatmap_peaks", "hmv_op_confidence_select", "hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax",
+           "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
+           "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -262,6 +264,23 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_frames_occlusions.argtypes = [vp, ci, fp, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                                   fp, fp, ci, ctypes.POINTER(ci), fp, fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames_occlusions.restype = ctypes.c_int
+    # the non-GEMM kernels of a forward (every operand a device pointer)
+    cf = ctypes.c_float
+    lib.hmv_op_input_layout.argtypes = [ci, ci, ci, fp, ci, ci, ci, fp, fp, vp]
+    lib.hmv_op_maxpool.argtypes = [ci, ci, fp, ci, ci, ci, ci, fp, vp]
+    lib.hmv_op_soft_argmax.argtypes = [ci, fp, ci, ci, ci, ci, fp, fp, cf, cf, fp, vp]
+    lib.hmv_op_sample_gather.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, fp, vp]
+    lib.hmv_op_sample_blend.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, fp, ci, ci, vp]
+    lib.hmv_op_tokens_finalize.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp, ci, fp, fp, fp, fp, vp]
+    lib.hmv_op_layernorm.argtypes = [ci, fp, ci, ci, ci, fp, fp, fp, ci, fp, fp, fp, vp]
+    lib.hmv_op_splitk_reduce.argtypes = [ci, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, ci, vp]
+    lib.hmv_op_splitk_layernorm.argtypes = [ci, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, fp, fp, fp, ci, fp, fp, fp, vp]
+    lib.hmv_op_add_pe.argtypes = [ci, fp, ci, ci, ci, fp, ci, fp, fp, ci, vp]
+    lib.hmv_op_cheb_mix.argtypes = [ci, fp, ci, ci, ci, fp, fp, ci, fp, ci, vp]
+    for name in ("hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax", "hmv_op_sample_gather", "hmv_op_sample_blend",
+                 "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce", "hmv_op_splitk_layernorm", "hmv_op_add_pe",
+                 "hmv_op_cheb_mix"):
+        getattr(lib, name).restype = ctypes.c_int
     lib.hmv_set_graphs.argtypes = [vp, ci]
     lib.hmv_set_graphs.restype = ctypes.c_int
     lib.hmv_graph_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]

@@ -3485,3 +3485,159 @@ extern "C" int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base,
     release();
     return HMV_OK;
 }
+
+// ------------------------------------------------------------------ the non-GEMM kernels of a forward, one launcher per entry
+// (op-level float64 tests: tests/test_gpu_ops_f64.py).  Every operand is a device pointer of the caller; argument check, hipSetDevice, the
+// launcher the engine itself calls, hipStreamSynchronize.  Nothing is allocated and nothing outlives the call.
+namespace {
+int op_bad(const char *who, const char *why) {
+    g_create_err = std::string(who) + ": " + why;
+    return HMV_ERR_ARG;
+}
+// Runs one launcher on `stream` of `device` and waits for it
+template <class F>
+int op_run(const char *who, int32_t device, void *stream, F &&launch) {
+    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { g_create_err = std::string(who) + ": " + hipGetErrorString(e); return HMV_ERR_HIP; }
+    return HMV_OK;
+}
+}  // namespace
+
+extern "C" int hmv_op_input_layout(int32_t device, int32_t kind, int32_t mode, const float *x, int32_t N, int32_t H, int32_t W, void *out,
+                                   int32_t *sat, void *stream) {
+    static const char *who = "hmv_op_input_layout";
+    if (!x || !out || N <= 0 || H <= 0 || W <= 0) return op_bad(who, "null operand or non-positive size");
+    if (kind < 0 || kind > 1 || mode < 0 || mode > 2) return op_bad(who, "kind must be 0 (pixel rows) or 1 (space-to-depth), mode 0 (fp32), 1 (fp16) or 2 (split pairs)");
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        if (kind == 1) return launch_nchw_to_s2d(x, out, N, H, W, mode, s, sat);
+        if (mode == 2) return launch_nchw_to_nhwc_split(x, out, N, H, W, s, sat);
+        if (mode == 1) return launch_nchw_to_nhwc8_f16(x, out, N, H, W, s);
+        return launch_nchw_to_nhwc4(x, static_cast<float *>(out), N, H, W, s);
+    });
+}
+
+extern "C" int hmv_op_maxpool(int32_t device, int32_t mode, const void *in, int32_t N, int32_t H, int32_t W, int32_t C, void *out, void *stream) {
+    static const char *who = "hmv_op_maxpool";
+    if (!in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0) return op_bad(who, "null operand or non-positive size");
+    if (mode < 0 || mode > 2) return op_bad(who, "mode must be 0 (fp32), 1 (fp16) or 2 (split pairs)");
+    if (C % (mode == 0 ? 4 : 8)) return op_bad(who, "C must be a multiple of 4 (fp32) or 8 (fp16, split pairs)");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;   // MaxPool2d(3, 2, 1)
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        if (mode == 2) return launch_maxpool3s2_split(in, out, N, H, W, C, Ho, Wo, s);
+        if (mode == 1) return launch_maxpool3s2_f16(in, out, N, H, W, C, Ho, Wo, s);
+        return launch_maxpool3s2(static_cast<const float *>(in), static_cast<float *>(out), N, H, W, C, Ho, Wo, s);
+    });
+}
+
+extern "C" int hmv_op_soft_argmax(int32_t device, const float *hm, int32_t ld, int32_t N, int32_t h, int32_t w, float *coords, float *crop_img,
+                                  float image_size, float heatmap_size, float *hm_nchw, void *stream) {
+    static const char *who = "hmv_op_soft_argmax";
+    if (!hm || !coords || !crop_img || N <= 0 || h <= 0 || w <= 0) return op_bad(who, "null operand or non-positive size");
+    if (ld < 21 || (int64_t)N * 21 > INT32_MAX) return op_bad(who, "ld must hold the 21 joint channels");
+    if (!(heatmap_size > 0.f)) return op_bad(who, "heatmap_size must be positive");
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_soft_argmax(hm, ld, N, h, w, coords, crop_img, image_size, heatmap_size, hm_nchw, s); });
+}
+
+extern "C" int hmv_op_sample_gather(int32_t device, const void *feat, int32_t N, int32_t H, int32_t W, int32_t C, int32_t elem_bytes,
+                                    const float *coords, void *out, void *stream) {
+    static const char *who = "hmv_op_sample_gather";
+    if (!feat || !coords || !out || N <= 0 || C <= 0) return op_bad(who, "null operand or non-positive size");
+    if (H < 2 || W < 2) return op_bad(who, "maps of at least 2 x 2 pixels (grid_sample's own unnormalisation divides by size - 1)");
+    if ((elem_bytes != 2 && elem_bytes != 4) || ((int64_t)C * elem_bytes) % 16) return op_bad(who, "elem_bytes 2 or 4, pixel rows of whole 16-byte chunks");
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        return launch_sample_gather(static_cast<const float *>(feat), N, H, W, C, coords, static_cast<float *>(out), s, elem_bytes);
+    });
+}
+
+extern "C" int hmv_op_sample_blend(int32_t device, const float *s4, int32_t lds4, int32_t C, int32_t N, int32_t H, int32_t W, const float *coords,
+                                   float *tokens, int32_t ldt, int32_t col0, void *stream) {
+    static const char *who = "hmv_op_sample_blend";
+    if (!s4 || !coords || !tokens || N <= 0 || C <= 0) return op_bad(who, "null operand or non-positive size");
+    if (H < 2 || W < 2) return op_bad(who, "maps of at least 2 x 2 pixels (grid_sample's own unnormalisation divides by size - 1)");
+    if (lds4 < C || col0 < 0 || (int64_t)col0 + C > ldt) return op_bad(who, "lds4 >= C and columns [col0, col0 + C) inside a token row of ldt");
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_sample_blend(s4, lds4, C, N, H, W, coords, tokens, ldt, col0, s); });
+}
+
+extern "C" int hmv_op_tokens_finalize(int32_t device, float *tokens, int32_t ldt, int32_t d, int32_t fdim, int32_t N, int32_t V, const int32_t *fpos,
+                                      const float *coords, const float *bbox, const float *intr, int32_t pos_mask, const float *pe, float *raw_copy,
+                                      void *pairs, int32_t *sat, void *stream) {
+    static const char *who = "hmv_op_tokens_finalize";
+    if (!tokens || N <= 0 || fdim <= 0) return op_bad(who, "null operand or non-positive size");
+    if (pos_mask < 0 || pos_mask > 3) return op_bad(who, "pos_mask is 1 (pos2d) | 2 (crop FoV)");
+    if (d != fdim + ((pos_mask & 1) ? 2 : 0) + ((pos_mask & 2) ? 10 : 0) || ldt < d) return op_bad(who, "d = fdim + 2 (pos2d) + 10 (crop FoV), d <= ldt");
+    if (((pos_mask & 1) && !coords) || ((pos_mask & 2) && (!bbox || !intr))) return op_bad(who, "pos2d needs coords, the crop FoV needs bbox and intr");
+    if (!fpos && V <= 0) return op_bad(who, "V must be positive in the uniform form");
+    if (fpos && raw_copy) return op_bad(who, "the ragged form has no raw_copy");
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        if (fpos) return launch_tokens_finalize_views(tokens, ldt, d, fdim, N, fpos, coords, bbox, intr, pos_mask, pe, s, pairs, sat);
+        return launch_tokens_finalize(tokens, ldt, d, fdim, N, V, coords, bbox, intr, pos_mask, pe, raw_copy, s, pairs, sat);
+    });
+}
+
+extern "C" int hmv_op_layernorm(int32_t device, const float *x, int32_t ldx, int32_t rows, int32_t d, const float *g1, const float *b1, float *y,
+                                int32_t ldy, const float *g2, const float *b2, float *y2, void *stream) {
+    static const char *who = "hmv_op_layernorm";
+    if (!x || !g1 || !b1 || !y || rows <= 0 || d <= 0) return op_bad(who, "null operand or non-positive size");
+    if (d > 1024 || ldy > 1024) return op_bad(who, "rows of at most 1024 columns (d, ldy)");
+    if (ldx < d || ldy < d) return op_bad(who, "ldx >= d and ldy >= d");
+    if ((g2 != nullptr) != (y2 != nullptr) || (b2 != nullptr) != (y2 != nullptr)) return op_bad(who, "the second norm takes g2, b2 and y2 together");
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_layernorm(x, ldx, rows, d, g1, b1, y, ldy, g2, b2, y2, s); });
+}
+
+namespace {
+const char *splitk_args_bad(const float *slab, int32_t S, int32_t rows, int32_t lds, int32_t N, const float *bias, const float *res, int32_t ldr,
+                            int32_t rg_out, int32_t rg_in, const void *out, int32_t ldc) {
+    if (!slab || !bias || !out || rows <= 0 || N <= 0) return "null operand or non-positive size";
+    if (S < 1) return "S must be positive";
+    if (lds < N || ldc < N || (res && ldr < N)) return "lds, ldc and ldr must hold N columns";
+    if (rg_out < 0 || (rg_out > 0 && rg_in < rg_out)) return "residual row groups: rg_out = 0, or 0 < rg_out <= rg_in";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int hmv_op_splitk_reduce(int32_t device, const float *slab, int32_t S, int32_t rows, int32_t lds, int32_t N, const float *bias,
+                                    const float *res, int32_t ldr, int32_t rg_out, int32_t rg_in, int32_t act, float *out, int32_t ldc, void *stream) {
+    static const char *who = "hmv_op_splitk_reduce";
+    if (const char *why = splitk_args_bad(slab, S, rows, lds, N, bias, res, ldr, rg_out, rg_in, out, ldc)) return op_bad(who, why);
+    if (act < ACT_NONE || act > ACT_LEAKY) return op_bad(who, "act must be 0 (none), 1 (ReLU), 2 (GELU) or 3 (LeakyReLU)");
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_splitk_reduce(slab, S, rows, lds, N, bias, res, ldr, rg_out, rg_in, act, out, ldc, s); });
+}
+
+extern "C" int hmv_op_splitk_layernorm(int32_t device, const float *slab, int32_t S, int32_t rows, int32_t lds, int32_t d, const float *bias,
+                                       const float *res, int32_t ldr, int32_t rg_out, int32_t rg_in, const float *g1, const float *b1, float *y,
+                                       int32_t ldy, const float *g2, const float *b2, float *y2, void *stream) {
+    static const char *who = "hmv_op_splitk_layernorm";
+    if (const char *why = splitk_args_bad(slab, S, rows, lds, d, bias, res, ldr, rg_out, rg_in, y, ldy)) return op_bad(who, why);
+    if (S != 4) return op_bad(who, "the fused form exists for S = 4 slices only");
+    if (!g1 || !b1) return op_bad(who, "null operand or non-positive size");
+    if (d > 1024 || ldy > 1024) return op_bad(who, "rows of at most 1024 columns (d, ldy)");
+    if ((g2 != nullptr) != (y2 != nullptr) || (b2 != nullptr) != (y2 != nullptr)) return op_bad(who, "the second norm takes g2, b2 and y2 together");
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        return launch_splitk_layernorm(slab, S, rows, lds, d, bias, res, ldr, rg_out, rg_in, g1, b1, y, ldy, g2, b2, y2, s);
+    });
+}
+
+extern "C" int hmv_op_add_pe(int32_t device, const float *x, int32_t ldx, int32_t rows, int32_t T, const int32_t *fpos, int32_t d, const float *pe,
+                             float *y, int32_t ldy, void *stream) {
+    static const char *who = "hmv_op_add_pe";
+    if (!x || !pe || !y || rows <= 0 || d <= 0) return op_bad(who, "null operand or non-positive size");
+    if (ldx < d || ldy < d) return op_bad(who, "ldx >= d and ldy >= d");
+    if (!fpos && T <= 0) return op_bad(who, "T must be positive in the uniform form");
+    if (fpos && rows % 21) return op_bad(who, "the ragged form takes whole frames: rows % 21 == 0");
+    return op_run(who, device, stream, [&](hipStream_t s) {
+        if (fpos) return launch_add_pe_views(x, ldx, rows, fpos, d, pe, y, ldy, s);
+        return launch_add_pe(x, ldx, rows, T, d, pe, y, ldy, s);
+    });
+}
+
+extern "C" int hmv_op_cheb_mix(int32_t device, const float *y, int32_t ldy, int32_t B, int32_t co, const float *tk, const float *bias, int32_t leaky,
+                               float *out, int32_t ldo, void *stream) {
+    static const char *who = "hmv_op_cheb_mix";
+    if (!y || !tk || !bias || !out || B <= 0 || co <= 0) return op_bad(who, "null operand or non-positive size");
+    if ((int64_t)3 * co > ldy || ldo < co) return op_bad(who, "ldy >= 3 co and ldo >= co");
+    if ((co + 31) / 32 > 65535) return op_bad(who, "co beyond the launch grid");
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_cheb_mix(y, ldy, B, co, tk, bias, leaky, out, ldo, s); });
+}

@@ -81,7 +81,7 @@ __device__ __forceinline__ void ln_rows2(ff32x4 (&v)[2][FF_VEC], int d, int lane
 #pragma unroll
         for (int e = 0; e < 4; ++e) { s0 += v[0][i][e]; s1 += v[1][i][e]; }
     const float inv_d = 1.f / (float)d;
-    const float m0 = fwave_sum(s0) * inv_d, m1 = fwave_sum(s1) * inv_d;
+    const float m0 = ln_mean(fwave_sum(s0), inv_d), m1 = ln_mean(fwave_sum(s1), inv_d);
     float q0 = 0.f, q1 = 0.f;
 #pragma unroll
     for (int i = 0; i < FF_VEC; ++i)

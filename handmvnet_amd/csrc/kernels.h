@@ -64,6 +64,15 @@ __device__ __forceinline__ void note_range(int *sat, bool over) {
 }
 __device__ __forceinline__ bool out_of_pair_range(float v) { return !(__builtin_fabsf(v) <= 65504.f); }
 
+// The mean of a LayerNorm row (layernorm_kernel, ff_block_kernel's ln_rows2) as ONE fp32 value, rounded before it is subtracted.  Left to the
+// compiler, sum * inv_d is contracted into every `v - mean` (an fma on the exact product): a row of one constant c whose sums are all exact
+// then keeps a residual v - mean of about 2^-24 |c| instead of 0, which rstd = 1 / sqrt(eps) = 316 turns into 1e-4 |gamma| where the
+// reference, and a plain fp32 evaluation, give exactly beta.
+__device__ __forceinline__ float ln_mean(float sum, float inv_d) {
+#pragma clang fp contract(off)
+    return sum * inv_d;
+}
+
 // Implicit-GEMM convolution / plain GEMM on fp32 MFMA.
 //   out[m][n] = act( sum_k A[m][k] * Wt[n][k] + bias[n] + res[m'][n] )
 // A[m][k] is gathered on the fly from an NHWC tensor: m = (img, ho, wo), k = (chunk, r, s, c % 32).

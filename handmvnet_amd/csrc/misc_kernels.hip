@@ -328,6 +328,13 @@ hipError_t launch_maxpool3s2(const float *in, float *out, int N, int H, int W, i
 
 // ------------------------------------------------------------------ soft_argmax_2d (temperature 1000)
 // models/utils.py:35-62.  One wave per (image, joint); logits stay fp32 end to end.
+// The logit is heatmap * temperature, a tensor op of its own in the model: the product is rounded to fp32 BEFORE the maximum is subtracted.
+// Left to the compiler, the product of the second pass is contracted into the subtraction (one fma, the exact product) while the maximum
+// is a rounded product: at |logit| ~ 7500 the two differ by up to 2.4e-4 in the exponent, 1e-4 px in the coordinate of a nearly flat map.
+__device__ __forceinline__ float sam_logit(float raw) {
+#pragma clang fp contract(off)
+    return raw * 1000.0f;
+}
 __global__ void soft_argmax_kernel(const float *__restrict__ hm, int ld, int h, int w, int total, float *coords,
                                    float *crop_img, float image_size, float heatmap_size, float *hm_nchw) {
     const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -338,12 +345,12 @@ __global__ void soft_argmax_kernel(const float *__restrict__ hm, int ld, int h, 
     for (int p = lane; p < hw; p += 64) {
         const float raw = src[(size_t)p * ld];
         if (hm_nchw) hm_nchw[((size_t)n * 21 + j) * hw + p] = raw;
-        mx = fmaxf(mx, raw * 1000.0f);
+        mx = fmaxf(mx, sam_logit(raw));
     }
     mx = wave_max(mx);
     float se = 0.f, sx = 0.f, sy = 0.f;
     for (int p = lane; p < hw; p += 64) {
-        const float e = expf(src[(size_t)p * ld] * 1000.0f - mx);
+        const float e = expf(sam_logit(src[(size_t)p * ld]) - mx);
         const int y = p / w, x = p - y * w;
         se += e;
         sx += e * (float)x;
@@ -390,7 +397,7 @@ __global__ __launch_bounds__(256) void soft_argmax_frame_kernel(const float *__r
                     if (4 * c4 + e < 21) hm_nchw[((size_t)n * 21 + 4 * c4 + e) * hw + p] = raw[u][e];
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], raw[u][e] * 1000.0f);
+            for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], sam_logit(raw[u][e]));
         }
     }
 #pragma unroll
@@ -417,7 +424,7 @@ __global__ __launch_bounds__(256) void soft_argmax_frame_kernel(const float *__r
             const int p = p0 + 32 * u, y = p / w, x = p - y * w;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float ex = act ? expf(raw[u][e] * 1000.0f - mx[e]) : 0.f;
+                const float ex = act ? expf(sam_logit(raw[u][e]) - mx[e]) : 0.f;
                 se[e] += ex;
                 sx[e] += ex * (float)x;
                 sy[e] += ex * (float)y;
@@ -607,7 +614,7 @@ __global__ void layernorm_kernel(const float *__restrict__ x, int ldx, int rows,
         s += v[i];
     }
     const float inv_d = 1.f / (float)d;
-    float mean = wave_sum(s) * inv_d, q = 0.f;
+    float mean = ln_mean(wave_sum(s), inv_d), q = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
@@ -628,7 +635,7 @@ __global__ void layernorm_kernel(const float *__restrict__ x, int ldx, int rows,
         }
     }
     if (!y2) return;
-    mean = wave_sum(s) * inv_d;
+    mean = ln_mean(wave_sum(s), inv_d);
     q = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {

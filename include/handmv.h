@@ -414,6 +414,68 @@ int hmv_op_attention_views(int32_t device, int32_t kind, const float *qkv, const
 int hmv_op_attention_probs(int32_t device, int32_t kind, const float *qkv, const float *probe, int32_t B, int32_t T, int32_t Tq, int32_t koff,
                            int32_t Tk, const int32_t *seg, float *probs, float *view_share, int32_t views, void *stream);
 
+/* ---- the non-GEMM kernels of a forward, each behind the launcher the engine calls (op-level float64 tests) ----
+ * Every operand is a DEVICE pointer.  Each entry checks its arguments (HMV_ERR_ARG with hmv_last_error(NULL) naming the entry, before any
+ * launch), runs one launcher on `stream` and synchronises it.  Nothing is allocated, nothing outlives the call.  `sat` (optional) is a range
+ * word as "Range contract" describes it: set to 1 when a value was clamped to the pair range, left alone otherwise. */
+
+/* Frames x [N][3][H][W] fp32 -> the stem's input rows.  kind 0, one row per pixel: mode 0 fp32 [r g b 0]; 1 fp16 [r g b 0 0 0 0 0];
+ * 2 split pairs [hi: r g b 0 x5 | lo: r g b 0 x5].  kind 1, one row per 2x2 pixel block of the (H + 1) / 2 x (W + 1) / 2 space-to-depth image,
+ * channel order (dy, dx, c), zeros beyond an odd H / W: mode 0 fp32 [12]; 1 fp16 [12 + 4 zeros]; 2 split pairs [hi 16 | lo 16]. */
+int hmv_op_input_layout(int32_t device, int32_t kind, int32_t mode, const float *x, int32_t N, int32_t H, int32_t W, void *out, int32_t *sat,
+                        void *stream);
+
+/* MaxPool2d(3, 2, 1) over NHWC rows in the kernel's own format: mode 0 fp32 [C] (C % 4 == 0); 1 fp16 [C]; 2 split pairs [hi C | lo C]
+ * (C % 8 == 0): the maximum of hi + lo, split again.  out [N][(H - 1) / 2 + 1][(W - 1) / 2 + 1] rows.  Finite inputs: the fp16 pool starts
+ * from -65504, not -inf. */
+int hmv_op_maxpool(int32_t device, int32_t mode, const void *in, int32_t N, int32_t H, int32_t W, int32_t C, void *out, void *stream);
+
+/* soft_argmax_2d at temperature 1000 over channels-last logits hm [N * h * w][ld] (21 joint channels, ld >= 21): coords [N][21][2] in
+ * heat-map pixels, crop_img = coords * image_size / heatmap_size, hm_nchw (or NULL) [N][21][h][w] the logits transposed. */
+int hmv_op_soft_argmax(int32_t device, const float *hm, int32_t ld, int32_t N, int32_t h, int32_t w, float *coords, float *crop_img,
+                       float image_size, float heatmap_size, float *hm_nchw, void *stream);
+
+/* SampleNet's grid_sample(align_corners=True, zeros padding) as gather -> (pointwise conv) -> blend, on maps of at least 2 x 2 pixels.
+ * gather: feat [N][H][W] pixel rows of C elements of elem_bytes (4: fp32 or split pairs, 2: fp16; whole 16-byte chunks) -> out
+ * [(n * 21 + j) * 4 + tap] rows, taps nw, ne, sw, se of coords [N][21][2]; a tap outside the map, or any tap of a non-finite coordinate, is zeros.
+ * blend: s4 [(n * 21 + j) * 4 + tap][lds4] -> tokens[n * 21 + j][col0, col0 + C) = the bilinear blend; no other column is written. */
+int hmv_op_sample_gather(int32_t device, const void *feat, int32_t N, int32_t H, int32_t W, int32_t C, int32_t elem_bytes, const float *coords,
+                         void *out, void *stream);
+int hmv_op_sample_blend(int32_t device, const float *s4, int32_t lds4, int32_t C, int32_t N, int32_t H, int32_t W, const float *coords,
+                        float *tokens, int32_t ldt, int32_t col0, void *stream);
+
+/* The token tail, in place on tokens [N * 21][ldt] whose first fdim columns hold the features: pos2d columns (pos_mask & HMV_POS2D: coords),
+ * crop FoV columns (HMV_POS_CROP: bbox, intr [N][4]), zeros in [d, ldt), d = fdim + 2 + 10 as selected; then raw_copy (or NULL) [N * 21][d] =
+ * the row, + pe (or NULL) [positions][d], and pairs (or NULL) [N * 21][hi ldt | lo ldt] fp16 = the finished row split.  fpos == NULL: frame n
+ * is view n % V, position (n % V) * 21 + j;  fpos device [N]: position fpos[n] + j (the ragged form, no raw_copy). */
+int hmv_op_tokens_finalize(int32_t device, float *tokens, int32_t ldt, int32_t d, int32_t fdim, int32_t N, int32_t V, const int32_t *fpos,
+                           const float *coords, const float *bbox, const float *intr, int32_t pos_mask, const float *pe, float *raw_copy,
+                           void *pairs, int32_t *sat, void *stream);
+
+/* y = LayerNorm(x; g1, b1) over d <= 1024 columns, eps 1e-5, zeros in [d, ldy) (ldy <= 1024); with g2, b2, y2 (all or none):
+ * y2 = LayerNorm(y; g2, b2) as well. */
+int hmv_op_layernorm(int32_t device, const float *x, int32_t ldx, int32_t rows, int32_t d, const float *g1, const float *b1, float *y, int32_t ldy,
+                     const float *g2, const float *b2, float *y2, void *stream);
+
+/* The epilogues of a split-K GEMM over slab [S][rows][lds]: v = slices added in index order + bias + res (or NULL; row r reads res row
+ * (r / rg_out) * rg_in + r % rg_out, rg_out = 0: row r), then act (0 none, 1 ReLU, 2 GELU, 3 LeakyReLU 0.01) -> out[r][0, N);
+ * or (S = 4 only) hmv_op_layernorm of v, bit for bit what the two calls in a row give. */
+int hmv_op_splitk_reduce(int32_t device, const float *slab, int32_t S, int32_t rows, int32_t lds, int32_t N, const float *bias, const float *res,
+                         int32_t ldr, int32_t rg_out, int32_t rg_in, int32_t act, float *out, int32_t ldc, void *stream);
+int hmv_op_splitk_layernorm(int32_t device, const float *slab, int32_t S, int32_t rows, int32_t lds, int32_t d, const float *bias,
+                            const float *res, int32_t ldr, int32_t rg_out, int32_t rg_in, const float *g1, const float *b1, float *y, int32_t ldy,
+                            const float *g2, const float *b2, float *y2, void *stream);
+
+/* y[r][0, d) = x[r][0, d) + pe[pos(r)][0, d), zeros in [d, ldy).  fpos == NULL: pos = r % T;  fpos device [rows / 21]:
+ * pos = fpos[r / 21] + r % 21 (rows % 21 == 0). */
+int hmv_op_add_pe(int32_t device, const float *x, int32_t ldx, int32_t rows, int32_t T, const int32_t *fpos, int32_t d, const float *pe, float *y,
+                  int32_t ldy, void *stream);
+
+/* ChebConv mix: out[b * 21 + i][o] = act(sum_k sum_j tk[k][i][j] * y[b * 21 + j][k * co + o] + bias[o]), k < 3, o < co; leaky: LeakyReLU 0.01.
+ * tk [3][21][21]; ldy >= 3 co, ldo >= co; no column from co on is written. */
+int hmv_op_cheb_mix(int32_t device, const float *y, int32_t ldy, int32_t B, int32_t co, const float *tk, const float *bias, int32_t leaky,
+                    float *out, int32_t ldo, void *stream);
+
 /* Diagnostic micro-benchmark: average milliseconds of `iters` launches of one NHWC conv shape on
  * pseudo-random data.  tile: -1 = the engine's own choice, else 0..7 = 128x32, 128x64, 128x128, 256x128,
  * 128x256, 256x256, 128x128 (k-step 16), 128x256 (k-step 16) (BM x BN); a value without an instantiation returns an error.

@@ -103,3 +103,74 @@ def test_op_attention_argument_errors():
     for args in ((2, 42, 43, 0, 42), (2, 42, 21, 30, 21), (2, 42, 21, 0, 0), (0, 42, 21, 0, 21), (2, 42, 0, 0, 21), (2, 42, 21, -1, 21)):
         assert lib.hmv_op_attention(0, qkv.data_ptr(), *args, out.data_ptr(), None) != 0, args
     assert lib.hmv_op_attention(0, None, 2, 42, 21, 0, 42, out.data_ptr(), None) != 0
+
+
+def test_non_gemm_op_entries_refuse_bad_arguments():
+    """The hmv_op_* entries of the non-GEMM kernels (tests/test_gpu_ops_f64.py): HMV_ERR_ARG with the entry's name in hmv_last_error(NULL),
+    before any launch -- the output keeps its bytes."""
+    from handmvnet_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    a = torch.zeros(1 << 16, device=dev)
+    out = torch.full((1 << 16,), 7.0, device=dev)
+    idx = torch.zeros(64, dtype=torch.int32, device=dev)
+    A, O, I = a.data_ptr(), out.data_ptr(), idx.data_ptr()
+    bad = [
+        ("hmv_op_input_layout", (0, 0, 0, None, 1, 4, 4, O, None, None)),
+        ("hmv_op_input_layout", (0, 2, 0, A, 1, 4, 4, O, None, None)),
+        ("hmv_op_input_layout", (0, 0, 3, A, 1, 4, 4, O, None, None)),
+        ("hmv_op_input_layout", (0, 1, 0, A, 1, 0, 4, O, None, None)),
+        ("hmv_op_maxpool", (0, 3, A, 1, 4, 4, 8, O, None)),
+        ("hmv_op_maxpool", (0, 0, A, 1, 4, 4, 6, O, None)),
+        ("hmv_op_maxpool", (0, 1, A, 1, 4, 4, 12, O, None)),
+        ("hmv_op_maxpool", (0, 0, A, 1, 4, 4, 8, None, None)),
+        ("hmv_op_soft_argmax", (0, A, 20, 1, 4, 4, O, O, 64.0, 16.0, None, None)),
+        ("hmv_op_soft_argmax", (0, A, 32, 1, 4, 4, O, None, 64.0, 16.0, None, None)),
+        ("hmv_op_soft_argmax", (0, A, 32, 1, 0, 4, O, O, 64.0, 16.0, None, None)),
+        ("hmv_op_soft_argmax", (0, A, 32, 1, 4, 4, O, O, 64.0, 0.0, None, None)),
+        ("hmv_op_sample_gather", (0, A, 1, 1, 4, 16, 4, A, O, None)),
+        ("hmv_op_sample_gather", (0, A, 1, 4, 4, 16, 3, A, O, None)),
+        ("hmv_op_sample_gather", (0, A, 1, 4, 4, 4, 2, A, O, None)),
+        ("hmv_op_sample_gather", (0, A, 1, 4, 4, 16, 4, None, O, None)),
+        ("hmv_op_sample_blend", (0, A, 8, 16, 1, 4, 4, A, O, 32, 0, None)),
+        ("hmv_op_sample_blend", (0, A, 16, 16, 1, 4, 4, A, O, 32, 17, None)),
+        ("hmv_op_sample_blend", (0, A, 16, 16, 1, 4, 4, A, O, 32, -1, None)),
+        ("hmv_op_sample_blend", (0, A, 16, 16, 1, 4, 1, A, O, 32, 0, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 44, 32, 1, 1, None, A, A, A, 4, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 43, 32, 1, 1, None, A, A, A, 3, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 40, 44, 32, 1, 1, None, A, A, A, 3, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 44, 32, 1, 1, None, A, None, A, 3, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 34, 32, 1, 1, None, None, A, A, 1, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 44, 32, 1, 0, None, A, A, A, 3, None, None, None, None, None)),
+        ("hmv_op_tokens_finalize", (0, O, 48, 44, 32, 1, 1, I, A, A, A, 3, None, A, None, None, None)),
+        ("hmv_op_layernorm", (0, A, 44, 2, 44, A, A, O, 40, None, None, None, None)),
+        ("hmv_op_layernorm", (0, A, 40, 2, 44, A, A, O, 44, None, None, None, None)),
+        ("hmv_op_layernorm", (0, A, 1028, 2, 1028, A, A, O, 1028, None, None, None, None)),
+        ("hmv_op_layernorm", (0, A, 44, 2, 44, A, A, O, 44, A, A, None, None)),
+        ("hmv_op_layernorm", (0, A, 44, 2, 44, A, None, O, 44, None, None, None, None)),
+        ("hmv_op_splitk_reduce", (0, A, 0, 5, 44, 44, A, None, 0, 0, 0, 0, O, 44, None)),
+        ("hmv_op_splitk_reduce", (0, A, 4, 5, 40, 44, A, None, 0, 0, 0, 0, O, 44, None)),
+        ("hmv_op_splitk_reduce", (0, A, 4, 5, 44, 44, A, A, 40, 0, 0, 0, O, 44, None)),
+        ("hmv_op_splitk_reduce", (0, A, 4, 5, 44, 44, A, None, 0, 0, 0, 4, O, 44, None)),
+        ("hmv_op_splitk_reduce", (0, A, 4, 5, 44, 44, A, A, 44, 21, 20, 0, O, 44, None)),
+        ("hmv_op_splitk_reduce", (0, A, 4, 5, 44, 44, None, None, 0, 0, 0, 0, O, 44, None)),
+        ("hmv_op_splitk_layernorm", (0, A, 2, 5, 44, 44, A, None, 0, 0, 0, A, A, O, 44, None, None, None, None)),
+        ("hmv_op_splitk_layernorm", (0, A, 4, 5, 1028, 1028, A, None, 0, 0, 0, A, A, O, 1028, None, None, None, None)),
+        ("hmv_op_splitk_layernorm", (0, A, 4, 5, 44, 44, A, None, 0, 0, 0, None, A, O, 44, None, None, None, None)),
+        ("hmv_op_add_pe", (0, A, 44, 42, 0, None, 44, A, O, 48, None)),
+        ("hmv_op_add_pe", (0, A, 44, 40, 42, I, 44, A, O, 48, None)),
+        ("hmv_op_add_pe", (0, A, 44, 42, 42, None, 44, A, O, 40, None)),
+        ("hmv_op_add_pe", (0, A, 44, 42, 42, None, 44, None, O, 48, None)),
+        ("hmv_op_cheb_mix", (0, A, 47, 1, 16, A, A, 0, O, 16, None)),
+        ("hmv_op_cheb_mix", (0, A, 48, 1, 16, A, A, 0, O, 12, None)),
+        ("hmv_op_cheb_mix", (0, A, 48, 0, 16, A, A, 0, O, 16, None)),
+        ("hmv_op_cheb_mix", (0, A, 48, 1, 16, None, A, 0, O, 16, None)),
+    ]
+    for name, args in bad:
+        assert getattr(lib, name)(*args) == ARG, (name, args)
+        assert name.encode() in lib.hmv_last_error(None), (name, args, lib.hmv_last_error(None))
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+    # ... and the smallest good call of one of them still runs
+    assert lib.hmv_op_add_pe(0, A, 44, 42, 42, None, 44, A, O, 48, None) == OK
+    assert not out[:42 * 48].any() and bool((out[42 * 48:] == 7.0).all())

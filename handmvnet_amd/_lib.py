@@ -23,7 +23,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate",
            "hmv_op_heatmap_peaks", "hmv_op_confidence_select", "hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax",
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
-           "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix"]
+           "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -70,6 +70,14 @@ class HmvEvalBreakdownArgs(ctypes.Structure):
                 ("gt_joints_2d", ctypes.c_void_p), ("joints_mask", ctypes.c_void_p), ("view_present", ctypes.c_void_p),
                 ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t), ("records", ctypes.c_void_p),
                 ("record_capacity", ctypes.c_int64), ("record_base", ctypes.c_int64)]
+
+
+class HmvEvalAbsoluteArgs(ctypes.Structure):
+    """hmv_eval_absolute_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("v_checked", ctypes.c_int32),
+                ("pred_joints_cam", ctypes.c_void_p), ("joints_tri", ctypes.c_void_p), ("tri_status", ctypes.c_void_p),
+                ("gt_joints_cam", ctypes.c_void_p), ("gt_root", ctypes.c_void_p), ("reproj_err", ctypes.c_void_p),
+                ("inliers", ctypes.c_void_p), ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t)]
 
 
 class HmvSeqEvalArgs(ctypes.Structure):
@@ -228,6 +236,10 @@ def load() -> ctypes.CDLL:
     lib.hmv_eval_record_floats.restype = ctypes.c_size_t
     lib.hmv_eval_breakdown_add.argtypes = [ci, ctypes.POINTER(HmvEvalBreakdownArgs), vp]
     lib.hmv_eval_breakdown_add.restype = ctypes.c_int
+    lib.hmv_eval_absolute_doubles.argtypes = [ci]
+    lib.hmv_eval_absolute_doubles.restype = ctypes.c_size_t
+    lib.hmv_eval_absolute_add.argtypes = [ci, ctypes.POINTER(HmvEvalAbsoluteArgs), vp]
+    lib.hmv_eval_absolute_add.restype = ctypes.c_int
     lib.hmv_forward_frames_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, ci, ci, fp, fp, ctypes.POINTER(ctypes.c_float),
                                              ctypes.POINTER(ctypes.c_float), fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames_views.restype = ctypes.c_int

@@ -27,6 +27,14 @@ up to ``n`` fp32 record rows, one per sample in feed order.  The pooled state is
 value on ragged steps is the plain mean over the samples that had the camera -- not the pooled value's mean over samples of
 per-sample means.  Records stay on their rank.
 
+Absolute position.  ``EpochEvaluator(model, mode, absolute=True)`` runs ``forward_absolute`` per step and one more accumulation
+launch (``hmv_eval_absolute_add``) into a third slice of the same tensor: the world MPJPE with the triangulated root
+(``{mode}_w_mpjpe``), the root's error, plain triangulation against the labels per joint, the status of every joint, the
+reprojection error per camera and the inlier histogram (``finish_absolute``).  Its means are over the LOCATED samples, those whose
+root joint was triangulated; ``lost`` counts the others.  With no sample lost, ``{mode}_w_mpjpe`` and ``{mode}_root_err`` are the
+epoch value above of what ``test_step`` logs with ``absolute_root = "triangulate"``.  Labels must be in the frame
+``forward_absolute`` reports in: view 0, or a ragged sample's first present view.
+
 Lightning is not a dependency of this package, so the ``_epoch`` / ``_step`` suffixes its loggers add to a key logged with both
 ``on_step`` and ``on_epoch`` cannot be pinned and are not reproduced: the keys are the names the reference passes to ``self.log``.
 """
@@ -46,6 +54,7 @@ STEPS = 20       # thresholds of the PCK curve (handmvnet.py:359-363)
 _SCALARS = 14    # state[0 .. 14): counts and sums, then the steps + 1 histogram bins (include/handmv.h: "State layout")
 NJ = 21
 _HEADER = 4      # breakdown state[0 .. 4): samples, steps added, V, S (include/handmv.h: "evaluation breakdown")
+_ABS_FIXED = 155 # absolute state[0 .. 155): 8 header slots, W, T, TN, S; then R[V], RN[V], H[V + 1] (include/handmv.h: "absolute evaluation")
 RECORD_KEYS = ("mpjpe", "pa_mpjpe", "mpjpe2d", "views", "mpjpe2d_per_camera")
 
 
@@ -156,6 +165,53 @@ def finish_breakdown(state, thr_min: float, thr_max: float, steps: int, mode: st
             "camera_samples": [int(n) for n in cn], "visible_joints": cv.astype(np.int64).tolist()}
 
 
+def absolute_doubles(views: int) -> int:
+    """hmv_eval_absolute_doubles on the host: 8 header slots, W, T, TN [21] each, S [21][4], R[V], RN[V], H[V + 1]."""
+    return _ABS_FIXED + 1 + 3 * views
+
+
+def finish_absolute(state, mode: str) -> dict:
+    """The absolute numbers from an absolute state on the host (include/handmv.h: "absolute evaluation"); V comes from its length.
+    The means are over the LOCATED samples -- those whose root joint was triangulated.  Millimetres for {mode}_w_mpjpe (what
+    test_step logs under that name with absolute_root = "triangulate", pooled: sum of B x the step's value / sum of B when no sample
+    is lost), {mode}_root_err, {mode}_w_mpjpe_per_joint [21], and for plain triangulation against the labels {mode}_tri_mpjpe and
+    {mode}_tri_mpjpe_per_joint [21] (over the joints with status 0 and a finite point); {mode}_tri_status_counts [21][4];
+    {mode}_tri_reproj_per_camera [V] and {mode}_tri_reproj in frame pixels; {mode}_tri_inlier_hist [V + 1]; located, lost.  A ratio
+    whose count is 0 is None.  Raises ValueError for an empty epoch, a length that is no state's, or a [2] that names another V."""
+    s = np.asarray(state, dtype=np.float64).reshape(-1)
+    V, rest = divmod(s.size - _ABS_FIXED - 1, 3)
+    if V < 1 or V > 16 or rest:
+        raise ValueError(f"{s.size} elements are not an absolute state (156 + 3 V, V in 1 .. 16)")
+    if not s[0] > 0:
+        raise ValueError("empty epoch: no step was added")
+    if s[2] != V:
+        raise ValueError(f"this absolute state was accumulated with V = {s[2]:g}, not V = {V}")
+    w, t, tn = s[8:8 + NJ], s[8 + NJ:8 + 2 * NJ], s[8 + 2 * NJ:8 + 3 * NJ]
+    status = s[8 + 3 * NJ:_ABS_FIXED].reshape(NJ, 4)
+    r, rn, hist = s[_ABS_FIXED:_ABS_FIXED + V], s[_ABS_FIXED + V:_ABS_FIXED + 2 * V], s[_ABS_FIXED + 2 * V:]
+
+    def over(total, count, scale=1.0):
+        return float(total / count * scale) if count > 0 else None
+
+    return {f"{mode}_w_mpjpe": over(s[4], s[3] * NJ, 1000), f"{mode}_root_err": over(s[5], s[3], 1000),
+            f"{mode}_w_mpjpe_per_joint": [over(w[j], s[3], 1000) for j in range(NJ)],
+            f"{mode}_tri_mpjpe": over(t.sum(), tn.sum(), 1000), f"{mode}_tri_mpjpe_per_joint": [over(t[j], tn[j], 1000) for j in range(NJ)],
+            f"{mode}_tri_status_counts": status.astype(np.int64).tolist(),
+            f"{mode}_tri_reproj_per_camera": [over(r[v], rn[v]) for v in range(V)], f"{mode}_tri_reproj": over(r.sum(), rn.sum()),
+            f"{mode}_tri_inlier_hist": hist.astype(np.int64).tolist(), "located": int(s[3]), "lost": int(s[0] - s[3])}
+
+
+def _absolute_options(absolute) -> Optional[dict]:
+    """None: the absolute path is off.  A dict of forward_absolute's keywords otherwise; an empty one stands for True."""
+    if absolute is False:
+        return None
+    if absolute is True:
+        return {}
+    if isinstance(absolute, dict) and set(absolute) <= {"ransac", "refit", "confidence"}:
+        return dict(absolute)
+    raise ValueError("absolute must be a bool or a dict with any of ransac, refit, confidence (forward_absolute's keywords)")
+
+
 def worst(records: dict, key: str = "mpjpe", k: int = 10) -> list:
     """The indices (feed order) of the k samples with the largest records[key], worst first; equal values in feed order, NaN last."""
     values = np.asarray(records[key], dtype=np.float64)
@@ -178,10 +234,20 @@ class EpochEvaluator:
     breakdown=True: every step also runs hmv_eval_breakdown_add, and compute() adds finish_breakdown's keys.  records=n > 0: that
     launch also fills one record row per sample, up to n on this rank, read with records(); the launch runs for them even with
     breakdown=False.  Every step must then have the V of the first (ValueError otherwise, before anything is launched), and the
-    two states are the two ends of ONE tensor, so that reduce() stays one collective."""
+    two states are the two ends of ONE tensor, so that reduce() stays one collective.
 
-    def __init__(self, model, mode: str = "test", breakdown: bool = False, records: int = 0):
+    absolute=True, or a dict with any of forward_absolute's ransac / refit / confidence (True: confidence=model.absolute_confidence,
+    read at every step): step() runs forward_absolute(..., details=True) in place of forward / forward_views, add() runs
+    hmv_eval_absolute_add behind what it runs today, and compute() adds finish_absolute's keys.  The absolute state is one more
+    slice of that ONE tensor.  Every batch needs inputs["root_joint"] and cam_params["extrinsic"], with the labels in the frame
+    forward_absolute reports in: view 0, or a ragged sample's first present view (the convention of test_step's w_mpjpe).  The
+    absolute means are over the located samples; see finish_absolute.  Every step must have the V of the first (ValueError
+    otherwise, before anything is launched); having compared here, add() passes v_checked, so that entry reads nothing back either."""
+
+    def __init__(self, model, mode: str = "test", breakdown: bool = False, records: int = 0, absolute=False):
         self.model, self.mode = model, mode
+        self._absolute = _absolute_options(absolute)                     # None: off; forward_absolute's keywords otherwise
+        self.absolute_state: Optional[torch.Tensor] = None
         self.thr_min, self.thr_max = float(model.auc_thresh[0]), float(model.auc_thresh[1])
         self.state_doubles = int(_lib.load().hmv_eval_state_doubles(STEPS))
         self.state: Optional[torch.Tensor] = None
@@ -197,14 +263,20 @@ class EpochEvaluator:
 
     def _state_on(self, dev: torch.device, views: Optional[int] = None) -> torch.Tensor:
         if self.state is None:
-            if not self._detail:
+            if not self._detail and self._absolute is None:
                 self.state = torch.zeros(self.state_doubles, device=dev, dtype=torch.float64)
             else:
                 if views is None:
-                    raise ValueError("the breakdown state is sized by V: a rank that saw no batch needs a model with num_views")
+                    raise ValueError("the breakdown and absolute states are sized by V: a rank that saw no batch needs a model with num_views")
                 self.views = int(views)
-                self._both = torch.zeros(self.state_doubles + breakdown_doubles(self.views, STEPS), device=dev, dtype=torch.float64)
-                self.state, self.breakdown_state = self._both[:self.state_doubles], self._both[self.state_doubles:]
+                mid = self.state_doubles + (breakdown_doubles(self.views, STEPS) if self._detail else 0)
+                end = mid + (absolute_doubles(self.views) if self._absolute is not None else 0)
+                self._both = torch.zeros(end, device=dev, dtype=torch.float64)   # pooled | breakdown | absolute
+                self.state = self._both[:self.state_doubles]
+                if self._detail:
+                    self.breakdown_state = self._both[self.state_doubles:mid]
+                if self._absolute is not None:
+                    self.absolute_state = self._both[mid:]
                 if self.record_capacity:
                     self.record_table = torch.full((self.record_capacity, 4 + self.views), float("nan"), device=dev)
         elif self.state.device != dev:
@@ -214,7 +286,7 @@ class EpochEvaluator:
     def _check_detail(self, B: int, V: int) -> None:
         """What the breakdown launch would refuse or cannot see, in front of every launch of the step."""
         if self.views is not None and V != self.views:
-            raise ValueError(f"this epoch's breakdown was begun with {self.views} views, the step has {V}")
+            raise ValueError(f"this epoch's breakdown / absolute state was begun with {self.views} views, the step has {V}")
         if self.record_capacity and self.record_rows + B > self.record_capacity:
             raise ValueError(f"{self.record_rows} + {B} samples do not fit the {self.record_capacity} record rows of this evaluator")
 
@@ -222,7 +294,14 @@ class EpochEvaluator:
         """One step from the forward's `out` and the labels as _eval_step passes them (joints_cam / root_joint in metres): the loss
         when the batch carries loss labels, then one hmv_eval_add on the current stream.  Returns nothing; nothing reaches the host.
         view_mask (bool [B, V], True = present): `out` is forward_views' and the step is a ragged one -- the ragged loss and
-        hmv_eval_add_views; rows of absent views are not read."""
+        hmv_eval_add_views; rows of absent views are not read.
+        With absolute on, `out` is forward_absolute's (details=True adds the reprojection and inlier tables; without them R, RN and H
+        stay as they are) and inputs["root_joint"] [B, 1, 3] is read: one hmv_eval_absolute_add behind the others."""
+        if self._absolute is not None:   # before anything is launched
+            if "joints_tri" not in out or "tri_status" not in out:
+                raise ValueError("absolute evaluation needs forward_absolute's output: `out` has no joints_tri / tri_status")
+            if "root_joint" not in inputs:
+                raise ValueError("absolute evaluation needs inputs['root_joint'], the label's root in the reference camera's frame")
         pc = _device_f32("out['joints_cam']", out["joints_cam"])
         dev = pc.device
         p2 = _device_f32("out['joints_crop_img']", out["joints_crop_img"], dev)
@@ -234,9 +313,28 @@ class EpochEvaluator:
         if p2.dim() != 4 or p2.shape[0] != B or tuple(p2.shape[2:]) != (21, 2) or g2.shape != p2.shape:
             raise ValueError(f"joints_crop_img must be [{B}, V, 21, 2] in the output and in the labels")
         V = p2.shape[1]
-        if self._detail:
+        if self._detail or self._absolute is not None:
             self._check_detail(B, V)
         keep = [pc, p2, gc, g2]
+        if self._absolute is not None:
+            tri = _device_f32("out['joints_tri']", out["joints_tri"], dev)
+            status = out["tri_status"].detach().to(dev).to(torch.int32).contiguous()
+            root = _device_f32("inputs['root_joint']", inputs["root_joint"], dev)
+            if tri.shape != pc.shape or tuple(status.shape) != (B, 21) or root.numel() != B * 3:
+                raise ValueError(f"absolute evaluation needs joints_tri [{B}, 21, 3], tri_status [{B}, 21] and root_joint [{B}, 1, 3]")
+            if not 1 <= V <= 16:
+                raise ValueError(f"absolute evaluation takes 1 .. 16 views, the step has {V}")
+            reproj = out.get("tri_reproj")
+            if reproj is not None:
+                reproj = _device_f32("out['tri_reproj']", reproj, dev)
+                if tuple(reproj.shape) != (B, V, 21):
+                    raise ValueError(f"tri_reproj must be [{B}, {V}, 21]")
+            inl = out.get("tri_inliers")
+            if inl is not None:
+                inl = inl.detach().to(dev).to(torch.int32).contiguous()
+                if tuple(inl.shape) != (B, 21):
+                    raise ValueError(f"tri_inliers must be [{B}, 21]")
+            keep += [tri, status, root, reproj, inl]
         a = _lib.HmvEvalArgs()
         a.struct_size = ctypes.sizeof(_lib.HmvEvalArgs)
         a.B, a.V, a.steps, a.thr_min, a.thr_max = B, V, STEPS, self.thr_min, self.thr_max
@@ -277,6 +375,17 @@ class EpochEvaluator:
                     d.records, d.record_capacity, d.record_base = self.record_table.data_ptr(), self.record_capacity, self.record_rows
                 _lib.check(_lib.load().hmv_eval_breakdown_add(_index(dev), ctypes.byref(d), stream))
                 self.record_rows += B
+            if self._absolute is not None:
+                w = _lib.HmvEvalAbsoluteArgs()
+                w.struct_size = ctypes.sizeof(_lib.HmvEvalAbsoluteArgs)
+                w.B, w.V = B, V
+                w.v_checked = 1                  # _check_detail has held the step to the epoch's V: no readback, nothing waits
+                w.pred_joints_cam, w.gt_joints_cam = a.pred_joints_cam, a.gt_joints_cam
+                w.joints_tri, w.tri_status, w.gt_root = tri.data_ptr(), status.data_ptr(), root.data_ptr()
+                w.reproj_err = None if reproj is None else reproj.data_ptr()
+                w.inliers = None if inl is None else inl.data_ptr()
+                w.state, w.state_doubles = self.absolute_state.data_ptr(), self.absolute_state.numel()
+                _lib.check(_lib.load().hmv_eval_absolute_add(_index(dev), ctypes.byref(w), stream))
         del keep   # allocated on the stream the kernel runs on: the caching allocator reuses them in stream order
 
     def step(self, batch: dict) -> dict:
@@ -284,7 +393,13 @@ class EpochEvaluator:
         inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE.  Returns the forward's output dictionary."""
         inputs = batch["data"]
         view_mask = batch.get("view_mask")
-        if view_mask is None:
+        if self._absolute is not None:
+            cam_params = batch.get("cam_params")
+            if "root_joint" not in inputs or cam_params is None or "extrinsic" not in cam_params:   # before anything is launched
+                raise ValueError("absolute evaluation needs inputs['root_joint'] and cam_params['extrinsic'] in every batch")
+            options = self._absolute or {"confidence": getattr(self.model, "absolute_confidence", None)}
+            out = self.model.forward_absolute(inputs["rgb"], inputs["bboxes"], cam_params, view_mask=view_mask, details=True, **options)
+        elif view_mask is None:
             out = self.model.forward(inputs["rgb"], inputs["bboxes"], batch["cam_params"])
         else:   # raises ValueError for a sample without a present view, before anything is launched
             out = self.model.forward_views(inputs["rgb"], view_mask, inputs["bboxes"], batch["cam_params"])
@@ -302,26 +417,34 @@ class EpochEvaluator:
         takes part with a zero state."""
         if self.state is None:
             self._state_on(torch.device("cuda", torch.cuda.current_device()), getattr(self.model, "num_views", None))
-        if not self._detail:
+        if self._both is None:
             reduce_state(self.state, group)
             return
-        reduce_state(self._both, group)          # both states in one collective; records stay on their rank
-        self.breakdown_state[2].fill_(float(self.views))   # V and S are not sums (include/handmv.h)
-        self.breakdown_state[3].fill_(float(STEPS))
+        reduce_state(self._both, group)          # every state in one collective; records stay on their rank
+        if self._detail:
+            self.breakdown_state[2].fill_(float(self.views))   # V and S are not sums (include/handmv.h)
+            self.breakdown_state[3].fill_(float(STEPS))
+        if self._absolute is not None:
+            self.absolute_state[2].fill_(float(self.views))
 
     def compute(self) -> dict:
         """ONE device->host copy of the state, the rest on the host (finish_state).  {mode}_mpjpe / {mode}_pa_mpjpe in millimetres,
         {mode}_mpjpe2d in crop pixels, {mode}_pck_j (list), {mode}_auc_j, {mode}_norm_auc_j, thresholds (list), {mode}/heatmap_loss
         ... {mode}/p2d_loss, {mode}/root_3d_loss, {mode}/loss (None when no step carried a loss), samples, steps.
+        With breakdown=True also finish_breakdown's keys, with absolute on also finish_absolute's, from the same copy.
         Raises ValueError for an empty epoch."""
-        if not self.breakdown:
+        if not self.breakdown and self._absolute is None:
             host = np.zeros(self.state_doubles) if self.state is None else self.state.cpu().numpy()
             return finish_state(host, self.thr_min, self.thr_max, STEPS, self.mode)
         if self.state is None:
             raise ValueError("empty epoch: no step was added")
-        host = self._both.cpu().numpy()           # still ONE copy: the two states are one tensor
+        host = self._both.cpu().numpy()           # still ONE copy: the states are one tensor
         out = finish_state(host[:self.state_doubles], self.thr_min, self.thr_max, STEPS, self.mode)
-        out.update(finish_breakdown(host[self.state_doubles:], self.thr_min, self.thr_max, STEPS, self.mode))
+        if self.breakdown:
+            mid = self.state_doubles + breakdown_doubles(self.views, STEPS)
+            out.update(finish_breakdown(host[self.state_doubles:mid], self.thr_min, self.thr_max, STEPS, self.mode))
+        if self._absolute is not None:
+            out.update(finish_absolute(host[host.size - absolute_doubles(self.views):], self.mode))
         return out
 
     def records(self) -> dict:

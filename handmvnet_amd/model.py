@@ -425,7 +425,7 @@ class HandMvNet(torch.nn.Module):
                    order_deviation=res["deviation"])
         return out
 
-    def forward_absolute(self, x, bbox, cam_params, view_mask=None, ransac=None, refit=True, confidence=None):
+    def forward_absolute(self, x, bbox, cam_params, view_mask=None, ransac=None, refit=True, confidence=None, details=False):
         """forward() -- or forward_views() when `view_mask` is given -- plus where the hand IS: one triangulation launch on the same
         stream (handmvnet_amd/triangulation.py, hmv_op_triangulate) fed the call's own `joints_crop_img` and `bbox`; the crop-to-frame
         mapping happens inside that launch.  Needs cam_params["intrinsic"] [b, v, 4] and cam_params["extrinsic"] [b, v, 4, 4], the
@@ -448,7 +448,11 @@ class HandMvNet(torch.nn.Module):
                                      It is made from `index` by five elementwise torch ops on [b, v, 21] device tensors (remainder, floor
                                      division, stack, multiply, divide) beside the two library launches: nothing is read back
           tri_level   [b, 21]        the threshold that decided each joint
-          tri_views   [b, 21]        int32, the views kept; below two, tri_status is 2 and the joint NaN"""
+          tri_views   [b, 21]        int32, the views kept; below two, tri_status is 2 and the joint NaN
+        details=True adds two outputs the same triangulation launch writes (no further launch, the other outputs keep their bits):
+          tri_reproj  [b, v, 21]     fp32, each triangulated joint's reprojection error in every view in frame pixels; NaN for a view
+                                     that is not usable
+          tri_inliers [b, 21]        int32, the RANSAC winner's inlier count; without `ransac` the number of usable views"""
         from .triangulation import candidate_table, triangulate
         if cam_params is None or "intrinsic" not in cam_params or "extrinsic" not in cam_params:
             raise ValueError("forward_absolute needs cam_params['intrinsic'] and cam_params['extrinsic']")
@@ -481,7 +485,7 @@ class HandMvNet(torch.nn.Module):
             present = torch.from_numpy(mask.astype(np.uint8)).to(x.device)
             frame_cam = mask.argmax(axis=1).astype(np.int32)   # the first present view of each sample
         crop = out["joints_crop_img"]
-        extra = {}
+        extra = dict(return_details=True) if details else {}
         if gate is not None:   # the peaks launch on the forward's own heat map; the select launch runs inside triangulate()
             hm = out["heatmap"]
             conf, index, _ = heatmap_peaks(hm.reshape(b, v, 21, hm.shape[-2], hm.shape[-1]))
@@ -489,9 +493,11 @@ class HandMvNet(torch.nn.Module):
         res = triangulate(crop, cam_params["intrinsic"].to(crop.device).reshape(b, v, 4), cam_params["extrinsic"],
                           bbox=bbox.to(crop.device).reshape(b, v, 4), image_size=self.data_params["image_size"], present=present,
                           subsets=table, threshold=threshold, refit=bool(refit) and table is not None, frame_cam=frame_cam, **extra)
-        tri, status = (res["points3d"], res["status"]) if gate is not None else res
+        tri, status = (res["points3d"], res["status"]) if isinstance(res, dict) else res
         root = tri[:, :1]
         out.update(joints_tri=tri, root_joint=root, joints_abs=out["joints_cam"] + root, tri_status=status)
+        if details:
+            out.update(tri_reproj=res["reproj_err"], tri_inliers=res["inliers"])
         if gate is not None:
             wmap = int(out["heatmap"].shape[-1])
             xy = torch.stack([index % wmap, torch.div(index, wmap, rounding_mode="floor")], dim=-1).float()
@@ -697,7 +703,7 @@ class HandMvNet(torch.nn.Module):
         """handmvnet.py:493-517: metric keys carry the "test_" prefix."""
         return self._eval_step(batch, "test")
 
-    def evaluate(self, batches, mode: str = "test", group=None, breakdown: bool = False, records: int = 0) -> dict:
+    def evaluate(self, batches, mode: str = "test", group=None, breakdown: bool = False, records: int = 0, absolute=False) -> dict:
         """What trainer.test(model, dm) / trainer.validate hand back (eval.py): the epoch's numbers over every batch of `batches`.
         Each step enqueues forward, loss and one accumulation launch and copies nothing to the host; one all-reduce combines the ranks
         when a process group is initialised; one readback ends the epoch.  Every value is sum(B x step value) / sum(B) over steps and
@@ -707,9 +713,14 @@ class HandMvNet(torch.nn.Module):
         ragged loss and the ragged accumulation, at the cost of its present frames; ragged and uniform batches may be mixed.
         breakdown=True adds the per-joint and per-camera tables (evaluation.finish_breakdown's keys) at one more launch per step,
         reduced in the same collective; records=n > 0 adds "records": one row per sample of THIS rank in feed order, at most n
-        (EpochEvaluator.records; evaluation.worst picks the worst of them).  With the defaults the result is what it always was."""
+        (EpochEvaluator.records; evaluation.worst picks the worst of them).
+        absolute=True (or a dict with any of ransac, refit, confidence for forward_absolute; True = confidence=absolute_confidence):
+        every step runs forward_absolute and one more accumulation launch (hmv_eval_absolute_add), and the result gains
+        evaluation.finish_absolute's keys -- {mode}_w_mpjpe, {mode}_root_err, the triangulation's own error, its status counts, the
+        reprojection error per camera and the inlier histogram; every batch then needs inputs["root_joint"] and
+        cam_params["extrinsic"], in the frame forward_absolute reports in.  With the defaults the result is what it always was."""
         from .evaluation import EpochEvaluator
-        ev = EpochEvaluator(self, mode, breakdown=breakdown, records=records)
+        ev = EpochEvaluator(self, mode, breakdown=breakdown, records=records, absolute=absolute)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():

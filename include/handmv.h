@@ -859,6 +859,70 @@ size_t hmv_eval_record_floats(int32_t V);
  * record_base < 0 or a last sample that would land at record_base + B > record_capacity. */
 int hmv_eval_breakdown_add(int32_t device, const hmv_eval_breakdown_args *args, void *stream);
 
+/* ---- absolute evaluation (where the hand is, over a whole split: the world MPJPE, and what the triangulation says about the rig) ----
+ * hmv_eval_absolute_add adds one step of HandMvNet.forward_absolute -- the root-relative prediction, the triangulated joints with
+ * their status, and optionally the triangulation launch's reprojection errors and inlier counts (hmv_op_triangulate's points3d with a
+ * frame_cam, status, reproj_err, inliers) -- into a THIRD caller-owned fp64 state.  The pooled and the breakdown state are untouched by
+ * it.  The labels must be in the frame joints_tri is in: each sample's reference camera, view 0 or a ragged sample's first present
+ * view.
+ *
+ * A sample is LOCATED when tri_status[b][0] == 0 and the three coordinates of joints_tri[b][0] are finite; every other sample is
+ * LOST and adds to [0] and to S, TN, R, H only.  The world distance of (b, j) is
+ *     | (pred_joints_cam[b][j] + joints_tri[b][0])  -  (gt_joints_cam[b][j] + gt_root[b]) |
+ * with both sums rounded to fp32 (what the evaluation step computes for {mode}_w_mpjpe, handmvnet.py:412-413) and the fp32 joint
+ * distance of the other evaluation entries.
+ *
+ * State layout: hmv_eval_absolute_doubles(V) = 156 + 3 V doubles, additive element by element except [2]:
+ *   [0]   samples, sum of B            [1]   steps added
+ *   [2]   V: WRITTEN by every add, not summed.  An add whose V differs from a non-zero [2] is refused; whoever sums two states
+ *         (an all-reduce) refills it
+ *   [3]   located samples
+ *   [4]   sum over the located samples and their 21 joints of the world distance (the units of joints_cam: metres)
+ *   [5]   sum over the located samples of | joints_tri[b][0] - gt_root[b] |
+ *   [6], [7]   reserved, left as they are
+ *   W   [21]      at [8]:   per joint, the world distance summed over the located samples; [4] is the sum of this step's 21 values
+ *   T   [21]      at [29]:  per joint, sum of | joints_tri[b][j] - (gt_joints_cam[b][j] + gt_root[b]) | over the samples with
+ *                           tri_status[b][j] == 0 and a finite point: plain triangulation against the labels
+ *   TN  [21]      at [50]:  the count for T
+ *   S   [21][4]   at [71]:  per joint, the samples whose tri_status[b][j] is 0, 1, 2, 3; a value outside 0 .. 3 counts as 3
+ *   R   [V]       at [155]:       per camera, sum of the finite reproj_err[b][v][j] over the (b, j) with status 0 (pixels)
+ *   RN  [V]       at [155 + V]:   the count for R.  R and RN are untouched when reproj_err is NULL
+ *   H   [V + 1]   at [155 + 2 V]: the (b, j) with status 0 whose inliers value, clamped to 0 .. V, is k.  Untouched when inliers is NULL
+ * Counts are integers held in doubles.  A zero-filled buffer is an empty epoch.
+ *
+ * One launch of 2 to 4 workgroups, each the only writer of its slice and each element read-modify-written by one lane: fp32
+ * distances, fp64 sums in a fixed order, no floating-point atomics -- two identical epochs give identical bits.  The loops stride over
+ * the B * 21 rows and the B * V * 21 reprojection entries.  The kernel reports and repairs nothing: a non-finite label or prediction of
+ * a located sample makes its distance non-finite, and that distance goes into [4], [5], W or T as it is.
+ * The state belongs to one stream at a time.  To compare V with [2] the entry reads those eight bytes back behind the stream's
+ * earlier work before it launches: unlike hmv_eval_add it waits for the stream once per call.  A caller that keeps the epoch's V on
+ * the host and has compared there sets v_checked: nothing is read back and nothing waits.  The kernel compares as well, in either
+ * case: on a state begun with another V it writes nothing, so a wrong promise loses the step and not the epoch. */
+typedef struct hmv_eval_absolute_args {
+    int32_t struct_size;            /* sizeof(hmv_eval_absolute_args), ABI guard */
+    int32_t B, V;                   /* samples; views, 1 .. 16 as for hmv_op_triangulate */
+    int32_t v_checked;              /* 0: the entry compares V with state[2] (one wait for the stream); non-zero: the caller has */
+    const float *pred_joints_cam;   /* out["joints_cam"]      [B][21][3] metres */
+    const float *joints_tri;        /* out["joints_tri"]      [B][21][3] in each sample's reference-camera frame */
+    const int32_t *tri_status;      /* out["tri_status"]      [B][21] */
+    const float *gt_joints_cam;     /* inputs["joints_cam"]   [B][21][3] metres */
+    const float *gt_root;           /* inputs["root_joint"]   [B][3] metres */
+    const float *reproj_err;        /* the triangulation's reproj_err [B][V][21]; may be NULL */
+    const int32_t *inliers;         /* the triangulation's inliers [B][21]; may be NULL */
+    double *state;                  /* device, 8-byte aligned */
+    size_t state_doubles;           /* >= hmv_eval_absolute_doubles(V) */
+} hmv_eval_absolute_args;
+
+/* Doubles in an absolute state: 156 + 3 V (180 for V = 8); 0 for V outside 1 .. 16. */
+size_t hmv_eval_absolute_doubles(int32_t V);
+
+/* Adds one step on `stream`.  Every argument is checked before any HIP call: a NULL args, a struct_size other than
+ * sizeof(hmv_eval_absolute_args), B < 1, V outside 1 .. 16, B * V beyond 2^24, a NULL pred_joints_cam / joints_tri / tri_status /
+ * gt_joints_cam / gt_root, a NULL or misaligned state, or a state_doubles below hmv_eval_absolute_doubles(V) returns HMV_ERR_ARG and
+ * the text behind a NULL handle's last error names the field.  So does, with v_checked == 0, a V that differs from a non-zero
+ * state[2]; nothing is launched then and the state keeps its bytes. */
+int hmv_eval_absolute_add(int32_t device, const hmv_eval_absolute_args *args, void *stream);
+
 /* ---- sequence evaluation (a followed sequence, hmv_forward_frames_track: labels in the tracker's windows, jitter, window quality) ----
  * Under a tracker the windows are the tracker's own, so 2D labels expressed in dataset boxes do not belong to the predictions.  The
  * three entries below keep the evaluation of such a sequence on the device.  Stateless like the metrics, loss and track entries: a

@@ -10,7 +10,7 @@ def __getattr__(name):
     if name == "HandMvNet":  # lazy: importing the package must not require torch.cuda / the .so
         from .model import HandMvNet
         return HandMvNet
-    if name in ("SequenceTracker", "next_crop_boxes", "joints_to_frame"):   # sequences without dataset boxes (tracking.py)
+    if name in ("SequenceTracker", "next_crop_boxes", "joints_to_frame", "reproject_crop_boxes"):   # sequences without dataset boxes (tracking.py)
         from . import tracking
         return getattr(tracking, name)
     if name in ("SequenceEvaluator", "labels_to_windows"):   # evaluating a followed sequence (sequence_eval.py)

@@ -23,7 +23,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_forward_frames_occlusions", "hmv_forward_orders", "hmv_op_pose_consensus", "hmv_op_triangulate",
            "hmv_op_heatmap_peaks", "hmv_op_confidence_select", "hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax",
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
-           "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add"]
+           "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
+           "hmv_op_reproject_crop_boxes"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -119,6 +120,16 @@ class HmvConfidenceSelectArgs(ctypes.Structure):
                 ("carry", ctypes.c_int32), ("threshold", ctypes.c_double), ("step", ctypes.c_double),
                 ("conf", ctypes.c_void_p), ("present", ctypes.c_void_p), ("joint_mask", ctypes.c_void_p), ("mask_out", ctypes.c_void_p),
                 ("level", ctypes.c_void_p), ("lowered", ctypes.c_void_p), ("selected", ctypes.c_void_p)]
+
+
+class HmvReprojectBoxesArgs(ctypes.Structure):
+    """hmv_reproject_boxes_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("margin", ctypes.c_int32),
+                ("square", ctypes.c_int32), ("require_all", ctypes.c_int32),
+                ("points3d", ctypes.c_void_p), ("point_status", ctypes.c_void_p), ("frame_cam", ctypes.c_void_p),
+                ("intrinsic", ctypes.c_void_p), ("extrinsic", ctypes.c_void_p), ("joints_img", ctypes.c_void_p),
+                ("crop_boxes", ctypes.c_void_p), ("bbox", ctypes.c_void_p), ("status", ctypes.c_void_p), ("source", ctypes.c_void_p),
+                ("joints_reproj", ctypes.c_void_p), ("gap", ctypes.c_void_p)]
 
 
 class HandMvError(RuntimeError):
@@ -252,6 +263,8 @@ def load() -> ctypes.CDLL:
     lib.hmv_forward_frames_track.restype = ctypes.c_int
     lib.hmv_forward_frames_views_track.argtypes = lib.hmv_forward_frames_views.argtypes[:-1] + [ci, ci, fp, fp, vp]
     lib.hmv_forward_frames_views_track.restype = ctypes.c_int
+    lib.hmv_op_reproject_crop_boxes.argtypes = [ci, ctypes.POINTER(HmvReprojectBoxesArgs), vp]
+    lib.hmv_op_reproject_crop_boxes.restype = ctypes.c_int
     lib.hmv_op_labels_to_windows.argtypes = [ci, ci, fp, fp, fp, fp, ci, fp, fp, fp, vp]
     lib.hmv_op_labels_to_windows.restype = ctypes.c_int
     lib.hmv_op_mka.argtypes = [ci, fp, ci, ci, ci, ci, fp, vp]

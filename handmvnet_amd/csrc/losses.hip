@@ -88,29 +88,7 @@ __global__ __launch_bounds__(kThreads) void target_heatmaps_kernel(const float *
     for (int e = threadIdx.x; e < len; e += kThreads) o[e] = target_at(lds, e, h, w);
 }
 
-// get_2d_joints_from_3d_joints for one joint of one view (camera.py:4-60), then optionally the crop mapping
-// (datasets/utils.py:124-143 with its default image_size of 256).  x3: the joint in camera `root` (metres), root3: added to it
-// first when given.  e_root / e_view: [4][4] extrinsics, k: fx, fy, cx, cy, box: x1, y1, x2, y2 or null.
-__device__ void project_joint(const float *__restrict__ x3, const float *__restrict__ root3, const float *__restrict__ e_root,
-                              const float *__restrict__ e_view, const float *__restrict__ k, const float *__restrict__ box,
-                              double &u, double &v) {
-    double X[3];
-    for (int c = 0; c < 3; ++c) X[c] = (double)x3[c] + (root3 ? (double)root3[c] : 0.0);
-    double xw[4], a[16], y[3];
-    for (int r = 0; r < 4; ++r)
-        xw[r] = (double)e_root[r * 4] * X[0] + (double)e_root[r * 4 + 1] * X[1] + (double)e_root[r * 4 + 2] * X[2] + (double)e_root[r * 4 + 3];
-    for (int i = 0; i < 16; ++i) a[i] = (double)e_view[i];
-    solve4_xyz(a, xw, y);
-    const double z = y[2] * 1000.0 + 1e-6;
-    u = y[0] * 1000.0 * (double)k[0] / z + (double)k[2];
-    v = y[1] * 1000.0 * (double)k[1] / z + (double)k[3];
-    if (box) {
-        u = (u - (double)box[0]) * (256.0 / ((double)box[2] - (double)box[0]));
-        v = (v - (double)box[1]) * (256.0 / ((double)box[3] - (double)box[1]));
-    }
-}
-
-// (b) one lane per (sample, view, joint).
+// (b) get_2d_joints_from_3d_joints (project_joint, pose_rows.h), one lane per (sample, view, joint).
 __global__ __launch_bounds__(kThreads) void project_joints_kernel(const float *__restrict__ joints, int B, int V, int root_idx,
                                                                  const float *__restrict__ intrinsic, const float *__restrict__ extrinsic,
                                                                  const float *__restrict__ bbox, float *__restrict__ out) {

@@ -140,6 +140,36 @@ __device__ double block_sum(double v, double* red) {
     y[2] = (i20 * b[0] + i21 * b[1] + i22 * b[2] + i23 * b[3]) / det;
 }
 
+// get_2d_joints_from_3d_joints for one joint of one view (camera.py:4-60), then optionally the crop mapping
+// (datasets/utils.py:124-143 with its default image_size of 256).  x3: the joint in camera `root` (metres), root3: added to it
+// first when given.  e_root / e_view: [4][4] extrinsics, k: fx, fy, cx, cy, box: x1, y1, x2, y2 or null.  depth, when given, receives
+// the depth term the division used: millimetres plus the reference's epsilon.  (hmv_project_joints and the losses' reprojection,
+// losses.hip; the windows from the reprojected pose, track.hip.)
+// This function is compiled with the compiler's default contraction (track.hip includes this header in front of its contract(off)
+// pragma for that reason), so which products are fused is the optimiser's choice.  That hmv_op_reproject_crop_boxes' joints_reproj has
+// hmv_project_joints' bits rests on it choosing alike in both kernels, whose inlining contexts differ (a null root3 and box and a
+// depth there); nothing in the source guarantees it, tests/test_gpu_reproject_track.py asserts it.  If a compiler ever breaks it, pin
+// the roundings here under contract(off), as distance_3 below does, and accept that hmv_project_joints' last bits move once.
+[[maybe_unused]] __device__ void project_joint(const float *__restrict__ x3, const float *__restrict__ root3, const float *__restrict__ e_root,
+                                               const float *__restrict__ e_view, const float *__restrict__ k, const float *__restrict__ box,
+                                               double &u, double &v, double *depth = nullptr) {
+    double X[3];
+    for (int c = 0; c < 3; ++c) X[c] = (double)x3[c] + (root3 ? (double)root3[c] : 0.0);
+    double xw[4], a[16], y[3];
+    for (int r = 0; r < 4; ++r)
+        xw[r] = (double)e_root[r * 4] * X[0] + (double)e_root[r * 4 + 1] * X[1] + (double)e_root[r * 4 + 2] * X[2] + (double)e_root[r * 4 + 3];
+    for (int i = 0; i < 16; ++i) a[i] = (double)e_view[i];
+    solve4_xyz(a, xw, y);
+    const double z = y[2] * 1000.0 + 1e-6;
+    u = y[0] * 1000.0 * (double)k[0] / z + (double)k[2];
+    v = y[1] * 1000.0 * (double)k[1] / z + (double)k[3];
+    if (box) {
+        u = (u - (double)box[0]) * (256.0 / ((double)box[2] - (double)box[0]));
+        v = (v - (double)box[1]) * (256.0 / ((double)box[3] - (double)box[1]));
+    }
+    if (depth) *depth = z;
+}
+
 // Rows 0..2 of inverse(e) for a row-major 4x4: solve4_xyz on the four unit vectors, so T[r][k] is cofactor / det exactly (the products
 // with 1 and the sums with 0 round nothing).  A singular e gives inf / NaN.  (pose_consensus.hip, triangulate.hip.)
 [[maybe_unused]] __device__ __forceinline__ void inverse_rows(const float *__restrict__ e, double T[3][4]) {

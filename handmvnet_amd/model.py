@@ -453,28 +453,15 @@ class HandMvNet(torch.nn.Module):
           tri_reproj  [b, v, 21]     fp32, each triangulated joint's reprojection error in every view in frame pixels; NaN for a view
                                      that is not usable
           tri_inliers [b, 21]        int32, the RANSAC winner's inlier count; without `ransac` the number of usable views"""
-        from .triangulation import candidate_table, triangulate
+        from .triangulation import parse_gate, parse_ransac, triangulate
         if cam_params is None or "intrinsic" not in cam_params or "extrinsic" not in cam_params:
             raise ValueError("forward_absolute needs cam_params['intrinsic'] and cam_params['extrinsic']")
         if bbox is None:
             raise ValueError("forward_absolute needs bbox: the windows joints_crop_img is in")
-        table, threshold = None, 10.0
-        if ransac is not None:
-            if isinstance(ransac, tuple) and len(ransac) == 2 and np.ndim(ransac[1]) == 0 and np.ndim(ransac[0]) in (0, 2):
-                table, threshold = ransac
-                if np.ndim(table) == 0:
-                    table = candidate_table(self.num_views, int(table), n_iterations=4096)
-            else:
-                table = ransac
-        gate = None
-        if confidence is not None:
-            from .confidence import check_schedule, heatmap_peaks
-            if isinstance(confidence, (tuple, list)):
-                if len(confidence) != 3:
-                    raise ValueError("confidence must be None, a threshold or (threshold, step, carry)")
-                gate = check_schedule(confidence[0], confidence[1]) + (bool(confidence[2]),)
-            else:
-                gate = check_schedule(confidence, 0.05) + (False,)
+        table, threshold = parse_ransac(self.num_views, ransac)
+        gate = parse_gate(confidence)
+        if gate is not None:
+            from .confidence import heatmap_peaks
         b, v = int(x.shape[0]), int(x.shape[1])
         if view_mask is None:
             out = self.forward(x, bbox, cam_params)

@@ -50,6 +50,34 @@ def candidate_table(V: int, n_cams: int, n_iterations: int = 100, seed=None) -> 
     return np.ascontiguousarray(np.array(combos[:min(len(combos), n_iterations)], dtype=np.int32).reshape(-1, n_cams))
 
 
+def parse_ransac(num_views: int, ransac):
+    """The `ransac` argument of forward_absolute and SequenceTracker -> (candidate table or None, threshold): None = one DLT over all
+    present views; a candidate table [S, n_cams] (threshold 10 px); (n_cams, threshold) = every combination of n_cams cameras in
+    itertools order; or (table, threshold)."""
+    table, threshold = None, 10.0
+    if ransac is not None:
+        if isinstance(ransac, tuple) and len(ransac) == 2 and np.ndim(ransac[1]) == 0 and np.ndim(ransac[0]) in (0, 2):
+            table, threshold = ransac
+            if np.ndim(table) == 0:
+                table = candidate_table(num_views, int(table), n_iterations=4096)
+        else:
+            table = ransac
+    return table, threshold
+
+
+def parse_gate(confidence):
+    """The `confidence` argument of forward_absolute and SequenceTracker -> None or (threshold, step, carry): a threshold alone has
+    step 0.05 and no carry."""
+    if confidence is None:
+        return None
+    from .confidence import check_schedule
+    if isinstance(confidence, (tuple, list)):
+        if len(confidence) != 3:
+            raise ValueError("confidence must be None, a threshold or (threshold, step, carry)")
+        return check_schedule(confidence[0], confidence[1]) + (bool(confidence[2]),)
+    return check_schedule(confidence, 0.05) + (False,)
+
+
 def _intrinsic_rows(intrinsics: torch.Tensor, B: int, V: int, what: str = "intrinsics") -> torch.Tensor:
     """[B, V, 4] (fx, fy, cx, cy) rows from rows or from [B, V, 3, 3] matrices (gathered on the device; their other entries are the
     caller's promise -- the drop-ins check them)."""
@@ -64,7 +92,7 @@ def _intrinsic_rows(intrinsics: torch.Tensor, B: int, V: int, what: str = "intri
 def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, present=None, joint_mask=None, subsets=None,
                 threshold: float = 10.0, refit: bool = False, frame_cam=None, extrinsic_kind: str = "cam_to_world",
                 return_details: bool = False, confidences=None, confidence_threshold: float = 0.5, confidence_step: float = 0.05,
-                carry: bool = False):
+                carry: bool = False, out=None):
     """One 3D point per (sample, joint) from its 2D positions in V views (one launch; fp64 arithmetic from the fp32 inputs).
       points      [B, V, J, 2] device tensor, J <= 64: frame pixels -- or crop pixels when `bbox` [B, V, 4] (x1, y1, x2, y2) and
                   `image_size` are given (the model's joints_crop_img and the batch's bboxes; the mapping has joints_to_frame's bits)
@@ -84,7 +112,9 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
     an inlier (the point is 0, 0, 0, as the reference leaves it); 2 fewer than two usable views or every candidate skipped (NaN);
     3 a coordinate is not finite.  return_details=True: a dict with those two and reproj_err [B, V, J] (the point's error in every
     view, NaN where the view is not usable), inliers [B, J], winner [B, J] (index into the table; -1 without one); with
-    `confidences` also level [B, J] (the confidence threshold that decided), lowered [B, J] and selected [B, J] (views kept)."""
+    `confidences` also level [B, J] (the confidence threshold that decided), lowered [B, J] and selected [B, J] (views kept).
+    out: None, or (points3d, status) -- contiguous fp32 [B, J, 3] and int32 [B, J] tensors on the points' device that receive the
+    result in the place of new ones (a caller that keeps its buffers, like SequenceTracker)."""
     if extrinsic_kind not in KINDS:
         raise ValueError('extrinsic_kind must be "cam_to_world" or "world_to_cam"')
     if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[-1] != 2:
@@ -134,6 +164,11 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
     if not points.is_cuda:
         raise _lib.HandMvError("handmvnet_amd runs on MI355X only: points must be a CUDA(HIP) tensor (no CPU fallback)")
     dev = points.device
+    if out is not None:
+        o3, ost = out
+        if (tuple(o3.shape) != (B, J, 3) or o3.dtype != torch.float32 or tuple(ost.shape) != (B, J) or ost.dtype != torch.int32
+                or o3.device != dev or ost.device != dev or not o3.is_contiguous() or not ost.is_contiguous()):
+            raise ValueError(f"out must be contiguous (float32 [{B}, {J}, 3], int32 [{B}, {J}]) tensors on {dev}")
     gate = None
     if confidences is not None:   # the select launch first, on the same stream; its mask holds the caller's joint_mask and the absent views
         from .confidence import confidence_mask
@@ -162,8 +197,8 @@ def triangulate(points, intrinsics, extrinsics, *, bbox=None, image_size=None, p
     pr = None if present is None else (present.detach().to(dev) != 0).to(torch.uint8).contiguous()
     jm = None if joint_mask is None else (joint_mask.detach().to(dev) != 0).to(torch.uint8).contiguous()
     tab = None if table is None else table.detach().to(dev).to(torch.int32).contiguous()
-    out3d = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
-    status = torch.empty((B, J), device=dev, dtype=torch.int32)
+    out3d = out[0] if out is not None else torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+    status = out[1] if out is not None else torch.empty((B, J), device=dev, dtype=torch.int32)
     err = inl = win = None
     if return_details:
         err = torch.empty((B, V, J), device=dev, dtype=torch.float32)

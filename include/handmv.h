@@ -1235,6 +1235,62 @@ typedef struct hmv_confidence_select_args {
 
 int hmv_op_confidence_select(int32_t device, const hmv_confidence_select_args *args, void *stream);
 
+/* ---- windows from the reprojected pose: the crop windows of ALL cameras of a sample from one 3D pose ----
+ * hmv_op_next_crop_boxes moves a camera's window to the box around that camera's own 2D joints: a view that loses the hand loses its
+ * window, and an absent view returns to a stale one.  This launch (track.hip) moves the windows of every camera to where ONE 3D pose --
+ * the triangulated joints, or the model's joints_cam on the triangulated root -- projects: get_2d_joints_from_3d_joints
+ * (utils/camera.py:25-44, the arithmetic of hmv_project_joints) followed by points2d_to_bbox (datasets/utils.py:5-27, the integer rule
+ * of hmv_op_next_crop_boxes), per slot (b, v).  It runs BEHIND the own-joints rule, in place on its windows and status, which stay
+ * wherever this launch does not move them.
+ *   points3d      [B][21][3] fp32, metres, in the frame of camera frame_cam[b]
+ *   point_status  NULL, or [B][21] int32: hmv_op_triangulate's status of every joint
+ *   frame_cam     NULL (camera 0), or DEVICE int32 [B]
+ *   intrinsic     [B][V][4] fp32 (fx, fy, cx, cy);  extrinsic [B][V][4][4] fp32, camera-to-world as hmv_project_joints takes them
+ *   joints_img    NULL, or [B][V][21][2] fp32: the views' own 2D joints in frame pixels, read for `gap` only
+ *   crop_boxes    [B][V][4] int32, in / out;  bbox NULL, or [B][V][4] fp32, in / out: the same four numbers as fp32
+ *   status        [B][V] int32, in / out: hmv_op_next_crop_boxes' 0 moved / 1 absent / 2 kept
+ *   source        [B][V] int32, out: 0 = the window is the own-joints rule's (or whatever crop_boxes held), 1 = it is the reprojection's
+ *   joints_reproj NULL, or [B][V][21][2] fp32, out: the projections in frame pixels
+ *   gap           NULL, or [B][V] fp32, out
+ * A sample is OK when its 63 coordinates are finite, frame_cam[b] lies in [0, V) and point_status is NULL or point_status[b][0] == 0
+ * (the root was triangulated) -- with require_all != 0: all 21 entries are 0.
+ * Slot (b, v) of an OK sample is REPROJECTED when every one of its 21 joints has a positive depth term z = z_cam * 1000 + 1e-6 (the
+ * reference's unit and epsilon), finite u and v of magnitude below 1e9, and the window of the 21 projections is at most 65536 px wide
+ * and tall.  Such a slot: crop_boxes = points2d_to_bbox(projections, margin, square), bbox its fp32, source 1; status 2 becomes 0, 0 stays
+ * 0, 1 stays 1 (the window moves, the view is still absent: the three window fractions of hmv_seq_eval_add still sum to one).
+ * Any other slot: source 0; not one byte of its crop_boxes, bbox and status is written.
+ * joints_reproj is the projection in fp64 from the fp32 inputs, rounded once -- the bits of hmv_project_joints without bbox -- written as
+ * computed for every slot of an OK sample, NaN for a sample that is not.
+ * gap[b][v] = the mean over the 21 joints of |joints_img - joints_reproj|, in fp64 from the fp32 values as written, rounded once: how far
+ * this camera's own joints are from what the others agree on, in frame pixels.  Defined when joints_img is given, the sample is OK and
+ * the INCOMING status is 0; NaN otherwise.  An output only: no rule reads it.
+ * One wave64 per slot, four per workgroup, a joint per lane; minimum, maximum and the gap's sum by fixed-order shuffles; no LDS, no
+ * atomics.  The bits of a slot depend on neither B nor its place in the call.  Takes no handle; asynchronous on `stream`.
+ * HMV_ERR_ARG before any HIP call, the outputs untouched, for: a NULL args, a struct_size below sizeof(hmv_reproject_boxes_args), B < 1,
+ * B * V beyond 2^24, V outside [1, 16] (hmv_op_triangulate's), margin < 0, a NULL points3d / intrinsic / extrinsic / crop_boxes /
+ * status / source. */
+typedef struct hmv_reproject_boxes_args {
+    int32_t struct_size;   /* sizeof(hmv_reproject_boxes_args) */
+    int32_t B, V;
+    int32_t margin;
+    int32_t square;
+    int32_t require_all;
+    const float *points3d;
+    const int32_t *point_status;
+    const int32_t *frame_cam;
+    const float *intrinsic;
+    const float *extrinsic;
+    const float *joints_img;
+    int32_t *crop_boxes;
+    float *bbox;
+    int32_t *status;
+    int32_t *source;
+    float *joints_reproj;
+    float *gap;
+} hmv_reproject_boxes_args;
+
+int hmv_op_reproject_crop_boxes(int32_t device, const hmv_reproject_boxes_args *args, void *stream);
+
 const char *hmv_version(void);
 
 /* The tile shape the general conv / GEMM kernel's launcher rule picks for M output pixels, Cout channels, reduction length K

@@ -24,7 +24,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_heatmap_peaks", "hmv_op_confidence_select", "hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax",
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
            "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
-           "hmv_op_reproject_crop_boxes"]
+           "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -130,6 +130,30 @@ class HmvReprojectBoxesArgs(ctypes.Structure):
                 ("intrinsic", ctypes.c_void_p), ("extrinsic", ctypes.c_void_p), ("joints_img", ctypes.c_void_p),
                 ("crop_boxes", ctypes.c_void_p), ("bbox", ctypes.c_void_p), ("status", ctypes.c_void_p), ("source", ctypes.c_void_p),
                 ("joints_reproj", ctypes.c_void_p), ("gap", ctypes.c_void_p)]
+
+
+class HmvFfBlockArgs(ctypes.Structure):
+    """hmv_ff_block_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("rows", ctypes.c_int32), ("d", ctypes.c_int32), ("ld", ctypes.c_int32),
+                ("hid", ctypes.c_int32), ("S", ctypes.c_int32), ("lds", ctypes.c_int32), ("ldr", ctypes.c_int32),
+                ("slice", ctypes.c_int64), ("rg_out", ctypes.c_int32), ("rg_in", ctypes.c_int32), ("ldx", ctypes.c_int32),
+                ("ldw1", ctypes.c_int32), ("ldw2", ctypes.c_int32), ("ldo", ctypes.c_int32), ("tile_rows", ctypes.c_int32),
+                ("tile_rows_used", ctypes.c_int32),
+                ("slab", ctypes.c_void_p), ("bias0", ctypes.c_void_p), ("res", ctypes.c_void_p), ("x", ctypes.c_void_p),
+                ("n1g", ctypes.c_void_p), ("n1b", ctypes.c_void_p), ("fg", ctypes.c_void_p), ("fb", ctypes.c_void_p),
+                ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("n2g", ctypes.c_void_p), ("n2b", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_pairs", ctypes.c_void_p),
+                ("sat", ctypes.c_void_p)]
+
+
+class HmvChebFusedArgs(ctypes.Structure):
+    """hmv_cheb_fused_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("K", ctypes.c_int32), ("ldx", ctypes.c_int32),
+                ("c1", ctypes.c_int32), ("ldw1", ctypes.c_int32), ("c2", ctypes.c_int32), ("ldw2", ctypes.c_int32),
+                ("c3", ctypes.c_int32), ("ldw3", ctypes.c_int32), ("ldo", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("bias1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
+                ("bias2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("bias3", ctypes.c_void_p), ("tk", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("out", ctypes.c_void_p)]
 
 
 class HandMvError(RuntimeError):
@@ -306,6 +330,11 @@ def load() -> ctypes.CDLL:
                  "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce", "hmv_op_splitk_layernorm", "hmv_op_add_pe",
                  "hmv_op_cheb_mix"):
         getattr(lib, name).restype = ctypes.c_int
+    # the fused tail kernels (struct entries)
+    lib.hmv_op_ff_block.argtypes = [ci, ctypes.POINTER(HmvFfBlockArgs), vp]
+    lib.hmv_op_ff_block.restype = ctypes.c_int
+    lib.hmv_op_cheb_fused.argtypes = [ci, ctypes.POINTER(HmvChebFusedArgs), vp]
+    lib.hmv_op_cheb_fused.restype = ctypes.c_int
     lib.hmv_set_graphs.argtypes = [vp, ci]
     lib.hmv_set_graphs.restype = ctypes.c_int
     lib.hmv_graph_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]

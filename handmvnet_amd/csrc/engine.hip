@@ -3641,3 +3641,53 @@ extern "C" int hmv_op_cheb_mix(int32_t device, const float *y, int32_t ldy, int3
     if ((co + 31) / 32 > 65535) return op_bad(who, "co beyond the launch grid");
     return op_run(who, device, stream, [&](hipStream_t s) { return launch_cheb_mix(y, ldy, B, co, tk, bias, leaky, out, ldo, s); });
 }
+
+// ------------------------------------------------------------------ the fused tail kernels (fusion_kernels.hip), each behind the launcher the
+// engine calls (op-level float64 tests: tests/test_gpu_tail_f64.py)
+extern "C" int hmv_op_ff_block(int32_t device, hmv_ff_block_args *a, void *stream) {
+    static const char *who = "hmv_op_ff_block";
+    if (!a) return op_bad(who, "args is NULL");
+    if (a->struct_size != (int32_t)sizeof(hmv_ff_block_args)) return op_bad(who, "struct_size does not match this library's hmv_ff_block_args");
+    if (a->rows <= 0 || a->d <= 0) return op_bad(who, "null operand or non-positive size");
+    if (!a->out || !a->w1 || !a->w2 || !a->b1 || !a->b2 || !a->fg || !a->fb) return op_bad(who, "out, w1, w2, b1, b2, fg and fb must not be NULL");
+    if ((a->n1g != nullptr) != (a->n1b != nullptr) || (a->n2g != nullptr) != (a->n2b != nullptr)) return op_bad(who, "a norm takes its gamma and beta together");
+    if ((a->slab != nullptr) == (a->x != nullptr)) return op_bad(who, "exactly one source: slab or x");
+    if (a->tile_rows != 0 && a->tile_rows != 16 && a->tile_rows != 32) return op_bad(who, "tile_rows must be 0 (the launcher's rule), 16 or 32");
+    FfBlockParams p{};
+    p.slab = a->slab; p.S = a->S; p.slice = a->slice > 0 ? (size_t)a->slice : 0; p.lds = a->lds; p.bias0 = a->bias0;
+    p.res = a->slab ? a->res : nullptr; p.ldr = a->ldr; p.rg_out = a->rg_out; p.rg_in = a->rg_in;
+    p.x = a->x; p.ldx = a->ldx;
+    p.rows = a->rows; p.d = a->d; p.ld = a->ld;
+    p.n1g = a->n1g; p.n1b = a->n1b; p.fg = a->fg; p.fb = a->fb; p.n2g = a->n2g; p.n2b = a->n2b;
+    p.w1 = a->w1; p.b1 = a->b1; p.ldw1 = a->ldw1; p.w2 = a->w2; p.b2 = a->b2; p.ldw2 = a->ldw2;
+    p.out = a->out; p.ldo = a->ldo; p.hid = a->hid; p.out_pairs = a->out_pairs; p.sat = a->sat;
+    if (const char *why = ff_block_refusal(p)) return op_bad(who, why);
+    if (a->slab && (a->lds < a->d || (a->S > 1 && a->slice < (int64_t)a->rows * a->lds))) return op_bad(who, "lds >= d, and slices of at least rows * lds floats");
+    if (p.res && (a->ldr < a->d || a->rg_out < 0 || (a->rg_out > 0 && a->rg_in < a->rg_out)))
+        return op_bad(who, "ldr >= d; residual row groups: rg_out = 0, or 0 < rg_out <= rg_in");
+    if (a->x && a->ldx < a->d) return op_bad(who, "ldx >= d");
+    if (a->tile_rows == 32 && ff_block_lds_bytes(p, 32) > (size_t)160 * 1024) return op_bad(who, "a 32-row tile of this ld and hid does not fit 160 KB of LDS");
+    int used = 0;
+    const int rc = op_run(who, device, stream, [&](hipStream_t s) { return launch_ff_block(p, s, a->tile_rows, &used); });
+    if (rc == HMV_OK) a->tile_rows_used = used;
+    return rc;
+}
+
+extern "C" int hmv_op_cheb_fused(int32_t device, const hmv_cheb_fused_args *a, void *stream) {
+    static const char *who = "hmv_op_cheb_fused";
+    if (!a) return op_bad(who, "args is NULL");
+    if (a->struct_size != (int32_t)sizeof(hmv_cheb_fused_args)) return op_bad(who, "struct_size does not match this library's hmv_cheb_fused_args");
+    if (!a->x || !a->w1 || !a->bias1 || !a->w2 || !a->bias2 || !a->w3 || !a->bias3 || !a->tk || !a->scratch || !a->out)
+        return op_bad(who, "null operand or non-positive size");
+    if (a->B <= 0 || a->K <= 0 || a->c1 <= 0 || a->c2 <= 0 || a->c3 <= 0 || (int64_t)a->B * 21 > INT32_MAX) return op_bad(who, "null operand or non-positive size");
+    if (!cheb_fusable(a->K, a->ldx, a->ldw1, a->c1, a->ldw2, a->c2, a->ldw3, a->c3))
+        return op_bad(who, "the shape has no fused form (K <= 576, c1 <= 256, c2 <= 64, each a multiple of 16; c3 <= 5; ldx, ldw1 >= K, ldw2 >= c1, ldw3 >= c2, multiples of 4)");
+    if (a->ldo < a->c3) return op_bad(who, "ldo >= c3");
+    ChebFusedParams p{};
+    p.x = a->x; p.ldx = a->ldx; p.B = a->B; p.K = a->K;
+    p.w1 = a->w1; p.ldw1 = a->ldw1; p.c1 = a->c1; p.bias1 = a->bias1;
+    p.w2 = a->w2; p.ldw2 = a->ldw2; p.c2 = a->c2; p.bias2 = a->bias2;
+    p.w3 = a->w3; p.ldw3 = a->ldw3; p.c3 = a->c3; p.bias3 = a->bias3;
+    p.tk = a->tk; p.scratch = a->scratch; p.out = a->out; p.ldo = a->ldo;
+    return op_run(who, device, stream, [&](hipStream_t s) { return launch_cheb_fused(p, s); });
+}

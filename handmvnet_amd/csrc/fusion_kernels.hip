@@ -327,16 +327,26 @@ __global__ __launch_bounds__(64 * FF_WAVES) void ff_block_kernel(const FfBlockPa
     }
 }
 
-hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s) {
+// What the launcher does not take, in words (nullptr: it takes p); hmv_op_ff_block answers with the same text
+const char *ff_block_refusal(const FfBlockParams &p) {
+    if (p.d > 256 * FF_VEC || p.ld > 256 * FF_VEC || p.ld > 16 * FF_NV1 || p.ld % 16 || p.ld < p.d || p.ldo != p.ld)
+        return "d <= ld = ldo <= 576, ld a multiple of 16";
+    if ((p.lds & 3) || (p.ldr & 3) || (p.ldx & 3) || (p.ldw1 & 3) || (p.ldw2 & 3)) return "every row stride must be a multiple of 4";
+    if ((p.hid != 128 && p.hid != 256) || p.ldw1 < p.ld || p.ldw2 < p.hid) return "hid must be 128 or 256, ldw1 >= ld and ldw2 >= hid";
+    if (!p.slab && !p.x) return "no source: slab or x";
+    if (p.slab && (p.S < 1 || p.S > 4 || !p.bias0)) return "a slab has 1 to 4 slices and a bias0";
+    return nullptr;
+}
+size_t ff_block_lds_bytes(const FfBlockParams &p, int tile_rows) {
+    const size_t rows = tile_rows, hreg = rows * (p.hid + 4) > (size_t)4 * p.ld ? rows * (p.hid + 4) : (size_t)4 * p.ld;
+    return ((size_t)2 * rows * (p.ld + 4) + hreg + (size_t)2 * p.ld) * sizeof(float);
+}
+
+hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s, int tile_rows, int *tile_rows_used) {
     if (p.rows <= 0) return hipSuccess;
-    if (p.d > 256 * FF_VEC || p.ld > 256 * FF_VEC || p.ldo != p.ld || p.ld % 16 || p.ld < p.d || (p.lds & 3) || (p.ldr & 3) || (p.ldx & 3) ||
-        p.ld > 16 * FF_NV1 || (p.hid != 128 && p.hid != 256) || p.ldw1 < p.ld || p.ldw2 < p.hid || (p.ldw1 & 3) || (p.ldw2 & 3) || (!p.slab && !p.x) ||
-        (p.slab && (p.S < 1 || p.S > 4 || !p.bias0)))
-        return hipErrorInvalidValue;
-    auto lds_of = [&](int rb) {
-        const size_t rows = 16 * rb, hreg = rows * (p.hid + 4) > (size_t)4 * p.ld ? rows * (p.hid + 4) : (size_t)4 * p.ld;
-        return ((size_t)2 * rows * (p.ld + 4) + hreg + (size_t)2 * p.ld) * sizeof(float);
-    };
+    if (ff_block_refusal(p) || (tile_rows != 0 && tile_rows != 16 && tile_rows != 32)) return hipErrorInvalidValue;
+    auto lds_of = [&](int rb) { return ff_block_lds_bytes(p, 16 * rb); };
+    if (tile_rows == 32 && lds_of(2) > 160 * 1024) return hipErrorInvalidValue;
     // 32-row tiles once 16-row ones would not fit one round of workgroups (one per CU: 90 KB of LDS, 240 registers), if they fit LDS
     static DeviceOnce once;
     static int ncu[64] = {};   // CUs per device, written once by `once`
@@ -349,7 +359,8 @@ hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s) {
         }, &dev);
         e != hipSuccess)
         return e;
-    const int rb = ((p.rows + 15) / 16 > ncu[dev] && lds_of(2) <= 160 * 1024) ? 2 : 1;
+    const int rb = tile_rows ? tile_rows / 16 : ((p.rows + 15) / 16 > ncu[dev] && lds_of(2) <= 160 * 1024) ? 2 : 1;
+    if (tile_rows_used) *tile_rows_used = 16 * rb;
     const size_t lds = lds_of(rb);
     const dim3 grid((p.rows + 16 * rb - 1) / (16 * rb)), block(64 * FF_WAVES);
     if (p.hid == 128) {

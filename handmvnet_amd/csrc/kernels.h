@@ -365,7 +365,11 @@ struct FfBlockParams {
     int hid;                               // 128 | 256
     unsigned long long *dbg;               // diagnostic builds only: 100 MHz stamps at the phase boundaries of workgroup 0
 };
-hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s);
+// tile_rows: token rows per workgroup -- 0: 32 once 16-row tiles would need more than one round of workgroups and 32 rows fit LDS, else 16;
+// 16 | 32 forces one (op-level tests; 32 beyond 160 KB of LDS is refused).  *tile_rows_used (or null) receives the height launched.
+hipError_t launch_ff_block(const FfBlockParams &p, hipStream_t s, int tile_rows = 0, int *tile_rows_used = nullptr);
+const char *ff_block_refusal(const FfBlockParams &p);            // why launch_ff_block does not take p, or nullptr
+size_t ff_block_lds_bytes(const FfBlockParams &p, int tile_rows);   // LDS of one workgroup of 16 | 32 rows
 // hr_fuse.hip: the up-sampling terms of an HRNet fuse layer (hrnet.py:194-212) as one launch:
 //   out = act(((base + G_0) + G_1) + G_2),  G_s = W_s x_s + b_s at x_s's resolution, read at (y >> shift_s, x >> shift_s)
 // base / out / x_s: NHWC rows of fp32 or fp16 (f16); w_s fp32 [>= C rows][ldw], bias_s fp32; sources in the reference's order (ascending j)

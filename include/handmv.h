@@ -476,6 +476,63 @@ int hmv_op_add_pe(int32_t device, const float *x, int32_t ldx, int32_t rows, int
 int hmv_op_cheb_mix(int32_t device, const float *y, int32_t ldy, int32_t B, int32_t co, const float *tk, const float *bias, int32_t leaky,
                     float *out, int32_t ldo, void *stream);
 
+/* The fused tail of a fusion block, everything behind its to_out GEMM in one launch (launch_ff_block):
+ *   t  = slab: slices 0 .. S - 1 added in index order + bias0 + res row (or no res)   |   x: the row as it is
+ *   n1 = n1g ? LayerNorm(t; n1g, n1b) : t;   f0 = LayerNorm(n1; fg, fb);   h = GELU(f0 W1^T + b1);   f2 = h W2^T + b2 + n1
+ *   out = n2g ? LayerNorm(f2; n2g, n2b) : f2, columns [d, ldo) written as zeros; out_pairs (or NULL) [rows][hi ldo | lo ldo] fp16 =
+ *   the same rows split, `sat` (or NULL) raised when a value was clamped to the pair range.
+ * Exactly one of slab / x.  slab [S][rows][lds], S in 1 .. 4, slice s at slab + s * slice (floats); bias0 has round4(d) floats; res row of
+ * output row r is (r / rg_out) * rg_in + r % rg_out (rg_out = 0: r), stride ldr.  Rows of slab, res and x are read up to round4(d), nothing
+ * beyond it, and what [d, round4(d)) holds changes no result.
+ * Operand contract of the kernel: w1 is [hid][ldw1], ldw1 >= ld, finite in columns [d, ld) (they meet zeros); w2 has at least ld rows of
+ * ldw2 >= hid floats, zeros in rows [d, ld); b1 has hid floats; b2 has ld floats, zeros past d; every gamma and beta has d floats; every row
+ * stride (lds, ldr, ldx, ldw1, ldw2, ldo) is a multiple of 4; d <= ld = ldo <= 576, ld % 16 == 0, hid 128 or 256.  n1g / n1b and n2g / n2b
+ * come in pairs or not at all.
+ * tile_rows: 0 = the launcher's rule (32-row tiles once ceil(rows / 16) exceeds the device's CU count and they fit LDS, else 16);
+ * 16 or 32 forces a height (32 is refused where it does not fit 160 KB of LDS: ld > 544 at hid 128, ld > 480 at hid 256).  A row's bits
+ * depend on neither the height nor the row's place in the call.  tile_rows_used receives the height launched (args is not const).
+ * HMV_ERR_ARG before any launch for a NULL args, another struct_size, everything above that does not hold, rows < 1, d < 1, lds / ldr /
+ * ldx below d, rg_out < 0 or 0 < rg_in < rg_out, a NULL out, w1, w2, b1, b2, fg or fb. */
+typedef struct hmv_ff_block_args {
+    int32_t struct_size;   /* sizeof(hmv_ff_block_args) */
+    int32_t rows, d, ld, hid;
+    int32_t S, lds, ldr;
+    int64_t slice;
+    int32_t rg_out, rg_in, ldx, ldw1, ldw2, ldo;
+    int32_t tile_rows;        /* in */
+    int32_t tile_rows_used;   /* out */
+    const float *slab, *bias0, *res, *x;
+    const float *n1g, *n1b, *fg, *fb;
+    const float *w1, *b1, *w2, *b2;
+    const float *n2g, *n2b;
+    float *out;
+    void *out_pairs;
+    int32_t *sat;
+} hmv_ff_block_args;
+
+int hmv_op_ff_block(int32_t device, hmv_ff_block_args *args, void *stream);
+
+/* JointsDecoderGCN as the engine runs it, two launches (launch_cheb_fused): three ChebConv layers K -> c1 -> c2 -> c3 over x [B * 21][ldx],
+ *   layer_i(v)[b * 21 + n][o] = sum_k sum_j tk[k][n][j] * (v_b W_i,k)[j][o] + bias_i[o],  LeakyReLU 0.01 after layers 1 and 2.
+ * w_i: [3 * c_i][ldw_i], row k * c_i + o = column o of order k's weight; w3 has 16 rows, zeros from row 3 * c3 on.  tk [3][21][21].
+ * scratch [B * 21][c1] receives layer 1's output, out[b * 21 + n][0, c3) the result (stride ldo; no other column is written).
+ * Shapes (cheb_fusable): K <= 576, K % 16 == 0, c1 <= 256, c1 % 16 == 0, c2 <= 64, c2 % 16 == 0, c3 <= 5, ldx / ldw1 >= K, ldw2 >= c1,
+ * ldw3 >= c2, strides multiples of 4.  A sample's bits do not depend on B.
+ * HMV_ERR_ARG before any launch for a NULL args, another struct_size, a shape outside that list, a size below 1, ldo < c3, a NULL pointer. */
+typedef struct hmv_cheb_fused_args {
+    int32_t struct_size;   /* sizeof(hmv_cheb_fused_args) */
+    int32_t B, K, ldx;
+    int32_t c1, ldw1, c2, ldw2, c3, ldw3;
+    int32_t ldo, reserved;
+    const float *x;
+    const float *w1, *bias1, *w2, *bias2, *w3, *bias3;
+    const float *tk;
+    float *scratch;
+    float *out;
+} hmv_cheb_fused_args;
+
+int hmv_op_cheb_fused(int32_t device, const hmv_cheb_fused_args *args, void *stream);
+
 /* Diagnostic micro-benchmark: average milliseconds of `iters` launches of one NHWC conv shape on
  * pseudo-random data.  tile: -1 = the engine's own choice, else 0..7 = 128x32, 128x64, 128x128, 256x128,
  * 128x256, 256x256, 128x128 (k-step 16), 128x256 (k-step 16) (BM x BN); a value without an instantiation returns an error.

@@ -174,3 +174,68 @@ def test_non_gemm_op_entries_refuse_bad_arguments():
     # ... and the smallest good call of one of them still runs
     assert lib.hmv_op_add_pe(0, A, 44, 42, 42, None, 44, A, O, 48, None) == OK
     assert not out[:42 * 48].any() and bool((out[42 * 48:] == 7.0).all())
+
+
+def test_fused_tail_op_entries_refuse_bad_arguments():
+    """hmv_op_ff_block and hmv_op_cheb_fused (tests/test_gpu_tail_f64.py): HMV_ERR_ARG with the entry's name in hmv_last_error(NULL), before
+    any launch -- the outputs keep their bytes -- for everything launch_ff_block / cheb_fusable refuse, null operands, and a forced 32-row
+    tile that does not fit LDS."""
+    from handmvnet_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    a = torch.zeros(1 << 18, device=dev)
+    out = torch.full((1 << 16,), 7.0, device=dev)
+    A, O = a.data_ptr(), out.data_ptr()
+
+    def ff(**over):
+        s = _lib.HmvFfBlockArgs()
+        s.struct_size = ctypes.sizeof(_lib.HmvFfBlockArgs)
+        s.rows, s.d, s.ld, s.ldo, s.hid = 5, 44, 48, 48, 128
+        s.S, s.lds, s.slice, s.ldr, s.ldx, s.ldw1, s.ldw2 = 4, 48, 5 * 48, 48, 48, 48, 128
+        s.slab = s.bias0 = s.res = s.n1g = s.n1b = s.fg = s.fb = s.w1 = s.b1 = s.w2 = s.b2 = s.n2g = s.n2b = A
+        s.out = O
+        for k, v in over.items():
+            setattr(s, k, v)
+        return s
+
+    def cheb(**over):
+        s = _lib.HmvChebFusedArgs()
+        s.struct_size = ctypes.sizeof(_lib.HmvChebFusedArgs)
+        s.B, s.K, s.ldx, s.c1, s.ldw1, s.c2, s.ldw2, s.c3, s.ldw3, s.ldo = 1, 96, 96, 32, 96, 16, 32, 1, 16, 4
+        s.x = s.w1 = s.bias1 = s.w2 = s.bias2 = s.w3 = s.bias3 = s.tk = A
+        s.scratch = s.out = O
+        for k, v in over.items():
+            setattr(s, k, v)
+        return s
+
+    bad_ff = [{"struct_size": 8}, {"rows": 0}, {"d": 0}, {"out": None}, {"w1": None}, {"w2": None}, {"b1": None}, {"b2": None}, {"fg": None},
+              {"fb": None}, {"n1b": None}, {"n2g": None}, {"slab": None}, {"x": A}, {"bias0": None}, {"S": 0}, {"S": 5}, {"tile_rows": 8},
+              {"ld": 40, "ldo": 40}, {"ld": 56, "ldo": 56, "ldw1": 56}, {"ldo": 64}, {"d": 580, "ld": 592, "ldo": 592, "ldw1": 592, "lds": 592, "ldr": 592},
+              {"lds": 46}, {"ldr": 50}, {"ldw1": 50}, {"ldw2": 130}, {"hid": 64}, {"ldw1": 44}, {"ldw2": 124}, {"lds": 40}, {"ldr": 40},
+              {"slice": 100}, {"rg_out": -1}, {"rg_out": 21, "rg_in": 20}, {"slab": None, "x": A, "ldx": 46}, {"slab": None, "x": A, "ldx": 40},
+              {"d": 560, "ld": 560, "ldo": 560, "ldw1": 560, "lds": 560, "ldr": 560, "slice": 5 * 560, "tile_rows": 32},
+              {"d": 496, "ld": 496, "ldo": 496, "ldw1": 496, "lds": 496, "ldr": 496, "slice": 5 * 496, "hid": 256, "ldw2": 256, "tile_rows": 32}]
+    for over in bad_ff:
+        assert lib.hmv_op_ff_block(0, ctypes.byref(ff(**over)), None) == ARG, over
+        assert b"hmv_op_ff_block" in lib.hmv_last_error(None), (over, lib.hmv_last_error(None))
+    assert lib.hmv_op_ff_block(0, None, None) == ARG and b"hmv_op_ff_block" in lib.hmv_last_error(None)
+    bad_cheb = [{"struct_size": 8}, {"B": 0}, {"K": 0}, {"c3": 0}, {"K": 592, "ldx": 592, "ldw1": 592}, {"K": 100, "ldx": 100, "ldw1": 100},
+                {"ldx": 92}, {"ldw1": 92}, {"ldx": 98}, {"c1": 24}, {"c1": 272, "ldw2": 272}, {"c2": 80, "ldw3": 80}, {"c2": 8}, {"c3": 6, "ldo": 8},
+                {"ldw2": 28}, {"ldw3": 12}, {"ldo": 0}, {"x": None}, {"w1": None}, {"bias1": None}, {"w2": None}, {"bias2": None}, {"w3": None},
+                {"bias3": None}, {"tk": None}, {"scratch": None}, {"out": None}]
+    for over in bad_cheb:
+        assert lib.hmv_op_cheb_fused(0, ctypes.byref(cheb(**over)), None) == ARG, over
+        assert b"hmv_op_cheb_fused" in lib.hmv_last_error(None), (over, lib.hmv_last_error(None))
+    assert lib.hmv_op_cheb_fused(0, None, None) == ARG and b"hmv_op_cheb_fused" in lib.hmv_last_error(None)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+    # ... and the good calls run: zeros in, LayerNorm2's beta (0) out; tile_rows_used says what was launched
+    good = ff(tile_rows=32)
+    assert lib.hmv_op_ff_block(0, ctypes.byref(good), None) == OK, lib.hmv_last_error(None)
+    assert good.tile_rows_used == 32
+    torch.cuda.synchronize()
+    assert not out[:5 * 48].any() and bool((out[5 * 48:] == 7.0).all())
+    out.fill_(7.0)
+    assert lib.hmv_op_cheb_fused(0, ctypes.byref(cheb()), None) == OK, lib.hmv_last_error(None)
+    torch.cuda.synchronize()
+    assert not out[:21 * 32].any()      # scratch and out alias here: zeros either way

@@ -23,7 +23,7 @@ Launcher (kernel)                                               test
   launch_splitk_layernorm (layernorm_kernel<4>)                   test_splitk_layernorm_is_reduce_then_layernorm_bit_for_bit
   launch_add_pe (add_pe_kernel) / launch_add_pe_views (..._views) test_add_pe
   launch_cheb_mix (cheb_mix_kernel)                               test_cheb_mix
-The fused tail kernels are held bit for bit to these launches by test_fused_tail_kernels_match_the_unfused_launches (test_gpu_parity.py)."""
+The fused tail kernels (fusion_kernels.hip) have float64 tests of their own: test_gpu_tail_f64.py."""
 import math
 
 import pytest

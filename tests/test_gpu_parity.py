@@ -139,8 +139,10 @@ FUSED_TAIL_CASES = ["tiny_r50", "cfg2s_r18_v4_256", "r50_lq", "r18_lq_wocam", "r
 def test_fused_tail_kernels_match_the_unfused_launches(name):
     """fusion_kernels.hip (FeedForward + LayerNorms behind the split-K to_out GEMM as ONE launch; the three ChebConv layers as
     two) against the launch-per-op path it replaces (hmv_set_tail_fusion(h, 0)): same arithmetic up to
-    the GEMMs' summation order, so the two agree far inside the parity tolerance -- and the fused path is the one the
-    reference fixtures are checked against (test_forward_matches_reference_fixture).  Fewer launches, too."""
+    the summation order of the GEMMs and of the LayerNorm rows, so the two agree far inside the parity tolerance -- and the fused path is
+    the one the reference fixtures are checked against (test_forward_matches_reference_fixture).  Fewer launches, too.  Asserted: `tokens`
+    (the tail's input) bit for bit, `fused` and `joints_cam` to 2e-5 rel-L2 -- not bit equality of the tail; the fused kernels alone, against
+    float64: test_gpu_tail_f64.py."""
     m, cfg, sd, (x, bbox, intr), _ = _model(name)
     fused = _run(m, x, bbox, intr)
     n_fused = m.launch_count()

@@ -34,4 +34,7 @@ def __getattr__(name):
     if name in ("JointsToVertices", "hand_ik", "rigid_unapply"):   # hand pose parameters and MANO vertices (ik.py)
         from . import ik
         return getattr(ik, name)
+    if name in ("ManoParams", "ManoSkin"):   # MANO skinning on the device (mano.py)
+        from . import mano
+        return getattr(mano, name)
     raise AttributeError(name)

@@ -24,7 +24,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_heatmap_peaks", "hmv_op_confidence_select", "hmv_op_input_layout", "hmv_op_maxpool", "hmv_op_soft_argmax",
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
            "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
-           "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused"]
+           "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused", "hmv_mano_pack_bytes", "hmv_op_mano_pack",
+           "hmv_op_mano_skin"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -154,6 +155,24 @@ class HmvChebFusedArgs(ctypes.Structure):
                 ("x", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("bias1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
                 ("bias2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("bias3", ctypes.c_void_p), ("tk", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+MANO_BETAS_NONE, MANO_BETAS_SHARED, MANO_BETAS_PER_ROW = 0, 1, 2   # HMV_MANO_BETAS_* of include/handmv.h
+
+
+class HmvManoParams(ctypes.Structure):
+    """hmv_mano_params of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("n_verts", ctypes.c_int32), ("tips", ctypes.c_int32 * 5), ("reserved", ctypes.c_int32),
+                ("v_template", ctypes.c_void_p), ("shapedirs", ctypes.c_void_p), ("posedirs", ctypes.c_void_p),
+                ("J_regressor", ctypes.c_void_p), ("weights", ctypes.c_void_p)]
+
+
+class HmvManoSkinArgs(ctypes.Structure):
+    """hmv_mano_skin_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("n", ctypes.c_int32), ("n_verts", ctypes.c_int32), ("betas_mode", ctypes.c_int32),
+                ("project", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("packed", ctypes.c_void_p), ("rot", ctypes.c_void_p), ("betas", ctypes.c_void_p), ("align", ctypes.c_void_p),
+                ("vertices", ctypes.c_void_p), ("joints", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 class HandMvError(RuntimeError):
@@ -303,6 +322,12 @@ def load() -> ctypes.CDLL:
     lib.hmv_op_hand_ik.restype = ctypes.c_int
     lib.hmv_op_rigid_unapply.argtypes = [ci, fp, fp, ci, ci, fp, vp]
     lib.hmv_op_rigid_unapply.restype = ctypes.c_int
+    lib.hmv_mano_pack_bytes.argtypes = [ci]
+    lib.hmv_mano_pack_bytes.restype = ctypes.c_size_t
+    lib.hmv_op_mano_pack.argtypes = [ci, ctypes.POINTER(HmvManoParams), vp, vp]
+    lib.hmv_op_mano_pack.restype = ctypes.c_int
+    lib.hmv_op_mano_skin.argtypes = [ci, ctypes.POINTER(HmvManoSkinArgs), vp]
+    lib.hmv_op_mano_skin.restype = ctypes.c_int
     lib.hmv_op_prepare_frames.argtypes = [ci, fp, ci, ci, ci, fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                           ci, ci, fp, vp]
     lib.hmv_op_prepare_frames.restype = ctypes.c_int

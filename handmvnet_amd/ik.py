@@ -8,7 +8,8 @@ MANO layer -- the three-point rigid alignment onto the template (utils/misc.py:1
     rigid_unapply(points, align)     -> R^T (points - t)
     JointsToVertices(mano_layer)     the batched drop-in for the reference class; the MANO layer is the caller's
 
-The MANO layer itself needs manopth and the licensed MANO files and is not part of this package: it is plugged in as a callable."""
+The MANO layer is plugged in as a callable: mano.ManoSkin (this package's skinning kernel over the caller's MANO arrays) or the
+caller's own, e.g. a manopth ManoLayer."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .mano import ManoSkin
 
 STATUS_OK, STATUS_NONFINITE = 0, 1   # include/handmv.h: hmv_op_hand_ik
 
@@ -97,7 +99,8 @@ class JointsToVertices:
     its input.  template: its flat-hand joints [21, 3]; by default mano_layer(identity)[1], as joints_to_vertices.py:23.  The
     constructor reads the template back once to refuse one with a zero-length bone (every result would be NaN).  __call__ runs the
     IK launch, the layer and the un-alignment launch with no copy to the host, and leaves last_pose_R [B, 16, 3, 3] and last_status
-    [B] (hand_ik's) on the object."""
+    [B] (hand_ik's) on the object.  With a mano.ManoSkin as mano_layer (this package's own MANO layer) the alignment goes into the skin
+    launch and there is no un-alignment launch; the skin's own status is mano_layer.last_status."""
 
     PARENTS = (0, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19)   # SNAP_PARENT, analytical_ik.py:8-30
 
@@ -129,5 +132,7 @@ class JointsToVertices:
             self.joints_template = self.joints_template.to(joints_mm.device)
         pose_R, align, status = hand_ik(joints_mm, self.joints_template)
         self.last_pose_R, self.last_status = pose_R, status
+        if isinstance(self.mano_layer, ManoSkin):   # the un-alignment runs inside the skin launch: one launch and one rounding fewer
+            return self.mano_layer(pose_R, align=align, joints=False)[0]
         vertices = self.mano_layer(pose_R)[0]
         return rigid_unapply(vertices, align)

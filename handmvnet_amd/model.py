@@ -600,7 +600,8 @@ class HandMvNet(torch.nn.Module):
                        f"{mode}_norm_auc_j": norm_auc_j}
         if self.get_vertices:
             if self.joints_to_vertices is None:
-                raise NotImplementedError("get_vertices needs manopth + MANO assets (joints_to_vertices.py:14-23), absent here")
+                raise NotImplementedError("get_vertices needs model.joints_to_vertices = ik.JointsToVertices(mano.ManoSkin(mano.ManoParams(...))): "
+                                          "the MANO arrays are the caller's (joints_to_vertices.py:14-23)")
             # handmvnet.py:390-408, the per-sample host loop as one batched device call (handmvnet_amd/ik.py)
             out["vertices"] = self.joints_to_vertices(out["joints_cam"] * 1000)
             gt_v = inputs["vertices"].to(out["vertices"].device)

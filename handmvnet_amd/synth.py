@@ -116,3 +116,84 @@ def synth_inputs(cfg: HotPathConfig, batch: int, seed: int = 0, size: int | None
     intr = np.stack([400.0 + 500.0 * w[..., 0], 400.0 + 500.0 * w[..., 1],
                      300.0 + 40.0 * w[..., 2], 220.0 + 40.0 * w[..., 3]], axis=-1).astype(np.float32)
     return x, bbox, intr
+
+
+# ---- MANO-shaped parameters (handmvnet_amd/mano.py): a seeded hand for tests and probes, not the licensed model
+
+# chain joints 1..15 in MANO's order: index, middle, little, ring, thumb; per finger the first joint (metres, right hand, wrist at the
+# origin, fingers along +x, thumb towards +y) and the direction of its bones
+_MANO_LIKE_FINGERS = (((0.095, 0.025, 0.002), (1.0, 0.10, 0.0)), ((0.098, 0.0, 0.004), (1.0, 0.0, 0.0)), ((0.080, -0.045, -0.002), (1.0, -0.20, 0.0)),
+                      ((0.090, -0.023, 0.001), (1.0, -0.10, 0.0)), ((0.030, 0.035, -0.012), (0.7, 0.7, -0.1)))
+_MANO_LIKE_BONES = (0.035, 0.025, 0.022)   # first to second joint, second to third, third to the tip
+_MANO_TIPS = {"right": (745, 317, 444, 556, 673), "left": (745, 317, 445, 556, 673)}   # thumb, index, middle, ring, little
+
+
+def mano_like(seed: int, n_verts: int = 778, side: str = "right"):
+    """Seeded MANO-shaped parameters -> mano.ManoParams: a hand about 0.1 m long in metres, n_verts >= 5 vertices scattered around
+    the bones of a 16-joint skeleton, every vertex weighted mostly to the joint it sits at, a joint regressor that puts each joint
+    among its own vertices, small seeded shape and pose directions.  Rows of `weights` and `J_regressor` sum to 1; the 21 template
+    joints have no zero-length bone (checked here), so ik.JointsToVertices accepts the template.  tips: MANO's own for n_verts >= 778,
+    else the last five vertices; the tip vertices sit one bone beyond their finger's last joint."""
+    from .mano import ManoParams
+    if n_verts < 5:
+        raise ValueError(f"n_verts must be at least 5 (the five finger tips), got {n_verts}")
+    if side not in _MANO_TIPS:
+        raise ValueError(f"side must be 'right' or 'left', got {side!r}")
+    nv = int(n_verts)
+    joints = np.zeros((16, 3))
+    ends = np.zeros((16, 3))            # where the bone that starts at joint k ends
+    for f, (base, d) in enumerate(_MANO_LIKE_FINGERS):
+        d = np.asarray(d) / np.sqrt(np.sum(np.square(d)))
+        p = np.asarray(base, np.float64)
+        for link in range(3):
+            joints[1 + 3 * f + link] = p
+            p = p + d * _MANO_LIKE_BONES[link]
+            ends[1 + 3 * f + link] = p
+    ends[0] = (0.09, -0.005, 0.0)
+    tips = _MANO_TIPS[side] if nv >= 778 else tuple(range(nv - 5, nv))
+    tip_finger = (4, 0, 1, 3, 2)        # thumb, index, middle, ring, little as fingers of the chain order above
+    primary = np.arange(nv) % 16
+    u = uniform01("mano_like.u", seed, nv)
+    off = normalish("mano_like.off", seed, nv * 3).reshape(nv, 3) * 0.006
+    v = joints[primary] + (ends[primary] - joints[primary]) * u[:, None] + off
+    palm = primary == 0
+    v[palm, 1] += (uniform01("mano_like.palm", seed, nv)[palm] - 0.5) * 0.07
+    for t, f in zip(tips, tip_finger):
+        primary[t] = 3 + 3 * f
+        v[t] = ends[3 + 3 * f]
+    # weights: 0.75 on the vertex's own joint, the rest seeded over all 16
+    w = uniform01("mano_like.w", seed, nv * 16).reshape(nv, 16) + 0.02
+    w = 0.25 * w / w.sum(1, keepdims=True)
+    w[np.arange(nv), primary] += 0.75
+    w = w / w.sum(1, keepdims=True)
+    # regressor, sparse like MANO's: seeded weights over the joint's own vertices (0.8 of the row) and over every 16th vertex from a
+    # seeded start (the rest); a joint without a vertex of its own (n_verts < 16) has the second part alone
+    r = uniform01("mano_like.reg", seed, 16 * nv).reshape(16, nv) + 0.02
+    start = (np.arange(16) + 1 + (uniform01("mano_like.reg_start", seed, 16) * 15).astype(np.int64)) % 16   # never the joint's own class
+    for k in range(16):
+        own = primary == k
+        far = (np.arange(nv) % 16 == start[k]) & ~own if nv >= 32 else ~own
+        row = np.where(far, r[k], 0.0)
+        row = row / row.sum()
+        if own.any():
+            mine = np.where(own, r[k], 0.0)
+            row = 0.2 * row + 0.8 * mine / mine.sum()
+        r[k] = row
+    r = r / r.sum(1, keepdims=True)
+    v *= 0.55                           # the layout above is 0.18 m from the wrist to the middle finger's tip: a hand of 0.1 m
+    if side == "left":
+        v[:, 1] = -v[:, 1]
+    sd = normalish("mano_like.shapedirs", seed, nv * 30).reshape(nv, 3, 10) * 0.002
+    pd = normalish("mano_like.posedirs", seed, nv * 405).reshape(nv, 3, 135) * 0.001
+    params = ManoParams(v.astype(np.float32), sd.astype(np.float32), pd.astype(np.float32), r.astype(np.float32), w.astype(np.float32),
+                        side=side, tips=tips)
+    # the 21 template joints, as the skinning rule builds them at identity rotations and zero betas
+    j16 = params.J_regressor.astype(np.float64) @ params.v_template.astype(np.float64)
+    wsum = params.weights.astype(np.float64).sum(1)
+    j21 = np.concatenate([j16, params.v_template[list(tips)].astype(np.float64) * wsum[list(tips), None]])[
+        [0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20]]
+    parents = [0, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19]
+    bones = np.sqrt(np.sum(np.square(j21[1:] - j21[parents[1:]]), axis=1))
+    if not (bones > 1e-4).all():
+        raise ValueError(f"mano_like({seed}, {nv}): the template has a bone shorter than 0.1 mm; use more vertices or another seed")
+    return params

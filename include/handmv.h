@@ -1104,6 +1104,80 @@ int hmv_op_hand_ik(int32_t device, const float *joints, const float *template_jo
  * HMV_ERR_ARG before any HIP call for n <= 0, n_pts <= 0, a NULL points / out, a NULL or misaligned align. */
 int hmv_op_rigid_unapply(int32_t device, const float *points, const double *align, int32_t n, int32_t n_pts, float *out, void *stream);
 
+/* ---- MANO skinning: 16 rotation matrices and 10 shape coefficients to the mesh and the 21 joints ----
+ * The published MANO / SMPL blend-skinning formula in the order ManoLayer.forward applies it with root_rot_mode = joint_rot_mode =
+ * "rotmat", use_pca=False and no th_trans / center_idx (the reference's configuration, models/joints_to_vertices.py:14-20), as one
+ * stateless launch over a packed parameter buffer (mano_skin.hip).  manopth and the MANO files are not part of this repository: the
+ * arithmetic is pinned to the formula below (tests/mano_oracle.py repeats it in float64), not to the package's bits.
+ *
+ * Parameters, fp32 DEVICE arrays in MANO's own layouts, Nv = n_verts:
+ *   v_template [Nv][3]   shapedirs [Nv][3][10]   posedirs [Nv][3][135]   J_regressor [16][Nv]   weights [Nv][16]
+ *   tips [5] (HOST values in the struct): the vertex indices of the thumb, index, middle, ring and little finger tips
+ *   parents of joints 0..15: -1,0,1,2,0,4,5,0,7,8,0,10,11,0,13,14
+ * hmv_op_mano_pack writes them once into `packed`, hmv_mano_pack_bytes(n_verts) bytes (0 for n_verts outside 1 .. 2^20), 8-byte
+ * aligned: 528 doubles (J_regressor . v_template [16][3], then J_regressor . shapedirs [16][3][10], each a sum over the vertices in
+ * ascending order in fp64), 8 int32 (tips, n_verts, 0, 0), then 454 planes of Nv floats: v_template [3][Nv], shapedirs [10][3][Nv],
+ * posedirs [135][3][Nv], weights [16][Nv].  No skin launch touches the regressor or the MANO layouts.
+ *
+ * hmv_op_mano_skin, per row, in fp64 from the fp32 inputs, no fused multiply-add, every output rounded once:
+ *   1. project != 0: each of the 16 matrices becomes Q = U V^T of its SVD, column 2 of Q negated when det Q < 0 (the polar factor,
+ *      made a rotation: what manopth's rotproj does in rotmat mode; it turns the reflection hmv_op_hand_ik keeps as slot 0 for a
+ *      mirrored hand into a rotation).  project == 0: the matrices are used as given.
+ *   2. v_shaped = v_template + shapedirs . betas;   J = J_regressor . v_shaped  (from the folded sums of the packed buffer)
+ *   3. v_posed = v_shaped + posedirs . vec(rot[1..15] - I), the 135 values in slot order, row-major
+ *   4. G[0] = [rot[0] | J[0]],  G[k] = G[parent k] . [rot[k] | J[k] - J[parent k]]
+ *   5. A[k] = G[k] with its translation reduced by G[k].R . J[k]
+ *   6. vertex v = (sum_k weights[v][k] A[k]) . [v_posed[v]; 1]
+ *   7. joints: the 16 translations of G, then the five tip vertices, reordered by [0,13,14,15,16,1,2,3,17,4,5,6,18,10,11,12,19,7,8,9,20]
+ *   8. everything times 1000 (metres to millimetres);  with `align` ([n][12] fp64 as hmv_op_hand_ik wrote it), then R^T (x - t): the mesh
+ *      back where the prediction was, in the same pass
+ *   rot       [n][16][3][3] fp32, slot 0 the global rotation
+ *   betas     NULL with HMV_MANO_BETAS_NONE (zeros), [10] with HMV_MANO_BETAS_SHARED, [n][10] with HMV_MANO_BETAS_PER_ROW
+ *   vertices  [n][Nv][3] fp32 or NULL;   joints [n][21][3] fp32 or NULL; not both NULL.  A call without vertices gives the joints the
+ *             bits they have in a call with them.
+ *   status    [n] int32: 1 when some value of the row (vertices when requested, joints whether or not requested) is non-finite.  The
+ *             values are written as computed; a bad row marks itself alone.
+ * A `packed` that was written for another n_verts is seen on the device: every value of the call is NaN, every status 1.
+ * One workgroup of 512 threads per row (the status is an OR over the row and there are no atomics, so a row has one owner); row i of
+ * an n-row call has the bits of a one-row call.  Outputs must not alias inputs.  Both entries take no handle and are asynchronous on
+ * `stream`.
+ * HMV_ERR_ARG before any HIP call (hmv_last_error(NULL) names the argument) for: a NULL params / args, another struct_size, n <= 0,
+ * n_verts outside 1 .. 2^20, a NULL parameter array, a tip outside [0, n_verts), a NULL or misaligned packed, a NULL rot / status, an
+ * unknown betas_mode, a betas_mode other than NONE with a NULL betas, a misaligned align, vertices and joints both NULL. */
+enum { HMV_MANO_BETAS_NONE = 0, HMV_MANO_BETAS_SHARED = 1, HMV_MANO_BETAS_PER_ROW = 2 };
+
+typedef struct hmv_mano_params {
+    int32_t struct_size;   /* sizeof(hmv_mano_params) */
+    int32_t n_verts;
+    int32_t tips[5];
+    int32_t reserved;      /* 0 */
+    const float *v_template;
+    const float *shapedirs;
+    const float *posedirs;
+    const float *J_regressor;
+    const float *weights;
+} hmv_mano_params;
+
+typedef struct hmv_mano_skin_args {
+    int32_t struct_size;   /* sizeof(hmv_mano_skin_args) */
+    int32_t n;
+    int32_t n_verts;
+    int32_t betas_mode;    /* HMV_MANO_BETAS_* */
+    int32_t project;
+    int32_t reserved;      /* 0 */
+    const void *packed;
+    const float *rot;
+    const float *betas;
+    const double *align;   /* or NULL */
+    float *vertices;
+    float *joints;
+    int32_t *status;
+} hmv_mano_skin_args;
+
+size_t hmv_mano_pack_bytes(int32_t n_verts);
+int hmv_op_mano_pack(int32_t device, const hmv_mano_params *params, void *packed, void *stream);
+int hmv_op_mano_skin(int32_t device, const hmv_mano_skin_args *args, void *stream);
+
 /* ---- pose consensus: the S estimates of a reference-view sweep in one camera's frame, their consensus and their disagreement ----
  * Every camera of a rig can serve as reference view (hmv_forward_orders), which gives S root-relative estimates of the same hand, estimate
  * s in the frame of camera ref_cam[s].  One stateless launch (pose_consensus.hip) rotates them into camera target_cam's frame by the

@@ -25,7 +25,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
            "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
            "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused", "hmv_mano_pack_bytes", "hmv_op_mano_pack",
-           "hmv_op_mano_skin"]
+           "hmv_op_mano_skin", "hmv_op_attention_pairs"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -261,6 +261,8 @@ def load() -> ctypes.CDLL:
     lib.hmv_op_attention_lq.restype = ctypes.c_int
     lib.hmv_op_attention.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, vp]
     lib.hmv_op_attention_x3.argtypes = [ci, fp, ci, ci, ci, ci, ci, fp, vp]
+    lib.hmv_op_attention_pairs.argtypes = [ci, ci, fp, ci, ci, ci, ci, ci, fp, fp, vp]
+    lib.hmv_op_attention_pairs.restype = ctypes.c_int
     lib.hmv_op_hr_fuse_up.argtypes = [ci, ci, fp, ci, ci, ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(ci),
                                       ctypes.POINTER(vp), ctypes.POINTER(vp), ci, vp, vp]
     lib.hmv_op_attention.restype = ctypes.c_int

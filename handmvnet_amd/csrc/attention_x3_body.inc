@@ -116,9 +116,12 @@
         for (int e = 0; e < 16; ++e) {
             const float pe = expf(sacc[e] - m_new);      // exp(-inf) = 0 for keys >= Tk
             psum += pe;
-            const _Float16 a = (_Float16)pe;               // 0 <= pe <= 1: no clamp
+            // P travels as a pair of 2^14 pe: fp16's subnormal spacing makes the pair's quantum ABSOLUTE, 2^-25 for pe itself -- a key with
+            // P below that vanished, whatever its value row held -- and 2^-39 for the scaled pe; the merge takes the 2^14 out again (exact)
+            const float ps = pe * 16384.f;
+            const _Float16 a = (_Float16)ps;               // 0 <= ps <= 16384: no clamp
             ph[e >> 3][e & 7] = a;
-            pl[e >> 3][e & 7] = (_Float16)(pe - (float)a);
+            pl[e >> 3][e & 7] = (_Float16)(ps - (float)a);
         }
         l_run = l_run * alpha + psum;
         m_run = m_new;
@@ -160,7 +163,7 @@
             a[w] = expf(sM[w * 32 + l31] - M);   // exp(-inf) = 0 for a wave that had no chunk
             den += sL[w * 32 + l31] * a[w];
         }
-        const float inv = 1.f / den;
+        const float inv = 6.103515625e-05f / den;   // 2^-14 / den: O carries the 2^14 of its P pairs, l does not
         const int row = qblk * 32 + l31;
         const int c = wave;   // this wave finishes channel block `wave`
 #pragma unroll

@@ -3119,6 +3119,34 @@ int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, 
     return HMV_OK;
 }
 
+/* Test hook: the `pairs` epilogue of both attention bodies on its own (include/handmv.h). */
+int hmv_op_attention_pairs(int32_t device, int32_t x3, const float *qkv, int32_t B, int32_t T, int32_t Tq, int32_t koff, int32_t Tk,
+                           void *out_pairs, int32_t *sat, void *stream) {
+    if (!qkv || !out_pairs || B <= 0 || T <= 0 || Tq <= 0 || Tq > T || Tk <= 0 || koff < 0 || koff + Tk > T || (x3 != 0 && x3 != 1)) {
+        g_create_err = "hmv_op_attention_pairs: bad argument";
+        return HMV_ERR_ARG;
+    }
+    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *out = static_cast<float *>(out_pairs);   // a row is 32 D bytes in either output form (AttSeg::rows)
+    void *pairs = nullptr;
+    RangeWord rw;
+    hipError_t e = hipSuccess;
+    if (x3) {   // the kernel takes rows of (hi, lo) fp16 pairs: split the fp32 rows first (hmv_op_attention_x3); the split reports to its own word
+        e = rw.alloc();
+        if (e == hipSuccess) e = op_guarded_alloc(&pairs, (size_t)B * T * 3072 * 4, s);
+        if (e == hipSuccess) e = launch_rows_f32_to_half(qkv, pairs, (size_t)B * T, 3072, 2, s, rw.p);
+        if (e == hipSuccess) e = launch_attention(static_cast<const float *>(pairs), B, T, Tq, koff, Tk, out, s, 1, 1, sat);
+    } else {
+        e = launch_attention(qkv, B, T, Tq, koff, Tk, out, s, 1, 0, sat);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    op_guarded_free(pairs);
+    if (e != hipSuccess) { g_create_err = std::string("attention launch failed: ") + hipGetErrorString(e); return HMV_ERR_HIP; }
+    if (x3 && rw.saturated()) { g_create_err = "hmv_op_attention_pairs: " + std::string(kRangeMsg); return HMV_ERR_RANGE; }
+    return HMV_OK;
+}
+
 int hmv_op_attention_lq(int32_t device, const float *q, int32_t q_ld, int32_t q_bstride, const float *k, const float *v, int32_t kv_ld,
                         int32_t B, int32_t T, int32_t Tq, float *out, void *stream) {
     if (!q || !k || !v || !out || B <= 0 || T <= 0 || Tq <= 0 || q_ld < 2048 || kv_ld < 2048 || q_bstride < 0 || (q_ld & 3) || (kv_ld & 3)) {

@@ -763,8 +763,11 @@ __global__ __launch_bounds__(64 * ATT_WAVES, D == 128 ? HMV_ATT_OCC : 1) void at
 // The fp16-kernel modes' form of attention_mfma_kernel<128>: same decomposition (one workgroup per (sample, head, 32-query block), the
 // 32-key chunks dealt to four waves, S^T = K Q^T so that a query row is a lane, P stays in registers, partials merged through LDS in
 // wave order), but both products run on v_mfma_f32_32x32x16_f16 with every operand split into fp16 (hi, lo) pairs, hi = fp16(x),
-// lo = fp16(x - hi), and three MFMAs per k16 step -- hi.hi + lo.hi + hi.lo, fp32 accumulation: fp32-equivalent (2^-22 per operand) like
-// the q / k / v projections in front of it (gemm_x3.hip) at 8 + 8 instead of 64 + 64 matrix-pipe cycles per 16 channels / keys.  The
+// lo = fp16(x - hi), and three MFMAs per k16 step -- hi.hi + lo.hi + hi.lo, fp32 accumulation: fp32-equivalent like the q / k / v
+// projections in front of it (gemm_x3.hip) at 8 + 8 instead of 64 + 64 matrix-pipe cycles per 16 channels / keys.  q, k, v are pairs to
+// 2^-22 relative; P reaches down to 0, where a pair's quantum is ABSOLUTE (fp16's subnormal spacing: 2^-25), so P is split as 2^14 P
+// (quantum 2^-39) and the merge divides the 2^14 out -- unscaled, a key with P < 2^-25 was dropped whatever its value row held
+// (tests/test_gpu_attention_rows.py, spread_v: 128 times torch fp32's row error before, 2 times after).  The
 // exact-fp32 kernel spends 41 of its 88 us at cfg-3 in the matrix pipe (tools/att_probe.py).
 //   S^T   A = K rows (the lane's own key row from global memory), B = Q block from LDS (staged once per workgroup)
 //   P V   B = P^T straight from the accumulator registers (slot j of step s = register 8 s + j = key 16 s + 8 (j >> 2) + 4 kh + (j & 3)),

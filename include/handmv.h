@@ -375,10 +375,20 @@ int hmv_op_hr_fuse_up(int32_t device, int32_t f16, const float *base, int32_t N,
 int hmv_op_attention(int32_t device, const float *qkv, int32_t B, int32_t T, int32_t Tq, int32_t koff, int32_t Tk, float *out,
                      void *stream);
 /* The same attention as the fp16-kernel modes (HMV_F16, HMV_F32X3) run it: q, k, v, P as fp16 (hi, lo) pairs on the fp16 matrix cores,
- * three products per step, fp32 accumulation and softmax -- fp32-equivalent (2^-22 per operand).  Same arguments; the fp32 rows are split into
- * pairs first (in those modes the projection GEMMs write pairs themselves); synchronises the stream. */
+ * three products per step, fp32 accumulation and softmax -- fp32-equivalent: q, k, v to 2^-22 relative (the pair range above), P, which
+ * reaches down to 0, as the pair of 2^14 P with an ABSOLUTE quantum of 2^-39 (fp16's subnormal spacing; unscaled it was 2^-25, and a key
+ * with P below that was dropped whatever its value row held).  Same arguments; the fp32 rows are split into pairs first (in those modes the
+ * projection GEMMs write pairs themselves); synchronises the stream. */
 int hmv_op_attention_x3(int32_t device, const float *qkv, int32_t B, int32_t T, int32_t Tq, int32_t koff, int32_t Tk, float *out,
                         void *stream);
+/* The same two kernels with their `pairs` epilogue (what a forward of the fp16-kernel modes with the fused tail launches; op-level tests):
+ * x3 = 0 the fp32 kernel of hmv_op_attention, x3 = 1 the pair kernel of hmv_op_attention_x3 (the fp32 rows are split first).  out_pairs:
+ * device [B][Tq][hi 1024 | lo 1024] halfs, hi = fp16(clamp(v, +-65504)), lo = fp16(clamped - hi) of the fp32 row the same kernel stores
+ * without the epilogue.  sat (or NULL): device range word, set to 1 by the fp32 kernel where a row value was clamped and left alone
+ * otherwise; the pair kernel never writes it (its rows are convex combinations of values that are pairs already) -- there the entry's own
+ * split of the inputs reports, as HMV_ERR_RANGE.  Synchronises the stream. */
+int hmv_op_attention_pairs(int32_t device, int32_t x3, const float *qkv, int32_t B, int32_t T, int32_t Tq, int32_t koff, int32_t Tk,
+                           void *out_pairs, int32_t *sat, void *stream);
 
 /* The attention of the learnable-query fusion (MultiHeadAttentionLearnableQuery, layers.py:284-291; 8 heads x 256) through the
  * engine's kernel: q rows at q + (b * q_bstride + i) * q_ld (q_bstride = 0: the same probe queries for every sample), k / v rows

@@ -103,6 +103,25 @@ def test_op_attention_argument_errors():
     for args in ((2, 42, 43, 0, 42), (2, 42, 21, 30, 21), (2, 42, 21, 0, 0), (0, 42, 21, 0, 21), (2, 42, 0, 0, 21), (2, 42, 21, -1, 21)):
         assert lib.hmv_op_attention(0, qkv.data_ptr(), *args, out.data_ptr(), None) != 0, args
     assert lib.hmv_op_attention(0, None, 2, 42, 21, 0, 42, out.data_ptr(), None) != 0
+    # hmv_op_attention_pairs: the same ranges, x3 outside {0, 1} and null operands -- HMV_ERR_ARG with the entry's name, nothing launched
+    pairs = torch.full((2 * 42, 2048), 7.0, dtype=torch.float16, device="cuda:0")
+    sat = torch.full((1,), 7, dtype=torch.int32, device="cuda:0")
+    for x3 in (0, 1):
+        for args in ((2, 42, 43, 0, 42), (2, 42, 21, 30, 21), (2, 42, 21, 0, 0), (0, 42, 21, 0, 21), (2, 42, 0, 0, 21), (2, 42, 21, -1, 21),
+                     (2, 0, 21, 0, 21)):
+            assert lib.hmv_op_attention_pairs(0, x3, qkv.data_ptr(), *args, pairs.data_ptr(), sat.data_ptr(), None) == ARG, (x3, args)
+            assert b"hmv_op_attention_pairs" in lib.hmv_last_error(None)
+        assert lib.hmv_op_attention_pairs(0, x3, None, 2, 42, 21, 21, 21, pairs.data_ptr(), sat.data_ptr(), None) == ARG
+        assert lib.hmv_op_attention_pairs(0, x3, qkv.data_ptr(), 2, 42, 21, 21, 21, None, sat.data_ptr(), None) == ARG
+    for x3 in (2, -1):
+        assert lib.hmv_op_attention_pairs(0, x3, qkv.data_ptr(), 2, 42, 21, 21, 21, pairs.data_ptr(), sat.data_ptr(), None) == ARG
+    torch.cuda.synchronize()
+    assert bool((pairs == 7.0).all()) and int(sat.item()) == 7
+    # ... and the good calls run: zero rows in, zero pairs out for the 21 query rows of both samples, the range word left alone (NULL is accepted)
+    for x3 in (0, 1):
+        pairs.fill_(7.0)
+        assert lib.hmv_op_attention_pairs(0, x3, qkv.data_ptr(), 2, 42, 21, 21, 21, pairs.data_ptr(), sat.data_ptr() if x3 else None, None) == OK
+        assert not pairs[:2 * 21].any() and bool((pairs[2 * 21:] == 7.0).all()) and int(sat.item()) == 7     # out_pairs is [B][Tq][2048]
 
 
 def test_non_gemm_op_entries_refuse_bad_arguments():

@@ -25,7 +25,7 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
            "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
            "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused", "hmv_mano_pack_bytes", "hmv_op_mano_pack",
-           "hmv_op_mano_skin", "hmv_op_attention_pairs"]
+           "hmv_op_mano_skin", "hmv_op_attention_pairs", "hmv_op_conv2d_form"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -155,6 +155,20 @@ class HmvChebFusedArgs(ctypes.Structure):
                 ("x", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("bias1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
                 ("bias2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("bias3", ctypes.c_void_p), ("tk", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+HMV_FORM_DUAL, HMV_FORM_CHAIN, HMV_FORM_POOL, HMV_FORM_PHASES, HMV_FORM_SPLITK, HMV_FORM_PAIR_OUT = 1, 2, 4, 8, 16, 32
+ROUTE_RULE, ROUTE_NEVER, ROUTE_FORCE = 0, 1, 2   # the route_* fields of hmv_conv_form_args
+
+
+class HmvConvFormArgs(ctypes.Structure):
+    """hmv_conv_form_args of include/handmv.h."""
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "struct_size", "dtype", "form", "N", "H", "W", "Cin", "Cout", "R", "S", "stride", "pad", "relu", "Ho", "Wo",
+        "ld_in", "ldc", "ldr", "ld_in2", "route_stream", "route_gemm8", "route_hs", "route_x3k16", "gemm8_persist",
+        "Cin2", "H2", "W2", "stride2", "next_cout", "pool_h", "pool_w", "merged", "slices", "reserved")] +
+                [(n, ctypes.c_void_p) for n in ("in_", "residual", "in2", "w", "bias", "w2", "bias2", "next_w", "next_bias",
+                                                "out", "next_out")] + [("kernel_name", ctypes.c_char_p)])
 
 
 MANO_BETAS_NONE, MANO_BETAS_SHARED, MANO_BETAS_PER_ROW = 0, 1, 2   # HMV_MANO_BETAS_* of include/handmv.h
@@ -362,6 +376,8 @@ def load() -> ctypes.CDLL:
     lib.hmv_op_ff_block.restype = ctypes.c_int
     lib.hmv_op_cheb_fused.argtypes = [ci, ctypes.POINTER(HmvChebFusedArgs), vp]
     lib.hmv_op_cheb_fused.restype = ctypes.c_int
+    lib.hmv_op_conv2d_form.argtypes = [ci, ctypes.POINTER(HmvConvFormArgs), vp]
+    lib.hmv_op_conv2d_form.restype = ctypes.c_int
     lib.hmv_set_graphs.argtypes = [vp, ci]
     lib.hmv_set_graphs.restype = ctypes.c_int
     lib.hmv_graph_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]

@@ -529,6 +529,73 @@ struct Loader {
         L.x3n = true;
     }
 
+    // Bottleneck conv3 and its block's downsample conv as ONE layer over the concatenated reduction [t2 | x] . [W3 ; Wds]
+    // (resnet.py:124-144): a3 [outc][planes], ad [outc][inpl]; each half carries its own BN scale, the shifts add up.  Whole
+    // 32 / 64-channel chunks on either side of the seam, else nothing is packed (-> false)
+    bool conv_dual(Layer &L, const std::string &label, const float *a3, const float *ad, int planes, int inpl, int outc,
+                   const std::vector<double> &s3, const std::vector<double> &b3, const std::vector<double> &sd_,
+                   const std::vector<double> &bd_, bool h16) {
+        const int CHK = h16 ? 64 : 32;
+        if (planes % CHK != 0 || inpl % CHK != 0) return false;
+        std::vector<double> shift(outc);
+        for (int o = 0; o < outc; ++o) shift[o] = b3[o] + bd_[o];
+        auto wt = [=, &s3, &sd_](int o, int k) -> double {
+            return k < planes ? (double)a3[(size_t)o * planes + k] * s3[o] : (double)ad[(size_t)o * inpl + (k - planes)] * sd_[o];
+        };
+        finish(L, label, planes + inpl, outc, 1, 1, planes + inpl, wt, nullptr, &shift, nullptr, h16);
+        L.Kreal = planes + inpl;
+        return true;
+    }
+
+    // ConvTranspose2d(k4,s2,p1) weight wd [c0][cout][4][4] (+ bias cb, BN scale / shift) as 4 sub-pixel 2x2 convs dl[a * 2 + b]:
+    // out[2q+a] takes ky = {3,1} (a=0, window starts at q-1) or {2,0} (a=1, window starts at q)
+    void deconv_phases(Layer *dl, const std::string &label, const float *wd, const float *cb, int c0, int cout,
+                       const std::vector<double> &sc, const std::vector<double> &sh, bool h16) {
+        static const int kmap[2][2] = {{3, 1}, {2, 0}};
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b) {
+                const int CH = h16 ? 64 : 32;
+                const bool sp = split && h16;          // (hi, lo) pairs: the K order walks 3 * c0 virtual channels
+                const int cv = sp ? 3 * c0 : c0;
+                auto wt = [=](int o, int k) -> float {   // K order (chunk, r, s, c % CH)
+                    const int chunk = k / (CH * 4), rem = k % (CH * 4), tap = rem / CH;
+                    const int ci = (chunk * CH + rem % CH) % c0, r = tap / 2, s = tap % 2;
+                    return wd[(((size_t)ci * cout + o) * 4 + kmap[a][r]) * 4 + kmap[b][s]];
+                };
+                std::vector<unsigned char> lo_plane;
+                if (sp) {
+                    lo_plane.assign(4 * cv, 0);
+                    for (int k = 0; k < 4 * cv; ++k) lo_plane[k] = ((k / (CH * 4)) * CH + (k % (CH * 4)) % CH) / c0 == 2;
+                }
+                Layer &l = dl[a * 2 + b];
+                finish(l, label + ".phase" + std::to_string(a * 2 + b), cv, cout, 2, 2, 4 * cv, wt,
+                       &sc, &sh, cb, h16, sp ? &lo_plane : nullptr);
+                l.Kreal = 4 * c0;
+                if (sp) l.plane = c0;
+            }
+    }
+
+    // the four phases' weight blocks back to back: one launch runs all of them (conv_igemm.hip, p.phases).  Not in the
+    // split mode, whose per-layer power-of-two weight scale differs between the phases.  all.w stays null where it is not made
+    void deconv_merge(const Layer *dl, Layer &all, size_t &stride, const std::string &label, bool h16) {
+        all = Layer();
+        if ((split && h16) || HMV_DEV_ENV("HMV_NO_PHASEMERGE") || rc != HMV_OK) return;
+        const Layer &d0 = dl[0];
+        const size_t elems = (size_t)d0.Cout_pad * d0.Kpad, bytes = elems * (h16 ? 2 : 4);
+        void *blk = nullptr;
+        hipError_t e = hipMalloc(&blk, 4 * bytes);
+        for (int i = 0; i < 4 && e == hipSuccess; ++i)
+            e = hipMemcpy(static_cast<char *>(blk) + i * bytes, dl[i].w, bytes, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) rc = h->fail(HMV_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
+        if (blk) h->dev_allocs.push_back(blk);
+        if (e == hipSuccess) {
+            all = d0;
+            all.label = label;
+            all.w = static_cast<float *>(blk);
+            stride = elems;
+        }
+    }
+
     float *vec(const std::string &key, int n) {
         const HostTensor *t = get(key, {n});
         return t ? upload(t->data) : nullptr;
@@ -810,17 +877,9 @@ int hmv_finalize_weights(hmv_handle h) {
                 const HostTensor *w3 = L.get(p + ".conv3.weight", {outc, planes, 1, 1}), *wd = L.get(p + ".downsample.0.weight", {outc, inpl, 1, 1});
                 std::vector<double> s3, b3, sd_, bd_;
                 if (w3 && wd && planes % CHK == 0 && inpl % CHK == 0 && L.bn_fold(p + ".bn3", outc, s3, b3) &&
-                    L.bn_fold(p + ".downsample.1", outc, sd_, bd_)) {
-                    const float *a3 = w3->data.data(), *ad = wd->data.data();
-                    std::vector<double> shift(outc);
-                    for (int o = 0; o < outc; ++o) shift[o] = b3[o] + bd_[o];
-                    auto wt = [=, &s3, &sd_](int o, int k) -> double {
-                        return k < planes ? (double)a3[(size_t)o * planes + k] * s3[o] : (double)ad[(size_t)o * inpl + (k - planes)] * sd_[o];
-                    };
-                    L.finish(b.c3ds, lab + ".conv3+downsample", planes + inpl, outc, 1, 1, planes + inpl, wt, nullptr, &shift, nullptr, h16);
-                    b.c3ds.Kreal = planes + inpl;
-                    b.fused_ds = true;
-                }
+                    L.bn_fold(p + ".downsample.1", outc, sd_, bd_))
+                    b.fused_ds = L.conv_dual(b.c3ds, lab + ".conv3+downsample", w3->data.data(), wd->data.data(), planes, inpl, outc,
+                                             s3, b3, sd_, bd_, h16);
             }
             inpl = outc;
             h->blocks[li].push_back(b);
@@ -839,48 +898,8 @@ int hmv_finalize_weights(hmv_handle h) {
         std::vector<double> sc, sh;
         const bool ok = L.bn_fold("pose_net.1", 128, sc, sh);
         if (w && cb && ok) {
-            static const int kmap[2][2] = {{3, 1}, {2, 0}};
-            for (int a = 0; a < 2; ++a)
-                for (int b = 0; b < 2; ++b) {
-                    const float *wd = w->data.data();
-                    const int CH = h16 ? 64 : 32;
-                    const bool sp = L.split && h16;          // (hi, lo) pairs: the K order walks 3 * c0 virtual channels
-                    const int cv = sp ? 3 * c0 : c0;
-                    auto wt = [=](int o, int k) -> float {   // K order (chunk, r, s, c % CH)
-                        const int chunk = k / (CH * 4), rem = k % (CH * 4), tap = rem / CH;
-                        const int ci = (chunk * CH + rem % CH) % c0, r = tap / 2, s = tap % 2;
-                        return wd[(((size_t)ci * 128 + o) * 4 + kmap[a][r]) * 4 + kmap[b][s]];
-                    };
-                    std::vector<unsigned char> lo_plane;
-                    if (sp) {
-                        lo_plane.assign(4 * cv, 0);
-                        for (int k = 0; k < 4 * cv; ++k) lo_plane[k] = ((k / (CH * 4)) * CH + (k % (CH * 4)) % CH) / c0 == 2;
-                    }
-                    Layer &dl = h->deconv[a * 2 + b];
-                    L.finish(dl, "pose_net.0.phase" + std::to_string(a * 2 + b), cv, 128, 2, 2, 4 * cv, wt,
-                             &sc, &sh, cb->data.data(), h16, sp ? &lo_plane : nullptr);
-                    dl.Kreal = 4 * c0;
-                    if (sp) dl.plane = c0;
-                }
-            // the four phases' weight blocks back to back: one launch runs all of them (conv_igemm.hip, p.phases).  Not in the
-            // split mode, whose per-layer power-of-two weight scale differs between the phases.
-            h->deconv_all = Layer();
-            if (!(L.split && h16) && !HMV_DEV_ENV("HMV_NO_PHASEMERGE") && L.rc == HMV_OK) {
-                const Layer &d0 = h->deconv[0];
-                const size_t elems = (size_t)d0.Cout_pad * d0.Kpad, bytes = elems * (h16 ? 2 : 4);
-                void *all = nullptr;
-                hipError_t e = hipMalloc(&all, 4 * bytes);
-                for (int i = 0; i < 4 && e == hipSuccess; ++i)
-                    e = hipMemcpy(static_cast<char *>(all) + i * bytes, h->deconv[i].w, bytes, hipMemcpyDeviceToDevice);
-                if (e != hipSuccess) L.rc = h->fail(HMV_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
-                if (all) h->dev_allocs.push_back(all);
-                if (e == hipSuccess) {
-                    h->deconv_all = d0;
-                    h->deconv_all.label = "pose_net.0";
-                    h->deconv_all.w = static_cast<float *>(all);
-                    h->deconv_stride = elems;
-                }
-            }
+            L.deconv_phases(h->deconv, "pose_net.0", w->data.data(), cb->data.data(), c0, 128, sc, sh, h16);
+            L.deconv_merge(h->deconv, h->deconv_all, h->deconv_stride, "pose_net.0", h16);
         }
         L.conv(h->pose1, "pose_net.3", "pose_net.3.weight", "pose_net.3.bias", "pose_net.4", 64, 128, 3, 3, 0, h16);
         L.conv(h->pose2, "pose_net.6", "pose_net.6.weight", "pose_net.6.bias", "", NJ, 64, 3, 3, 0, h16);
@@ -3448,6 +3467,200 @@ int hmv_op_conv2d_as(int32_t device, int32_t dtype, const float *in, int32_t N, 
     }
     return op_conv("hmv_op_conv2d_as", device, dtype, in, N, H, W, Cin, w_oihw, bias_host, Cout, R, S, stride, pad, residual, relu, out, false,
                    conv_rule(), kernel_name, stream, false, rd, Ho, Wo);
+}
+
+// One launch in a form that only a forward issues otherwise (include/handmv.h): the loader's packing (Loader::conv, conv_dual,
+// deconv_phases / deconv_merge), the Runner's launch path (conv, conv_slices, chains_into), guarded temporaries as in op_conv.  What the
+// engine would never issue is refused by the rules the engine itself asks (chains_into, conv_hs_supported, splitk_slices, launch_conv)
+int hmv_op_conv2d_form(int32_t device, hmv_conv_form_args *a, void *stream) {
+    static const char *who = "hmv_op_conv2d_form";
+    auto bad = [&](const std::string &why) { g_create_err = std::string(who) + ": " + why; return (int)HMV_ERR_ARG; };
+    if (!a) return bad("args is NULL");
+    if (a->struct_size != (int32_t)sizeof(hmv_conv_form_args)) return bad("struct_size does not match this library's hmv_conv_form_args");
+    a->kernel_name = nullptr;
+    const int form = a->form, dtype = a->dtype;
+    const bool dual = form & HMV_FORM_DUAL, chain = form & HMV_FORM_CHAIN, pool = form & HMV_FORM_POOL, phases = form & HMV_FORM_PHASES,
+               splitk = form & HMV_FORM_SPLITK, pair_out = form & HMV_FORM_PAIR_OUT;
+    if (form & ~63) return bad("form holds an unknown bit");
+    if (dtype != HMV_F32 && dtype != HMV_F16 && dtype != HMV_F32X3) return bad("dtype must be HMV_F32, HMV_F16 or HMV_F32X3");
+    const bool half = dtype != HMV_F32, x3 = dtype == HMV_F32X3;
+    if (!a->in || !a->w || !a->out || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->R <= 0 || a->S <= 0 ||
+        a->stride <= 0 || a->pad < 0)
+        return bad("null operand or non-positive size");
+    if ((long long)a->N * a->H * a->W > INT32_MAX / 8) return bad("N x H x W is too large");
+    if ((int)pool + (int)phases + (int)splitk + (int)(dual || chain) > 1) return bad("pool, phases, split-K and dual / chain do not meet in one launch");
+    if (pair_out && (!x3 || dual || chain || pool || splitk))
+        return bad("the pair-output epilogue belongs to HMV_F32X3 layers (plain or phases)");
+    if ((chain || pool) && dtype != HMV_F16) return bad("chain and pool are forms of HMV_F16");
+    if (splitk && dtype != HMV_F32) return bad("split-K is a form of HMV_F32");
+    if (dual && x3) return bad("the pair mode runs conv3 and downsample as two launches");
+    const int unit = half ? 8 : 4;
+    const int Cin = a->Cin, Cout = a->Cout;
+    const int ld_in = a->ld_in ? a->ld_in : Cin, ldc = a->ldc ? a->ldc : Cout, ldr = a->ldr ? a->ldr : Cout;
+    if (ld_in < Cin || ld_in % unit || ldc < Cout || ldc % 4 || (a->residual && (ldr < Cout || ldr % unit)) || (half && Cout % 4))
+        return bad("row strides: ld_in >= Cin, ldc >= Cout, ldr >= Cout, whole 16-byte units of the mode's storage (fp32 4, fp16-based 8 elements; ldc 4)");
+    int Ho = 0, Wo = 0, Hout = 0, Wout = 0;   // launch grid; rows of `out`
+    if (phases) {
+        if (a->R != 4 || a->S != 4 || a->stride != 2 || a->pad != 1 || a->residual || a->Ho || a->Wo || ld_in != Cin)
+            return bad("phases: a ConvTranspose2d(4, 2, 1) without residual (R = S = 4, stride 2, pad 1), dense input rows, its own map size");
+        if (Cin % (half ? 64 : 32)) return bad("phases: whole 32 (fp32) / 64 (fp16) channel chunks");
+        if (a->merged != 0 && a->merged != 1) return bad("merged must be 0 or 1");
+        if (a->merged && x3) return bad("the pair mode issues the four phase launches only");
+        if (x3 != pair_out) return bad("phases in HMV_F32X3 write pairs, as the engine's do");
+        Ho = a->H; Wo = a->W; Hout = 2 * a->H; Wout = 2 * a->W;
+    } else {
+        const int Ho_own = (a->H + 2 * a->pad - a->R) / a->stride + 1, Wo_own = (a->W + 2 * a->pad - a->S) / a->stride + 1;
+        if (Ho_own <= 0 || Wo_own <= 0 || a->Ho < 0 || a->Wo < 0 || a->Ho > Ho_own || a->Wo > Wo_own) return bad("Ho x Wo within the conv's own map");
+        Ho = a->Ho ? a->Ho : Ho_own; Wo = a->Wo ? a->Wo : Wo_own;
+        Hout = Ho; Wout = Wo;
+    }
+    if (dual) {
+        if (!a->in2 || !a->w2 || a->Cin2 <= 0 || a->H2 <= 0 || a->W2 <= 0 || a->stride2 <= 0) return bad("dual: in2, w2, Cin2, H2, W2, stride2");
+        const int ld2 = a->ld_in2 ? a->ld_in2 : a->Cin2;
+        if (a->R != 1 || a->S != 1 || a->stride != 1 || a->pad || a->residual || ld_in != Cin || ld2 < a->Cin2 || ld2 % unit)
+            return bad("dual: a 1x1 stride-1 conv without residual, ld_in = Cin, ld_in2 >= Cin2 in whole 16-byte units");
+        if ((long long)(Ho - 1) * a->stride2 > a->H2 - 1 || (long long)(Wo - 1) * a->stride2 > a->W2 - 1)
+            return bad("dual: the sampled pixels (ho * stride2, wo * stride2) lie outside the H2 x W2 map");
+    }
+    if (chain && (!a->next_w || !a->next_out || a->next_cout <= 0 || a->next_cout % 8)) return bad("chain: next_w, next_out, next_cout in whole 16-byte rows");
+    if (pool && (a->pool_h <= 0 || a->pool_w <= 0 || a->residual)) return bad("pool: pool_h, pool_w, no residual");
+    if (splitk && (a->slices < 1 || a->R != 1 || a->S != 1 || a->H != 1 || a->W != 1 || a->stride != 1 || a->pad || a->residual || a->relu || ld_in != Cin))
+        return bad("split-K: GEMM rows (H = W = 1, 1x1), slices >= 1, no residual, no activation");
+    auto rt = [&](int v, int &dst) { if (v == 1) dst = ROUTE_NEVER; else if (v == 2) dst = ROUTE_FORCE; return v >= 0 && v <= 2; };
+    ConvRoute route = conv_rule();
+    if (!rt(a->route_stream, route.stream) || !rt(a->route_gemm8, route.gemm8) || !rt(a->route_hs, route.hs) || !rt(a->route_x3k16, route.x3k16) ||
+        a->gemm8_persist < 0 || a->gemm8_persist > 2)
+        return bad("route_* and gemm8_persist must be 0 (the rule), 1 (never) or 2 (forced / wherever it exists)");
+    if (a->gemm8_persist) route.gemm8_persist = a->gemm8_persist == 2 ? 2 : 0;
+    if (hipSetDevice(device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return HMV_ERR_HIP; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+
+    // ---- packing: the loader's
+    hmv_engine eng;
+    eng.cfg.device = device;
+    eng.cfg.dtype = dtype;
+    Loader L{&eng};
+    L.split = x3;
+    Layer layer, next, dl[4], dall;
+    size_t dstride = 0;
+    const std::vector<double> one(Cout, 1.0), zero(Cout, 0.0);
+    std::vector<float> b1(Cout, 0.f);
+    if (a->bias) b1.assign(a->bias, a->bias + Cout);
+    if (phases) {
+        L.deconv_phases(dl, "op", a->w, b1.data(), Cin, Cout, one, zero, half);
+        if (a->merged) {
+            L.deconv_merge(dl, dall, dstride, "op", half);
+            if (L.rc == HMV_OK && !dall.w) { eng.err = "the merged phase layer was not made"; L.rc = HMV_ERR_ARG; }
+        }
+    } else if (dual) {
+        std::vector<double> bd1(b1.begin(), b1.end()), bd2(Cout, 0.0);
+        if (a->bias2) bd2.assign(a->bias2, a->bias2 + Cout);
+        if (!L.conv_dual(layer, "op+downsample", a->w, a->w2, Cin, a->Cin2, Cout, one, bd1, one, bd2, half))
+            return bad("dual: whole 32 (fp32) / 64 (fp16) channel chunks on either side of the seam");
+    } else {
+        HostTensor wt, bt;
+        wt.shape = {Cout, Cin, a->R, a->S};
+        wt.data.assign(a->w, a->w + (size_t)Cout * Cin * a->R * a->S);
+        eng.host["w"] = wt;
+        bt.shape = {Cout};
+        bt.data = b1;
+        if (a->bias) eng.host["b"] = bt;
+        L.conv(layer, "op", "w", a->bias ? "b" : "", "", Cout, Cin, a->R, a->S, ld_in != Cin ? ld_in : 0, half);
+    }
+    if (chain) {
+        HostTensor wt, bt;
+        wt.shape = {a->next_cout, Cout, 1, 1};
+        wt.data.assign(a->next_w, a->next_w + (size_t)a->next_cout * Cout);
+        eng.host["nw"] = wt;
+        bt.shape = {a->next_cout};
+        bt.data.assign(a->next_cout, 0.f);
+        if (a->next_bias) bt.data.assign(a->next_bias, a->next_bias + a->next_cout);
+        eng.host["nb"] = bt;
+        L.conv(next, "next", "nw", "nb", "", a->next_cout, Cout, 1, 1, 0, true);
+    }
+    if (splitk) eng.zero_bias = L.upload(std::vector<float>(4096, 0.f));
+    int rc = L.rc;
+
+    // ---- operands in the mode's storage format
+    const size_t rows_in = (size_t)a->N * a->H * a->W, rows_out = (size_t)a->N * Hout * Wout;
+    const void *x = a->in, *res = a->residual, *x2 = a->in2;
+    void *din = nullptr, *dres = nullptr, *din2 = nullptr;
+    const int ld2 = dual ? (a->ld_in2 ? a->ld_in2 : a->Cin2) : 0;
+    RangeWord rw;
+    hipError_t e = rc == HMV_OK ? rw.alloc() : hipSuccess;
+    eng.sat = rw.p;
+    if (rc == HMV_OK && e == hipSuccess && half) {
+        const int mode = x3 ? 2 : 1;
+        e = op_guarded_alloc(&din, rows_in * ld_in * 2 * mode, s);
+        if (e == hipSuccess) e = launch_rows_f32_to_half(a->in, din, rows_in, ld_in, mode, s, rw.p);
+        x = din;
+        if (e == hipSuccess && a->residual) {
+            e = op_guarded_alloc(&dres, rows_out * ldr * 2 * mode, s);
+            if (e == hipSuccess) e = launch_rows_f32_to_half(a->residual, dres, rows_out, ldr, mode, s, rw.p);
+            res = dres;
+        }
+        if (e == hipSuccess && dual) {
+            const size_t rows2 = (size_t)a->N * a->H2 * a->W2;
+            e = op_guarded_alloc(&din2, rows2 * ld2 * 2, s);
+            if (e == hipSuccess) e = launch_rows_f32_to_half(a->in2, din2, rows2, ld2, 1, s, rw.p);
+            x2 = din2;
+        }
+    }
+
+    // ---- the launch(es): the Runner's
+    const char *kname = nullptr;
+    if (rc == HMV_OK && e == hipSuccess) {
+        Arena dummy;
+        Runner Rn{&eng, s, false, HMV_OK, dummy};
+        Rn.kernel_name = &kname;
+        Rn.route = route;
+        const float *xf = static_cast<const float *>(x);
+        float *of = static_cast<float *>(a->out);
+        const int act = a->relu ? ACT_RELU : ACT_NONE;
+        const bool out16 = dtype == HMV_F16 || pair_out;
+        if (phases) {
+            if (a->merged)
+                Rn.conv(ConvCall(dall, xf, a->N, a->H, a->W, of, ldc, Ho, Wo).pad(1).act(act).f16(out16).all_phases(4, dstride));
+            else
+                for (int pa = 0; pa < 2; ++pa)
+                    for (int pb = 0; pb < 2; ++pb)
+                        Rn.conv(ConvCall(dl[pa * 2 + pb], xf, a->N, a->H, a->W, of, ldc, Ho, Wo).pad(1 - pa, 1 - pb).act(act).f16(out16).phase(pa, pb));
+        } else if (splitk) {
+            const int rule = Runner::splitk_slices(layer, a->N);
+            if (a->slices != 1 && a->slices != rule) {
+                eng.err = "the engine cuts this layer into " + std::to_string(rule) + " slice(s), or runs it whole";
+                Rn.rc = HMV_ERR_ARG;
+            } else {
+                Rn.conv_slices(layer, xf, a->N, a->slices, of, ldc);
+            }
+        } else {
+            ConvCall c(layer, xf, a->N, a->H, a->W, of, ldc, Ho, Wo);
+            c.s(a->stride).pad(a->pad).add(static_cast<const float *>(res), ldr).act(act).f16(out16);
+            if (dual) c.second(static_cast<const float *>(x2), Cin, a->H2, a->W2, ld2, a->stride2);
+            if (chain) {
+                Block nb;
+                nb.c1 = next;
+                if (!Rn.chains_into(c, &nb)) { eng.err = "the engine does not chain this launch into a 1x1 conv of next_cout channels"; Rn.rc = HMV_ERR_ARG; }
+                c.chain(next, static_cast<float *>(a->next_out));
+            }
+            if (pool) {
+                c.pooled(a->pool_h, a->pool_w);
+                if (!conv_hs_supported(Rn.params(c), route)) { eng.err = "the engine does not pool behind this launch (conv_hs_supported)"; Rn.rc = HMV_ERR_ARG; }
+            }
+            Rn.conv(c);
+        }
+        rc = Rn.rc;
+        if (rc == HMV_OK) e = hipStreamSynchronize(s);
+    }
+    op_guarded_free(din);
+    op_guarded_free(dres);
+    op_guarded_free(din2);
+    for (void *ptr : eng.dev_allocs) (void)hipFree(ptr);
+    if (rc != HMV_OK) { g_create_err = std::string(who) + ": " + eng.err; return rc; }
+    if (e != hipSuccess) { g_create_err = std::string(who) + ": " + hipGetErrorString(e); return HMV_ERR_HIP; }
+    a->kernel_name = kname;
+    if (rw.saturated()) { g_create_err = std::string(who) + ": " + kRangeMsg; return HMV_ERR_RANGE; }
+    return HMV_OK;
 }
 
 }  // extern "C"

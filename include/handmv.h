@@ -359,6 +359,51 @@ int hmv_op_conv2d_x3(int32_t device, const float *in, int32_t N, int32_t H, int3
                      int32_t pad, const float *residual, int32_t relu, float *out, int32_t kernel_sel, const char **kernel_name,
                      void *stream);
 
+/* One conv / GEMM launch in a LAUNCH FORM that only the engine's forward issues otherwise (op-level float64 tests: tests/test_gpu_conv_forms.py):
+ * packed by the loader members the model loader calls (identity BatchNorm folds), launched through the engine's own launch path, temporaries
+ * framed by guard bands.  `form` is a sum of HMV_FORM_* bits; 0 is the plain launch of hmv_op_conv2d_ex.  Every device operand is fp32 rows
+ * (converted to the mode's storage format first, pad columns included); weights and biases are on the host.
+ *   in        [N][H][W][ld_in]: ld_in = 0 or Cin, or more: the map then has ld_in physical channels of which Cin are real, as the loader's
+ *             padded layers have (the stem's 12 of 16); the extra channels meet zero weights and must be finite.  Dual: ld_in = Cin only.
+ *   residual  [N][Ho][Wo][ldr] or NULL; out [N][Ho][Wo][ldc]: fp32 rows in HMV_F32 and HMV_F32X3, fp16 rows in HMV_F16.  Columns from Cout on
+ *             are never written.  Ho, Wo = 0: the conv's own map; else its top-left Ho x Wo (hmv_op_conv2d_as).
+ *   route_*   per kernel family: 0 the launcher's rule, 1 never, 2 whenever the shape has an instantiation (ROUTE_FORCE);
+ *             gemm8_persist: 0 the rule, 1 never, 2 wherever the persistent form exists.
+ *   HMV_FORM_DUAL    1x1 only: out = act([in | in2(strided)] . [w ; w2] + bias + bias2), in2 [N][H2][W2][ld_in2] with Cin2 real channels
+ *                    sampled at (ho * stride2, wo * stride2), w2 [Cout][Cin2].  HMV_F32 / HMV_F16, whole 32 / 64-channel chunks per source.
+ *   HMV_FORM_CHAIN   HMV_F16: the launch also writes next_out [M][next_cout] fp16 = relu(conv1x1(fp16 out, next_w [next_cout][Cout]) +
+ *                    next_bias), where the engine's rule for its own launches (under the given route) chains; with or without DUAL.
+ *   HMV_FORM_POOL    HMV_F16: MaxPool2d(3, 2, 1) of the conv map in the same launch; out is the pooled map [N][pool_h][pool_w][ldc].
+ *   HMV_FORM_PHASES  w is a ConvTranspose2d(4, 2, 1) weight [Cin][Cout][4][4] (R = S = 4, stride 2, pad 1 describe it); out
+ *                    [N][2 H][2 W][ldc].  merged 0: four phase launches; 1: the one launch over the four weight blocks (not with pairs).
+ *   HMV_FORM_SPLITK  HMV_F32 1x1: `slices` partial products over the reduction columns [i Kpad / slices, (i + 1) Kpad / slices), without
+ *                    bias, into out [slices][M][ldc]; slices is 1 or what the engine's rule gives the layer.
+ *   HMV_FORM_PAIR_OUT  HMV_F32X3: out receives [hi ldc | lo ldc] fp16 rows; HMV_ERR_RANGE when the range word was raised.
+ * kernel_name receives the family of the (last) launch.  HMV_ERR_ARG, naming the entry, before any launch for a NULL args, another
+ * struct_size, a NULL or non-positive operand, a form or stride the engine never issues; a launch the launcher refuses is HMV_ERR_HIP. */
+enum { HMV_FORM_DUAL = 1, HMV_FORM_CHAIN = 2, HMV_FORM_POOL = 4, HMV_FORM_PHASES = 8, HMV_FORM_SPLITK = 16, HMV_FORM_PAIR_OUT = 32 };
+typedef struct hmv_conv_form_args {
+    int32_t struct_size;   /* sizeof(hmv_conv_form_args) */
+    int32_t dtype, form;
+    int32_t N, H, W, Cin, Cout, R, S, stride, pad, relu;
+    int32_t Ho, Wo;
+    int32_t ld_in, ldc, ldr, ld_in2;
+    int32_t route_stream, route_gemm8, route_hs, route_x3k16, gemm8_persist;
+    int32_t Cin2, H2, W2, stride2;   /* dual */
+    int32_t next_cout;               /* chain */
+    int32_t pool_h, pool_w;          /* pool */
+    int32_t merged;                  /* phases */
+    int32_t slices;                  /* split-K */
+    int32_t reserved;
+    const float *in, *residual, *in2;           /* device */
+    const float *w, *bias, *w2, *bias2;         /* host */
+    const float *next_w, *next_bias;            /* host */
+    void *out, *next_out;                       /* device */
+    const char *kernel_name;                    /* out */
+} hmv_conv_form_args;
+
+int hmv_op_conv2d_form(int32_t device, hmv_conv_form_args *args, void *stream);
+
 /* The up-sampling terms of an HRNet fuse layer (hrnet.py:194-212) through hr_fuse.hip alone (op-level parity tests; the fp16 instantiation
  * needs row strides of whole 16-byte units: ldc % 8 == 0, source ld % 8 == 0):
  *   out = act(base + sum_s Upsample_{2^shift_s, nearest}(W_s x_s + b_s)),   terms added in the order given (1 <= nsrc <= 3, 1 <= shift <= 3).

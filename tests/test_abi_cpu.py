@@ -65,6 +65,23 @@ def test_config_struct_matches_header_and_is_validated():
     assert b"odd" in lib.hmv_last_error(None)
 
 
+def test_conv_form_struct_matches_header_and_is_validated():
+    """hmv_conv_form_args: 34 int32 fields, 11 pointers and the kernel name out; a NULL args or another struct_size is refused before any HIP call."""
+    lib = _lib.load()
+    assert ctypes.sizeof(_lib.HmvConvFormArgs) == 34 * 4 + 12 * ctypes.sizeof(ctypes.c_void_p)
+    header = open(os.path.join(ROOT, "include", "handmv.h")).read()
+    body = re.search(r"typedef struct hmv_conv_form_args \{(.*?)\} hmv_conv_form_args;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n.strip(" *") for decl in body.split(";") if decl.strip() for n in decl.split(None, 2 if decl.strip().startswith("const") else 1)[-1].split(",")]
+    assert names == [("in" if n == "in_" else n) for n, _ in _lib.HmvConvFormArgs._fields_], names
+    a = _lib.HmvConvFormArgs()
+    a.struct_size = 12
+    assert lib.hmv_op_conv2d_form(0, ctypes.byref(a), None) == 1 and b"hmv_op_conv2d_form: struct_size" in lib.hmv_last_error(None)
+    assert lib.hmv_op_conv2d_form(0, None, None) == 1 and b"hmv_op_conv2d_form" in lib.hmv_last_error(None)
+    for k, v in (("HMV_FORM_DUAL", 1), ("HMV_FORM_CHAIN", 2), ("HMV_FORM_POOL", 4), ("HMV_FORM_PHASES", 8), ("HMV_FORM_SPLITK", 16), ("HMV_FORM_PAIR_OUT", 32)):
+        assert getattr(_lib, k) == v and re.search(rf"\b{k} = {v}\b", header), k
+
+
 def test_product_package_never_imports_the_oracle():
     """The oracle is test infrastructure: nothing under handmvnet_amd/ may import or load it."""
     pkg = os.path.join(ROOT, "handmvnet_amd")

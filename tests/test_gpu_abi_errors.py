@@ -258,3 +258,68 @@ def test_fused_tail_op_entries_refuse_bad_arguments():
     assert lib.hmv_op_cheb_fused(0, ctypes.byref(cheb()), None) == OK, lib.hmv_last_error(None)
     torch.cuda.synchronize()
     assert not out[:21 * 32].any()      # scratch and out alias here: zeros either way
+
+
+def test_conv_form_entry_refuses_what_the_engine_never_issues():
+    """hmv_op_conv2d_form (tests/test_gpu_conv_forms.py): a non-zero code with the entry's name in hmv_last_error(NULL) and the outputs
+    untouched -- HMV_ERR_ARG before any launch for a NULL args, another struct_size, null operands, forms that do not meet, a second
+    source sampled outside its map, a chain or a pool the engine's own rule (conv_stream_chain_ok, conv_hs_supported) would not issue, a
+    slice count splitk_slices never gives -- and the good call runs."""
+    import numpy as np
+    from handmvnet_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    ARG, OK = 1, 0
+    N, H, W = 1, 4, 4
+    x = torch.zeros(N * H * W * 64, device=dev)
+    x2 = torch.zeros(N * 8 * 8 * 64, device=dev)
+    out = torch.full((N * 8 * 8 * 256,), 7.0, device=dev)
+    nxt = torch.full((N * H * W * 128,), 7.0, device=dev)
+    w = np.zeros(256 * 64 * 16, dtype=np.float32)
+    wp = w.ctypes.data_as(ctypes.c_void_p)
+
+    def form(**over):
+        a = _lib.HmvConvFormArgs()
+        a.struct_size = ctypes.sizeof(_lib.HmvConvFormArgs)
+        a.dtype, a.form, a.N, a.H, a.W, a.Cin, a.Cout, a.R, a.S, a.stride, a.pad, a.relu = 1, _lib.HMV_FORM_DUAL, N, H, W, 64, 256, 1, 1, 1, 0, 1
+        a.in_, a.out, a.w, a.in2, a.w2 = x.data_ptr(), out.data_ptr(), wp, x2.data_ptr(), wp
+        a.Cin2, a.H2, a.W2, a.stride2 = 64, 7, 7, 2
+        for k, v in over.items():
+            setattr(a, k, v)
+        return a
+
+    F = _lib
+    res = x2.data_ptr()
+    bad = [({"struct_size": 8}, ARG), ({"in_": None}, ARG), ({"w": None}, ARG), ({"out": None}, ARG), ({"N": 0}, ARG), ({"dtype": 3}, ARG),
+           ({"form": 64}, ARG), ({"in2": None}, ARG), ({"w2": None}, ARG), ({"stride2": 0}, ARG),
+           ({"H2": 6}, ARG),                                    # row (H - 1) * stride2 = 6 lies outside a 6-row map
+           ({"W2": 4, "stride2": 2}, ARG),
+           ({"ld_in2": 60}, ARG), ({"ld_in": 72}, ARG),        # the first source of a dual launch has no stride of its own
+           ({"dtype": 2}, ARG),                                 # the pair mode never fuses the downsample
+           ({"Cin": 32, "dtype": 1}, ARG),                      # half a 64-channel chunk before the seam
+           ({"form": F.HMV_FORM_DUAL | F.HMV_FORM_POOL}, ARG), ({"form": F.HMV_FORM_DUAL | F.HMV_FORM_SPLITK, "dtype": 0}, ARG),
+           ({"form": F.HMV_FORM_PAIR_OUT}, ARG),                # pairs out of an fp16 layer
+           ({"form": F.HMV_FORM_CHAIN, "residual": res, "next_w": wp, "next_out": nxt.data_ptr(), "next_cout": 96}, ARG),   # no 96-channel chain
+           ({"form": F.HMV_FORM_CHAIN, "next_w": wp, "next_out": nxt.data_ptr(), "next_cout": 64}, ARG),    # conv3 without a residual
+           ({"form": F.HMV_FORM_CHAIN, "dtype": 0, "residual": res, "next_w": wp, "next_out": nxt.data_ptr(), "next_cout": 64}, ARG),
+           ({"form": F.HMV_FORM_POOL, "pool_h": 2, "pool_w": 2}, ARG),                                      # a 1x1 conv is no stem
+           ({"form": F.HMV_FORM_POOL, "Cin": 12, "ld_in": 16, "Cout": 64, "R": 4, "S": 4, "pad": 2, "Ho": 4, "Wo": 4, "pool_h": 3, "pool_w": 2}, ARG),
+           ({"form": F.HMV_FORM_SPLITK, "dtype": 0, "H": 1, "W": 1, "relu": 0, "slices": 4}, ARG),         # K = 64: the rule never slices it
+           ({"form": F.HMV_FORM_SPLITK, "dtype": 0, "relu": 0, "slices": 1}, ARG),                          # a map, not GEMM rows
+           ({"form": F.HMV_FORM_PHASES, "R": 4, "S": 4, "stride": 2, "pad": 1, "merged": 2}, ARG),
+           ({"form": F.HMV_FORM_PHASES, "R": 3, "S": 3, "stride": 2, "pad": 1}, ARG),
+           ({"form": F.HMV_FORM_PHASES, "dtype": 2, "R": 4, "S": 4, "stride": 2, "pad": 1, "merged": 1}, ARG),   # the pair mode never merges
+           ({"route_stream": 3}, ARG), ({"gemm8_persist": -1}, ARG)]
+    for over, want in bad:
+        rc = lib.hmv_op_conv2d_form(0, ctypes.byref(form(**over)), None)
+        assert rc == want, (over, rc, lib.hmv_last_error(None))
+        assert b"hmv_op_conv2d_form" in lib.hmv_last_error(None), (over, lib.hmv_last_error(None))
+    assert lib.hmv_op_conv2d_form(0, None, None) == ARG and b"hmv_op_conv2d_form" in lib.hmv_last_error(None)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((nxt == 7.0).all())
+    good = form()
+    assert lib.hmv_op_conv2d_form(0, ctypes.byref(good), None) == OK, lib.hmv_last_error(None)
+    assert good.kernel_name and good.kernel_name.startswith(b"conv_")
+    torch.cuda.synchronize()
+    o = out.view(torch.float16)
+    assert not o[:N * H * W * 256].any() and bool((out[N * H * W * 128:] == 7.0).all())   # zeros in, zeros out (fp16 rows); nothing beyond

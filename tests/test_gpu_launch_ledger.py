@@ -11,9 +11,12 @@ holds a build to it three ways:
   2. every element -- each distinct (kernel, layer shape, epilogue) of the headline workloads (cfg3, hr40) runs once through the
                      op hooks at the full launch size (256 frames), the hook must report the ledger's kernel name, and ALL
                      output elements are compared with a float64 reference computed on the device (unfold + matmul);
-  3. launch forms that have no op hook (dual source, chain, +maxpool, 4-phase transposed conv, split-K, pair-output epilogue)
-     are listed in ENGINE_ONLY_FORMS with the test that pins each; a ledger record that is neither checked at op level nor of
-     one of those forms fails test_every_ledger_record_is_checked.
+  3. launch forms that only a forward issues (dual source, chain, +maxpool, 4-phase transposed conv, split-K, pair-output
+     epilogue) have a hook of their own, hmv_op_conv2d_form, and are held to float64 one launch at a time, at small and ragged
+     sizes, by tests/test_gpu_conv_forms.py; the sweep below does not take them.  ENGINE_ONLY_FORMS lists each with the full-size
+     test that still pins what depends on the batch size (which kernel the launcher picks there, and that its bits are the small
+     launch's) and the op-level test beside it; a ledger record that is neither checked at op level nor of one of those forms
+     fails test_every_ledger_record_is_checked.
 """
 import ctypes
 import json
@@ -518,17 +521,18 @@ SWEEP_WORKLOADS = ("cfg3", "hr40")
 BARS = {"f32": 4e-6, "f32x3": 5e-6, "f16": 3e-3}   # tests/test_gpu_parity.py::test_conv_kernel_random_shapes: max |got - ref| / max |ref|
 F16_RAN = 1e-6                                      # an fp16-path result closer than this to the UNROUNDED reference did not run in fp16
 
-# Launch forms that only the engine can issue (no op hook takes them): (form, how a record shows it, the test that pins the form at a
-# size that reaches the ledger's kernel).  A record may be exempted from the op-level sweep only through a row of this table.
+# Launch forms that only a forward issues: (form, how a record shows it, the full-size test that pins the form at a size that reaches the
+# ledger's kernel; the op-level float64 test of the form through hmv_op_conv2d_form).  A record may be exempted from the op-level sweep
+# only through a row of this table.
 ENGINE_ONLY_FORMS = [
     # (B = 32: all 32 samples' feat0 bit-equal to their solo runs, whose dual launches are OTHER kernels -- which
     # test_solo_dual_launches_are_other_kernels_than_the_batch's below asserts --; sample 0 against the f64 oracle)
-    ("dual source", "label a+downsample", "test_gpu_parity.py::test_full_size_properties"),
-    ("chain +1x1", "label a+<next block's conv1>", "test_gpu_parity.py::test_chained_launches_give_the_bits_of_one_launch_per_conv"),
-    ("+maxpool", "label stem+maxpool", "test_gpu_parity.py::test_chained_launches_give_the_bits_of_one_launch_per_conv"),
-    ("4-phase transposed conv", "label pose_net.0 / pose_net.0.phaseK of ResNet-18/34", "test_gpu_parity.py::test_cfg2_full_batch_against_the_oracle"),
-    ("split-K", "fp32 1x1 layer with K >= 1024 behind a label .to_out / sample_nets.N", "test_gpu_parity.py::test_fused_tail_kernels_match_the_unfused_launches"),
-    ("pair-output epilogue", "label .qkv in the fp16-kernel modes", "test_gpu_parity.py::test_full_size_properties"),
+    ("dual source", "label a+downsample", "test_gpu_parity.py::test_full_size_properties; test_gpu_conv_forms.py::test_dual"),
+    ("chain +1x1", "label a+<next block's conv1>", "test_gpu_parity.py::test_chained_launches_give_the_bits_of_one_launch_per_conv; test_gpu_conv_forms.py::test_chain"),
+    ("+maxpool", "label stem+maxpool", "test_gpu_parity.py::test_chained_launches_give_the_bits_of_one_launch_per_conv; test_gpu_conv_forms.py::test_pool"),
+    ("4-phase transposed conv", "label pose_net.0 / pose_net.0.phaseK of ResNet-18/34", "test_gpu_parity.py::test_cfg2_full_batch_against_the_oracle; test_gpu_conv_forms.py::test_phases"),
+    ("split-K", "fp32 1x1 layer with K >= 1024 behind a label .to_out / sample_nets.N", "test_gpu_parity.py::test_fused_tail_kernels_match_the_unfused_launches; test_gpu_conv_forms.py::test_splitk"),
+    ("pair-output epilogue", "label .qkv in the fp16-kernel modes", "test_gpu_parity.py::test_full_size_properties; test_gpu_conv_forms.py::test_pair_out"),
 ]
 
 
@@ -604,9 +608,10 @@ def test_every_ledger_record_is_checked():
     """Each record of the headline workloads is either reproduced by an op-hook run of the sweep below or shows the marker of a row of
     ENGINE_ONLY_FORMS -- so a new launch form cannot arrive untested -- and every row names a test that exists."""
     import importlib
-    for _, _, where in ENGINE_ONLY_FORMS:
-        mod, name = where.split("::")
-        assert hasattr(importlib.import_module(mod[:-3]), name), where
+    for _, _, wheres in ENGINE_ONLY_FORMS:
+        for where in wheres.split("; "):
+            mod, name = where.split("::")
+            assert hasattr(importlib.import_module(mod[:-3]), name), where
     forms = {f for f, _, _ in ENGINE_ONLY_FORMS}
     used = {}
     for wl in SWEEP_WORKLOADS:

@@ -25,7 +25,8 @@ SYMBOLS = ["hmv_create", "hmv_set_tensor", "hmv_finalize_weights", "hmv_workspac
            "hmv_op_sample_gather", "hmv_op_sample_blend", "hmv_op_tokens_finalize", "hmv_op_layernorm", "hmv_op_splitk_reduce",
            "hmv_op_splitk_layernorm", "hmv_op_add_pe", "hmv_op_cheb_mix", "hmv_eval_absolute_doubles", "hmv_eval_absolute_add",
            "hmv_op_reproject_crop_boxes", "hmv_op_ff_block", "hmv_op_cheb_fused", "hmv_mano_pack_bytes", "hmv_op_mano_pack",
-           "hmv_op_mano_skin", "hmv_op_attention_pairs", "hmv_op_conv2d_form"]
+           "hmv_op_mano_skin", "hmv_op_attention_pairs", "hmv_op_conv2d_form", "hmv_eval_vertices_doubles",
+           "hmv_eval_vertices_scratch_bytes", "hmv_eval_vertices_add"]
 
 HMV_OK = 0
 HMV_ERR_ARG = 1
@@ -80,6 +81,16 @@ class HmvEvalAbsoluteArgs(ctypes.Structure):
                 ("pred_joints_cam", ctypes.c_void_p), ("joints_tri", ctypes.c_void_p), ("tri_status", ctypes.c_void_p),
                 ("gt_joints_cam", ctypes.c_void_p), ("gt_root", ctypes.c_void_p), ("reproj_err", ctypes.c_void_p),
                 ("inliers", ctypes.c_void_p), ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t)]
+
+
+class HmvEvalVerticesArgs(ctypes.Structure):
+    """hmv_eval_vertices_args of include/handmv.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("B", ctypes.c_int32), ("n_verts", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("thr_min", ctypes.c_float), ("thr_max", ctypes.c_float), ("unit_div", ctypes.c_float),
+                ("pred_vertices", ctypes.c_void_p), ("gt_vertices", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("state_doubles", ctypes.c_size_t), ("scratch", ctypes.c_void_p),
+                ("scratch_bytes", ctypes.c_size_t), ("records", ctypes.c_void_p), ("record_capacity", ctypes.c_int64),
+                ("record_base", ctypes.c_int64)]
 
 
 class HmvSeqEvalArgs(ctypes.Structure):
@@ -310,6 +321,12 @@ def load() -> ctypes.CDLL:
     lib.hmv_eval_absolute_doubles.restype = ctypes.c_size_t
     lib.hmv_eval_absolute_add.argtypes = [ci, ctypes.POINTER(HmvEvalAbsoluteArgs), vp]
     lib.hmv_eval_absolute_add.restype = ctypes.c_int
+    lib.hmv_eval_vertices_doubles.argtypes = [ci, ci]
+    lib.hmv_eval_vertices_doubles.restype = ctypes.c_size_t
+    lib.hmv_eval_vertices_scratch_bytes.argtypes = [ci, ci, ci]
+    lib.hmv_eval_vertices_scratch_bytes.restype = ctypes.c_size_t
+    lib.hmv_eval_vertices_add.argtypes = [ci, ctypes.POINTER(HmvEvalVerticesArgs), vp]
+    lib.hmv_eval_vertices_add.restype = ctypes.c_int
     lib.hmv_forward_frames_views.argtypes = [vp, ci, ctypes.POINTER(ci), fp, ci, ci, fp, fp, ctypes.POINTER(ctypes.c_float),
                                              ctypes.POINTER(ctypes.c_float), fp, fp, fp, fp, fp, vp]
     lib.hmv_forward_frames_views.restype = ctypes.c_int

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libhandmv.so")
-SOURCES = ["conv_igemm.hip", "conv_stream.hip", "conv_gemm8.hip", "conv_hs.hip", "conv_ht.hip", "conv_m16.hip", "gemm_x3.hip", "conv_rds.hip", "misc_kernels.hip", "attention_probs.hip", "fusion_kernels.hip", "hr_fuse.hip", "engine.hip", "metrics.hip", "losses.hip", "eval_epoch.hip", "eval_breakdown.hip", "eval_absolute.hip", "track.hip", "seq_eval.hip", "hand_ik.hip", "pose_consensus.hip", "triangulate.hip", "confidence.hip", "mano_skin.hip"]
+SOURCES = ["conv_igemm.hip", "conv_stream.hip", "conv_gemm8.hip", "conv_hs.hip", "conv_ht.hip", "conv_m16.hip", "gemm_x3.hip", "conv_rds.hip", "misc_kernels.hip", "attention_probs.hip", "fusion_kernels.hip", "hr_fuse.hip", "engine.hip", "metrics.hip", "losses.hip", "eval_epoch.hip", "eval_breakdown.hip", "eval_absolute.hip", "eval_vertices.hip", "track.hip", "seq_eval.hip", "hand_ik.hip", "pose_consensus.hip", "triangulate.hip", "confidence.hip", "mano_skin.hip"]
 HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "pose_rows.h"), os.path.join(CSRC, "attention_mfma_body.inc"),
            os.path.join(CSRC, "attention_x3_body.inc"), os.path.join(CSRC, "tokens_finalize_body.inc"),
            os.path.join(CSRC, "frames_to_input_body.inc"), os.path.join(os.path.dirname(HERE), "include", "handmv.h")]

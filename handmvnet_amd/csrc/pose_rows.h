@@ -1,6 +1,6 @@
 // Device code shared by the evaluation kernels (metrics.hip: one step's metrics; eval_epoch.hip: an epoch's running sums;
-// eval_breakdown.hip: the same by joint, camera and sample; losses.hip: the step's losses; hand_ik.hip uses svd3, pose_consensus.hip
-// solve4_xyz), as functions, so that they cannot drift apart: the workgroup reduction, the 3x3 SVD, the 4x4 cofactor solve of the
+// eval_breakdown.hip: the same by joint, camera and sample; eval_vertices.hip: the mesh block, one workgroup per mesh; losses.hip: the
+// step's losses; hand_ik.hip uses svd3, pose_consensus.hip solve4_xyz), as functions, so that they cannot drift apart: the workgroup reduction, the 3x3 SVD, the 4x4 cofactor solve of the
 // camera-to-camera transforms, the present-view count of a ragged sample, and the per-row
 // arithmetic of models/metrics.py -- thresholds as torch.linspace builds them, the fp32 joint distance, its PCK bin, the similarity
 // alignment of one pose.  The arithmetic that decides a comparison (joint distance vs threshold) is fp32 like the reference's and
@@ -284,26 +284,47 @@ __device__ __forceinline__ void pose_moments(const float* p, const float* g, int
     }
 }
 
-// From the moments and the U, V of svd3(m.K, ...): point(j, y, dist) for every point j, with its transformed coordinates y[3] and the
-// distance to g's point that remains.
-template <typename F>
-__device__ __forceinline__ void pose_aligned_points(const float* p, const float* g, int n_pts, const PoseMoments& m, const double U[3][3],
-                                                    const double V[3][3], F&& point) {
+// From the moments and the U, V of svd3(m.K, ...): the rotation R, the scale and the translation tr of y = scale * R x + tr.
+// (pose_aligned_points below, one lane per pose; eval_vertices.hip, where one lane computes them for a workgroup's mesh.)
+__device__ __forceinline__ void pose_similarity(const PoseMoments& m, const double U[3][3], const double V[3][3], double R[3][3],
+                                                double& scale, double tr[3]) {
     // Z = diag(1, 1, sign(det(U V^T)));  R = V Z U^T
     double UVt[3][3];
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) UVt[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + U[a][2] * V[b][2];
     const double dd = det3(UVt);
     const double z = dd > 0 ? 1.0 : (dd < 0 ? -1.0 : 0.0);
-    double R[3][3];
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) R[a][b] = V[a][0] * U[b][0] + V[a][1] * U[b][1] + z * V[a][2] * U[b][2];
     double trace = 0.0;   // trace(R K)
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) trace += R[a][b] * m.K[b][a];
-    const double scale = trace / m.var1;
-    double tr[3];
+    scale = trace / m.var1;
     for (int a = 0; a < 3; ++a) tr[a] = m.mu2[a] - scale * (R[a][0] * m.mu1[0] + R[a][1] * m.mu1[1] + R[a][2] * m.mu1[2]);
+}
+
+// The distance that remains between the transformed point y = scale * R p + tr and g, and y itself: the per-point arithmetic of
+// pose_aligned_points for a caller that spreads the points over lanes (eval_vertices.hip).  pose_aligned_points keeps its own loop:
+// routed through this function, pose_metrics_kernel and eval_breakdown_kernel come out in another instruction schedule; as it is,
+// the device code of the three files that use it is what it was before the split, instruction for instruction (tools/isa_diff.py).
+__device__ __forceinline__ double pose_aligned_distance(const float* p, const float* g, const double R[3][3], double scale,
+                                                        const double tr[3], double y[3]) {
+    double e2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        y[a] = scale * (R[a][0] * p[0] + R[a][1] * p[1] + R[a][2] * p[2]) + tr[a];
+        const double e = y[a] - (double)g[a];
+        e2 += e * e;
+    }
+    return sqrt(e2);
+}
+
+// From the moments and the U, V of svd3(m.K, ...): point(j, y, dist) for every point j, with its transformed coordinates y[3] and the
+// distance to g's point that remains.
+template <typename F>
+__device__ __forceinline__ void pose_aligned_points(const float* p, const float* g, int n_pts, const PoseMoments& m, const double U[3][3],
+                                                    const double V[3][3], F&& point) {
+    double R[3][3], scale, tr[3];
+    pose_similarity(m, U, V, R, scale, tr);
     for (int j = 0; j < n_pts; ++j) {
         double y[3], e2 = 0.0;
         for (int a = 0; a < 3; ++a) {

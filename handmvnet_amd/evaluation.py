@@ -35,6 +35,14 @@ root joint was triangulated; ``lost`` counts the others.  With no sample lost, `
 epoch value above of what ``test_step`` logs with ``absolute_root = "triangulate"``.  Labels must be in the frame
 ``forward_absolute`` reports in: view 0, or a ragged sample's first present view.
 
+Vertices.  ``EpochEvaluator(model, mode, vertices=True)`` takes every step's ``joints_cam`` to its MANO mesh
+(``model.joints_to_vertices``: ``hmv_op_hand_ik`` and the skin launch) and runs one more accumulation entry
+(``hmv_eval_vertices_add``) into a fourth slice of the same tensor: the mesh block of ``_calculate_mpjpe`` -- ``{mode}_mpvpe``,
+``{mode}_pa_mpvpe``, ``{mode}_pck_v``, ``{mode}_auc_v``, ``{mode}_norm_auc_v`` -- and the error of every vertex
+(``finish_vertices``).  All five are linear in the vertex rows, so they are the values on the pooled split.  A sample whose IK or
+skin status is non-zero is skipped and counted (``vertex_skipped``); the status words are combined on the device.  Its state has
+the same bits however the split is cut into batches.
+
 Lightning is not a dependency of this package, so the ``_epoch`` / ``_step`` suffixes its loggers add to a key logged with both
 ``on_step`` and ``on_epoch`` cannot be pinned and are not reproduced: the keys are the names the reference passes to ``self.log``.
 """
@@ -54,6 +62,7 @@ STEPS = 20       # thresholds of the PCK curve (handmvnet.py:359-363)
 _SCALARS = 14    # state[0 .. 14): counts and sums, then the steps + 1 histogram bins (include/handmv.h: "State layout")
 NJ = 21
 _HEADER = 4      # breakdown state[0 .. 4): samples, steps added, V, S (include/handmv.h: "evaluation breakdown")
+_VERT_SCALARS = 8  # vertex state[0 .. 8): counts and sums, then H[steps + 1], PV[Nv], PVA[Nv] (include/handmv.h: "vertex evaluation")
 _ABS_FIXED = 155 # absolute state[0 .. 155): 8 header slots, W, T, TN, S; then R[V], RN[V], H[V + 1] (include/handmv.h: "absolute evaluation")
 RECORD_KEYS = ("mpjpe", "pa_mpjpe", "mpjpe2d", "views", "mpjpe2d_per_camera")
 
@@ -201,6 +210,41 @@ def finish_absolute(state, mode: str) -> dict:
             f"{mode}_tri_inlier_hist": hist.astype(np.int64).tolist(), "located": int(s[3]), "lost": int(s[0] - s[3])}
 
 
+def vertices_doubles(n_verts: int, steps: int) -> int:
+    """hmv_eval_vertices_doubles on the host: 8 scalars, H[steps + 1], PV[n_verts], PVA[n_verts]."""
+    return _VERT_SCALARS + steps + 1 + 2 * n_verts
+
+
+def finish_vertices(state, thr_min: float, thr_max: float, steps: int, mode: str) -> dict:
+    """The mesh numbers from a vertex state on the host (include/handmv.h: "vertex evaluation"); n_verts comes from its length.
+    {mode}_mpvpe and {mode}_pa_mpvpe in millimetres ([6] / [5] * 1000, [7] / [5] * 1000), {mode}_pck_v (list), {mode}_auc_v and
+    {mode}_norm_auc_v from the pooled histogram with finish_state's fp32 trapezoid, vertex_err and vertex_pa_err [n_verts] in
+    millimetres (numpy), vertex_samples, vertex_skipped.  When every sample was skipped the means are None and the curve is NaN.
+    Raises ValueError for an empty epoch, a length that is no state's, or a header that names another n_verts or steps."""
+    s = np.asarray(state, dtype=np.float64).reshape(-1)
+    nv, rest = divmod(s.size - vertices_doubles(0, steps), 2)
+    if nv < 1 or nv > 4096 or rest:
+        raise ValueError(f"{s.size} elements are not a vertex state with {steps} thresholds (8 + (steps + 1) + 2 n_verts, n_verts in 1 .. 4096)")
+    if not s[1] > 0:
+        raise ValueError("empty epoch: no step was added")
+    if s[2] != nv or s[3] != steps:
+        raise ValueError(f"this vertex state was accumulated with n_verts = {s[2]:g}, steps = {s[3]:g}, not n_verts = {nv}, steps = {steps}")
+    at = _VERT_SCALARS + steps + 1
+    thr = torch.linspace(thr_min, thr_max, steps).numpy()                       # fp32, as metrics.py:106 builds them
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pck = np.cumsum(s[_VERT_SCALARS:_VERT_SCALARS + steps]).astype(np.float32) / np.float32(s[5])
+    auc, one = np.float32(0), np.float32(0)                                      # fp32 trapezoid (metrics.py:114-121)
+    for i in range(1, steps):
+        dx = thr[i] - thr[i - 1]
+        auc += dx * (pck[i] + pck[i - 1]) * np.float32(0.5)
+        one += dx
+    some = s[0] > 0
+    return {f"{mode}_mpvpe": float(s[6] / s[5] * 1000) if some else None, f"{mode}_pa_mpvpe": float(s[7] / s[5] * 1000) if some else None,
+            f"{mode}_pck_v": pck.tolist(), f"{mode}_auc_v": float(auc), f"{mode}_norm_auc_v": float(auc / one) if steps > 1 else float("nan"),
+            "vertex_err": s[at:at + nv] / s[0] * 1000 if some else None, "vertex_pa_err": s[at + nv:] / s[0] * 1000 if some else None,
+            "vertex_samples": int(s[0]), "vertex_skipped": int(s[4])}
+
+
 def _absolute_options(absolute) -> Optional[dict]:
     """None: the absolute path is off.  A dict of forward_absolute's keywords otherwise; an empty one stands for True."""
     if absolute is False:
@@ -242,10 +286,22 @@ class EpochEvaluator:
     slice of that ONE tensor.  Every batch needs inputs["root_joint"] and cam_params["extrinsic"], with the labels in the frame
     forward_absolute reports in: view 0, or a ragged sample's first present view (the convention of test_step's w_mpjpe).  The
     absolute means are over the located samples; see finish_absolute.  Every step must have the V of the first (ValueError
-    otherwise, before anything is launched); having compared here, add() passes v_checked, so that entry reads nothing back either."""
+    otherwise, before anything is launched); having compared here, add() passes v_checked, so that entry reads nothing back either.
 
-    def __init__(self, model, mode: str = "test", breakdown: bool = False, records: int = 0, absolute=False):
+    vertices=True: add() runs model.joints_to_vertices (an ik.JointsToVertices) on out["joints_cam"] * 1000 and ONE
+    hmv_eval_vertices_add behind what it runs today, against inputs["vertices"] [B, Nv, 3] in millimetres with unit_div = 1000;
+    compute() adds finish_vertices' keys.  The status it passes is j2v.last_status OR, for a mano.ManoSkin, mano_layer.last_status,
+    combined on the device.  The vertex state is one more slice of that ONE tensor, sized from the Nv of the first step; a later
+    step with another Nv, a model without joints_to_vertices or a batch without inputs["vertices"] raises ValueError before anything
+    is launched.  The mesh is made before the step's accumulation launches: a layer that returns another shape than the labels'
+    (one that is no ManoSkin and names no n_verts cannot be asked beforehand) raises ValueError with no state touched.  With records on, records() gains mpvpe and pa_mpvpe.  model.get_vertices alone switches nothing on here."""
+
+    def __init__(self, model, mode: str = "test", breakdown: bool = False, records: int = 0, absolute=False, vertices: bool = False):
         self.model, self.mode = model, mode
+        self._vertices = bool(vertices)
+        self.n_verts: Optional[int] = None                               # Nv of the vertex state
+        self.vertex_state: Optional[torch.Tensor] = None
+        self.vertex_records: Optional[torch.Tensor] = None               # fp32 [records][2], NaN until a row is written
         self._absolute = _absolute_options(absolute)                     # None: off; forward_absolute's keywords otherwise
         self.absolute_state: Optional[torch.Tensor] = None
         self.thr_min, self.thr_max = float(model.auc_thresh[0]), float(model.auc_thresh[1])
@@ -261,24 +317,36 @@ class EpochEvaluator:
         self.record_rows = 0                                             # samples fed so far, counted on the host
         self._both: Optional[torch.Tensor] = None
 
-    def _state_on(self, dev: torch.device, views: Optional[int] = None) -> torch.Tensor:
+    def _state_on(self, dev: torch.device, views: Optional[int] = None, n_verts: Optional[int] = None) -> torch.Tensor:
         if self.state is None:
-            if not self._detail and self._absolute is None:
+            if not self._detail and self._absolute is None and not self._vertices:
                 self.state = torch.zeros(self.state_doubles, device=dev, dtype=torch.float64)
             else:
-                if views is None:
+                by_views = self._detail or self._absolute is not None
+                if by_views and views is None:
                     raise ValueError("the breakdown and absolute states are sized by V: a rank that saw no batch needs a model with num_views")
-                self.views = int(views)
+                if self._vertices and n_verts is None:
+                    raise ValueError("the vertex state is sized by Nv: a rank that saw no batch needs a model whose joints_to_vertices "
+                                     "has a mano.ManoSkin as its layer")
+                if by_views:
+                    self.views = int(views)
                 mid = self.state_doubles + (breakdown_doubles(self.views, STEPS) if self._detail else 0)
                 end = mid + (absolute_doubles(self.views) if self._absolute is not None else 0)
-                self._both = torch.zeros(end, device=dev, dtype=torch.float64)   # pooled | breakdown | absolute
+                if self._vertices:
+                    self.n_verts = int(n_verts)
+                total = end + (vertices_doubles(self.n_verts, STEPS) if self._vertices else 0)
+                self._both = torch.zeros(total, device=dev, dtype=torch.float64)   # pooled | breakdown | absolute | vertices
                 self.state = self._both[:self.state_doubles]
                 if self._detail:
                     self.breakdown_state = self._both[self.state_doubles:mid]
                 if self._absolute is not None:
-                    self.absolute_state = self._both[mid:]
+                    self.absolute_state = self._both[mid:end]
+                if self._vertices:
+                    self.vertex_state = self._both[end:]
                 if self.record_capacity:
                     self.record_table = torch.full((self.record_capacity, 4 + self.views), float("nan"), device=dev)
+                    if self._vertices:
+                        self.vertex_records = torch.full((self.record_capacity, 2), float("nan"), device=dev)
         elif self.state.device != dev:
             raise ValueError(f"this epoch's state is on {self.state.device}, the step on {dev}")
         return self.state
@@ -290,14 +358,34 @@ class EpochEvaluator:
         if self.record_capacity and self.record_rows + B > self.record_capacity:
             raise ValueError(f"{self.record_rows} + {B} samples do not fit the {self.record_capacity} record rows of this evaluator")
 
+    def _check_vertices(self, inputs: dict) -> int:
+        """What the vertex path cannot run without, in front of every launch of the step; returns the labels' Nv."""
+        if getattr(self.model, "joints_to_vertices", None) is None:
+            raise ValueError("vertex evaluation needs model.joints_to_vertices = ik.JointsToVertices(mano.ManoSkin(mano.ManoParams(...)))")
+        gt = inputs.get("vertices")
+        if not isinstance(gt, torch.Tensor):
+            raise ValueError("vertex evaluation needs inputs['vertices'], the labelled mesh [B, Nv, 3] in millimetres")
+        if gt.dim() != 3 or gt.shape[2] != 3 or not 1 <= gt.shape[1] <= 4096:
+            raise ValueError(f"inputs['vertices'] must be [B, Nv, 3] with 1 .. 4096 vertices, got {list(gt.shape)}")
+        nv = int(gt.shape[1])
+        if self.n_verts is not None and nv != self.n_verts:
+            raise ValueError(f"this epoch's vertex state was begun with {self.n_verts} vertices, the step has {nv}")
+        layer_nv = getattr(getattr(self.model.joints_to_vertices, "mano_layer", None), "n_verts", None)
+        if layer_nv is not None and int(layer_nv) != nv:
+            raise ValueError(f"model.joints_to_vertices makes {int(layer_nv)} vertices, inputs['vertices'] has {nv}")
+        return nv
+
     def add(self, out: dict, inputs: dict, cam_params, view_mask=None) -> None:
         """One step from the forward's `out` and the labels as _eval_step passes them (joints_cam / root_joint in metres): the loss
         when the batch carries loss labels, then one hmv_eval_add on the current stream.  Returns nothing; nothing reaches the host.
         view_mask (bool [B, V], True = present): `out` is forward_views' and the step is a ragged one -- the ragged loss and
         hmv_eval_add_views; rows of absent views are not read.
         With absolute on, `out` is forward_absolute's (details=True adds the reprojection and inlier tables; without them R, RN and H
-        stay as they are) and inputs["root_joint"] [B, 1, 3] is read: one hmv_eval_absolute_add behind the others."""
-        if self._absolute is not None:   # before anything is launched
+        stay as they are) and inputs["root_joint"] [B, 1, 3] is read: one hmv_eval_absolute_add behind the others.
+        With vertices on, out["vertices"] = model.joints_to_vertices(out["joints_cam"] * 1000) and inputs["vertices"] [B, Nv, 3]
+        (millimetres) is read: one hmv_eval_vertices_add behind the others."""
+        nv = self._check_vertices(inputs) if self._vertices else None   # before anything is launched
+        if self._absolute is not None:
             if "joints_tri" not in out or "tri_status" not in out:
                 raise ValueError("absolute evaluation needs forward_absolute's output: `out` has no joints_tri / tri_status")
             if "root_joint" not in inputs:
@@ -310,12 +398,29 @@ class EpochEvaluator:
         if pc.dim() != 3 or tuple(pc.shape[1:]) != (21, 3) or gc.shape != pc.shape:
             raise ValueError("joints_cam must be [B, 21, 3] in the output and in the labels")
         B = pc.shape[0]
+        if self._vertices and inputs["vertices"].shape[0] != B:
+            raise ValueError(f"inputs['vertices'] must be [{B}, Nv, 3], got {list(inputs['vertices'].shape)}")
         if p2.dim() != 4 or p2.shape[0] != B or tuple(p2.shape[2:]) != (21, 2) or g2.shape != p2.shape:
             raise ValueError(f"joints_crop_img must be [{B}, V, 21, 2] in the output and in the labels")
         V = p2.shape[1]
         if self._detail or self._absolute is not None:
             self._check_detail(B, V)
         keep = [pc, p2, gc, g2]
+        if self._vertices:   # the mesh first: a layer that returns another shape is refused before any state is touched
+            from .mano import ManoSkin
+            j2v = self.model.joints_to_vertices
+            with torch.cuda.device(dev):
+                pv = j2v(pc * 1000).detach().contiguous().float()        # hand_ik and the skin: the mesh stays on the device
+            gv = _device_f32("inputs['vertices']", inputs["vertices"], dev)
+            if pv.shape != gv.shape:
+                raise ValueError(f"model.joints_to_vertices returned {list(pv.shape)}, inputs['vertices'] is {list(gv.shape)}")
+            out["vertices"] = pv
+            vstatus = j2v.last_status.to(torch.int32)
+            layer = getattr(j2v, "mano_layer", None)
+            if isinstance(layer, ManoSkin) and layer.last_status is not None:
+                vstatus = vstatus | layer.last_status.to(torch.int32)   # on the device: nothing is read back
+            vstatus = vstatus.contiguous()
+            keep += [pv, gv, vstatus]
         if self._absolute is not None:
             tri = _device_f32("out['joints_tri']", out["joints_tri"], dev)
             status = out["tri_status"].detach().to(dev).to(torch.int32).contiguous()
@@ -351,10 +456,11 @@ class EpochEvaluator:
             loss = self.model.last_loss_vector
             a.loss_result = loss.data_ptr()
             keep.append(loss)
-        state = self._state_on(dev, V)
+        state = self._state_on(dev, V, nv)
         a.state, a.state_doubles = state.data_ptr(), state.numel()
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         present = None
+        record_base = self.record_rows
         with torch.cuda.device(dev):
             if view_mask is None:
                 rc = _lib.load().hmv_eval_add(_index(dev), ctypes.byref(a), stream)
@@ -386,6 +492,19 @@ class EpochEvaluator:
                 w.inliers = None if inl is None else inl.data_ptr()
                 w.state, w.state_doubles = self.absolute_state.data_ptr(), self.absolute_state.numel()
                 _lib.check(_lib.load().hmv_eval_absolute_add(_index(dev), ctypes.byref(w), stream))
+            if self._vertices:
+                lib = _lib.load()
+                scratch = torch.empty(int(lib.hmv_eval_vertices_scratch_bytes(B, nv, STEPS)) // 8, device=dev, dtype=torch.float64)
+                m = _lib.HmvEvalVerticesArgs()
+                m.struct_size = ctypes.sizeof(_lib.HmvEvalVerticesArgs)
+                m.B, m.n_verts, m.steps, m.thr_min, m.thr_max, m.unit_div = B, nv, STEPS, self.thr_min, self.thr_max, 1000.0
+                m.pred_vertices, m.gt_vertices, m.status = pv.data_ptr(), gv.data_ptr(), vstatus.data_ptr()
+                m.state, m.state_doubles = self.vertex_state.data_ptr(), self.vertex_state.numel()
+                m.scratch, m.scratch_bytes = scratch.data_ptr(), scratch.numel() * 8
+                if self.vertex_records is not None:
+                    m.records, m.record_capacity, m.record_base = self.vertex_records.data_ptr(), self.record_capacity, record_base
+                _lib.check(lib.hmv_eval_vertices_add(_index(dev), ctypes.byref(m), stream))
+                keep.append(scratch)
         del keep   # allocated on the stream the kernel runs on: the caching allocator reuses them in stream order
 
     def step(self, batch: dict) -> dict:
@@ -393,6 +512,8 @@ class EpochEvaluator:
         inputs["joints_cam"] / ["root_joint"] from mm to metres IN PLACE.  Returns the forward's output dictionary."""
         inputs = batch["data"]
         view_mask = batch.get("view_mask")
+        if self._vertices:   # before anything is launched
+            self._check_vertices(inputs)
         if self._absolute is not None:
             cam_params = batch.get("cam_params")
             if "root_joint" not in inputs or cam_params is None or "extrinsic" not in cam_params:   # before anything is launched
@@ -416,7 +537,9 @@ class EpochEvaluator:
         """One all_reduce(SUM) of the state over `group`: afterwards every rank holds the global sums.  A rank that saw no batch
         takes part with a zero state."""
         if self.state is None:
-            self._state_on(torch.device("cuda", torch.cuda.current_device()), getattr(self.model, "num_views", None))
+            layer = getattr(getattr(self.model, "joints_to_vertices", None), "mano_layer", None)
+            self._state_on(torch.device("cuda", torch.cuda.current_device()), getattr(self.model, "num_views", None),
+                           getattr(layer, "n_verts", None))
         if self._both is None:
             reduce_state(self.state, group)
             return
@@ -426,37 +549,48 @@ class EpochEvaluator:
             self.breakdown_state[3].fill_(float(STEPS))
         if self._absolute is not None:
             self.absolute_state[2].fill_(float(self.views))
+        if self._vertices:
+            self.vertex_state[2].fill_(float(self.n_verts))    # n_verts and S are not sums either
+            self.vertex_state[3].fill_(float(STEPS))
 
     def compute(self) -> dict:
         """ONE device->host copy of the state, the rest on the host (finish_state).  {mode}_mpjpe / {mode}_pa_mpjpe in millimetres,
         {mode}_mpjpe2d in crop pixels, {mode}_pck_j (list), {mode}_auc_j, {mode}_norm_auc_j, thresholds (list), {mode}/heatmap_loss
         ... {mode}/p2d_loss, {mode}/root_3d_loss, {mode}/loss (None when no step carried a loss), samples, steps.
-        With breakdown=True also finish_breakdown's keys, with absolute on also finish_absolute's, from the same copy.
-        Raises ValueError for an empty epoch."""
-        if not self.breakdown and self._absolute is None:
+        With breakdown=True also finish_breakdown's keys, with absolute on also finish_absolute's, with vertices on also
+        finish_vertices', from the same copy.  Raises ValueError for an empty epoch."""
+        if not self.breakdown and self._absolute is None and not self._vertices:
             host = np.zeros(self.state_doubles) if self.state is None else self.state.cpu().numpy()
             return finish_state(host, self.thr_min, self.thr_max, STEPS, self.mode)
         if self.state is None:
             raise ValueError("empty epoch: no step was added")
         host = self._both.cpu().numpy()           # still ONE copy: the states are one tensor
         out = finish_state(host[:self.state_doubles], self.thr_min, self.thr_max, STEPS, self.mode)
+        end = host.size - (vertices_doubles(self.n_verts, STEPS) if self._vertices else 0)
         if self.breakdown:
             mid = self.state_doubles + breakdown_doubles(self.views, STEPS)
             out.update(finish_breakdown(host[self.state_doubles:mid], self.thr_min, self.thr_max, STEPS, self.mode))
         if self._absolute is not None:
-            out.update(finish_absolute(host[host.size - absolute_doubles(self.views):], self.mode))
+            out.update(finish_absolute(host[end - absolute_doubles(self.views):end], self.mode))
+        if self._vertices:
+            out.update(finish_vertices(host[end:], self.thr_min, self.thr_max, STEPS, self.mode))
         return out
 
     def records(self) -> dict:
         """ONE device->host copy of the record rows filled so far, in feed order, as numpy arrays: mpjpe and pa_mpjpe [n] in
         millimetres, mpjpe2d [n] in crop pixels (the sample's own value over its present views), views [n] (int), and
-        mpjpe2d_per_camera [n, V] with NaN for an absent camera.  This rank's samples only."""
+        mpjpe2d_per_camera [n, V] with NaN for an absent camera; with vertices on also mpvpe and pa_mpvpe [n] in millimetres, NaN for
+        a skipped sample.  This rank's samples only."""
         if not self.record_capacity:
             raise ValueError("this evaluator was built with records=0")
         n = min(self.record_rows, self.record_capacity)
         rows = np.zeros((0, 4 + (self.views or 0))) if self.record_table is None else self.record_table[:n].cpu().numpy().astype(np.float64)
-        return {"mpjpe": rows[:, 0] * 1000, "pa_mpjpe": rows[:, 1] * 1000, "mpjpe2d": rows[:, 2].copy(), "views": rows[:, 3].astype(np.int64),
-                "mpjpe2d_per_camera": rows[:, 4:].copy()}
+        out = {"mpjpe": rows[:, 0] * 1000, "pa_mpjpe": rows[:, 1] * 1000, "mpjpe2d": rows[:, 2].copy(), "views": rows[:, 3].astype(np.int64),
+               "mpjpe2d_per_camera": rows[:, 4:].copy()}
+        if self._vertices:
+            mesh = np.zeros((0, 2)) if self.vertex_records is None else self.vertex_records[:n].cpu().numpy().astype(np.float64)
+            out["mpvpe"], out["pa_mpvpe"] = mesh[:, 0] * 1000, mesh[:, 1] * 1000
+        return out
 
     def reset(self) -> None:
         """An empty epoch again (a zero state is one)."""
@@ -466,4 +600,6 @@ class EpochEvaluator:
             self.state.zero_()
         if self.record_table is not None:
             self.record_table.fill_(float("nan"))
+        if self.vertex_records is not None:
+            self.vertex_records.fill_(float("nan"))
         self.record_rows = 0

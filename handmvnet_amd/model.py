@@ -691,7 +691,8 @@ class HandMvNet(torch.nn.Module):
         """handmvnet.py:493-517: metric keys carry the "test_" prefix."""
         return self._eval_step(batch, "test")
 
-    def evaluate(self, batches, mode: str = "test", group=None, breakdown: bool = False, records: int = 0, absolute=False) -> dict:
+    def evaluate(self, batches, mode: str = "test", group=None, breakdown: bool = False, records: int = 0, absolute=False,
+                 vertices: bool = False) -> dict:
         """What trainer.test(model, dm) / trainer.validate hand back (eval.py): the epoch's numbers over every batch of `batches`.
         Each step enqueues forward, loss and one accumulation launch and copies nothing to the host; one all-reduce combines the ranks
         when a process group is initialised; one readback ends the epoch.  Every value is sum(B x step value) / sum(B) over steps and
@@ -706,9 +707,14 @@ class HandMvNet(torch.nn.Module):
         every step runs forward_absolute and one more accumulation launch (hmv_eval_absolute_add), and the result gains
         evaluation.finish_absolute's keys -- {mode}_w_mpjpe, {mode}_root_err, the triangulation's own error, its status counts, the
         reprojection error per camera and the inlier histogram; every batch then needs inputs["root_joint"] and
-        cam_params["extrinsic"], in the frame forward_absolute reports in.  With the defaults the result is what it always was."""
+        cam_params["extrinsic"], in the frame forward_absolute reports in.
+        vertices=True: every step takes joints_cam to its MANO mesh (self.joints_to_vertices) and runs one more accumulation entry
+        (hmv_eval_vertices_add) against inputs["vertices"] [B, Nv, 3] in millimetres; the result gains the mesh block of test_step --
+        {mode}_mpvpe, {mode}_pa_mpvpe, {mode}_pck_v, {mode}_auc_v, {mode}_norm_auc_v -- over the whole split, and
+        evaluation.finish_vertices' per-vertex errors and counts.  get_vertices alone does not switch it on.
+        With the defaults the result is what it always was."""
         from .evaluation import EpochEvaluator
-        ev = EpochEvaluator(self, mode, breakdown=breakdown, records=records, absolute=absolute)
+        ev = EpochEvaluator(self, mode, breakdown=breakdown, records=records, absolute=absolute, vertices=vertices)
         for batch in batches:
             ev.step(batch)
         if torch.distributed.is_available() and torch.distributed.is_initialized():

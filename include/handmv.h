@@ -1035,6 +1035,79 @@ size_t hmv_eval_absolute_doubles(int32_t V);
  * state[2]; nothing is launched then and the state keeps its bytes. */
 int hmv_eval_absolute_add(int32_t device, const hmv_eval_absolute_args *args, void *stream);
 
+/* ---- vertex evaluation (the mesh block of _calculate_mpjpe over a whole split: MPVPE, PA-MPVPE, the vertex PCK curve) ----
+ * hmv_eval_vertices_add adds one step's predicted and labelled meshes -- what HandMvNet._calculate_mpjpe (handmvnet.py:389-408) hands
+ * to PoseMetrics as `vertices / 1000.` -- into a FOURTH caller-owned fp64 state, and optionally writes one fp32 record row per sample.
+ * The other states and their entries are untouched by it.  Every number is the reference's PoseMetrics.mpjpe /
+ * compute_similarity_transform / pck applied to [B][n_verts][3] point sets.
+ *
+ * A sample whose status is non-zero (hmv_op_hand_ik's or hmv_op_mano_skin's status of the row that made its mesh) is SKIPPED: its
+ * vertices are not read, it adds to [4] only, and its record row is NaN.  With status == NULL every sample is added, and a mesh
+ * with a NaN then makes the sums NaN, as it does in the reference.
+ *
+ * State layout: hmv_eval_vertices_doubles(n_verts, steps) = 8 + (S + 1) + 2 n_verts doubles, S = steps, additive element by element
+ * except [2] and [3]:
+ *   [0]   samples added (status 0)      [1]   steps added
+ *   [2]   n_verts      [3]   S          written by the first add (the one that finds [1] == 0), not added to afterwards, like [2]
+ *                                       and [3] of the breakdown state: whoever sums two states keeps them
+ *   [4]   samples skipped               [5]   vertex rows, [0] * n_verts
+ *   [6]   sum of the fp32 vertex distances (the units after unit_div: metres for millimetres and unit_div = 1000)
+ *   [7]   sum of the distances that remain after each mesh's similarity alignment (fp64)
+ *   H   [S + 1]     at [8]:  the PCK histogram of the fp32 distances, the bins of hmv_eval_add's [14 ..]; it sums to [5]
+ *   PV  [n_verts]   per vertex: sum over the added samples of its fp32 distance
+ *   PVA [n_verts]   per vertex: the same after the alignment
+ * [6] / [5] is the MPVPE, [7] / [5] the PA-MPVPE, the cumulative H over [5] the curve {mode}_pck_v.  Counts are integers held in
+ * doubles.  A zero-filled buffer is an empty epoch.
+ *
+ * Record row of sample b: two floats at records[(record_base + b) * 2]
+ *   [0]   the mean of its n_verts fp32 distances      [1]   that mean after its alignment
+ * each an fp64 mean rounded to fp32 once; both NaN for a skipped sample.  The caller counts samples on the host and passes the row of
+ * this step's sample 0, as for hmv_eval_breakdown_add.
+ *
+ * Both meshes are divided by unit_div first, every coordinate in fp32 and correctly rounded (the reference's `vertices / 1000.`);
+ * the distance is the fp32 one of the joint entries, the alignment their fp64 arithmetic on centred values.
+ *
+ * Two launches.  The first runs one workgroup per sample, all of whose lanes walk that sample's vertices: the meshes are staged in
+ * LDS once and read three times, one lane solves the 3x3 problem in between.  It leaves every vertex's two distances and the
+ * sample's partial sums in `scratch`.  The second, 1 + ceil(n_verts / 256) workgroups each the only writer of its slice, adds them
+ * onto the state one sample after the other in row order.  Every sum has a fixed order and there are no floating-point atomics; a
+ * sample's values depend neither on B nor on its row.  So two identical epochs give identical bits, and so do two epochs that cut
+ * the same samples, in the same order, into different batches -- in everything but [1], which counts the adds.
+ * The state belongs to one stream at a time, and the scratch to this call: it may be reused by the next call on the same stream.
+ * n_verts and steps of a later step cannot be compared with [2] and [3] without a synchronisation, so they are not: the caller keeps
+ * them the same. */
+typedef struct hmv_eval_vertices_args {
+    int32_t struct_size;            /* sizeof(hmv_eval_vertices_args), ABI guard */
+    int32_t B, n_verts;             /* samples, 1 .. 4096; vertices of a mesh, 1 .. 4096 (MANO: 778) */
+    int32_t steps;                  /* PCK thresholds, 1 .. 256 (the reference uses 20) */
+    float thr_min, thr_max;         /* thr_min <= thr_max, in the units AFTER unit_div */
+    float unit_div;                 /* finite and > 0; 1.0f leaves the coordinates alone */
+    const float *pred_vertices;     /* out["vertices"]    [B][n_verts][3] */
+    const float *gt_vertices;       /* inputs["vertices"] [B][n_verts][3] */
+    const int32_t *status;          /* device int32 [B]; may be NULL: every sample is added */
+    double *state;                  /* device, 8-byte aligned */
+    size_t state_doubles;           /* >= hmv_eval_vertices_doubles(n_verts, steps) */
+    void *scratch;                  /* device, 8-byte aligned; written by the call, nothing of it is kept */
+    size_t scratch_bytes;           /* >= hmv_eval_vertices_scratch_bytes(B, n_verts, steps) */
+    float *records;                 /* device fp32 [record_capacity][2]; may be NULL: no records, the next two are ignored */
+    int64_t record_capacity;        /* rows */
+    int64_t record_base;            /* the row of this step's sample 0 */
+} hmv_eval_vertices_args;
+
+/* Doubles in a vertex state: 8 + (steps + 1) + 2 n_verts (1585 for 778 vertices and 20 thresholds); 0 for n_verts outside 1 .. 4096
+ * or steps outside 1 .. 256. */
+size_t hmv_eval_vertices_doubles(int32_t n_verts, int32_t steps);
+
+/* Bytes of scratch one call takes: B (8 (steps + 4) + 12 n_verts); 0 for a B or n_verts outside 1 .. 4096 or steps outside 1 .. 256. */
+size_t hmv_eval_vertices_scratch_bytes(int32_t B, int32_t n_verts, int32_t steps);
+
+/* Adds one step, asynchronously on `stream`.  Every argument is checked before any HIP call, with hmv_eval_add's texts where the rule
+ * is the same: a NULL args, a wrong struct_size, B, n_verts or steps out of range, thr_max below thr_min, a unit_div that is not
+ * finite and > 0, a NULL pred_vertices / gt_vertices, a misaligned status, a NULL or misaligned state or scratch, a state_doubles or
+ * scratch_bytes below what the two functions above give, and with records hmv_eval_breakdown_add's rules for them return
+ * HMV_ERR_ARG with nothing launched. */
+int hmv_eval_vertices_add(int32_t device, const hmv_eval_vertices_args *args, void *stream);
+
 /* ---- sequence evaluation (a followed sequence, hmv_forward_frames_track: labels in the tracker's windows, jitter, window quality) ----
  * Under a tracker the windows are the tracker's own, so 2D labels expressed in dataset boxes do not belong to the predictions.  The
  * three entries below keep the evaluation of such a sequence on the device.  Stateless like the metrics, loss and track entries: a
